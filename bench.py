@@ -1,7 +1,7 @@
 """bench.py - triples/sec of the WGAN-GP "G+D step" (one critic update + one generator update on one minibatch,
 train.py:362-368 with CRITIC_ITERS = 1) on N MI355X GPUs of one node.
 
-  python bench.py --gpus 1 --steps K --warmup W [--config {1,3,4}]
+  python bench.py --gpus 1 --steps K --warmup W [--config {1,3,4}] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Default workload = BASELINE.json configs[1]: batch 64 per GPU, 224x224 synthetic images, vocab 1000, length-3 triples
@@ -12,6 +12,10 @@ gradient all-reduce over RCCL).  Inputs are resident in HBM before the timed reg
                         filter gradients beside the dgrad -> LayerNorm-backward chain - and a third for the recurrent heads' deferred
                         parameter-gradient work; bit-identical to the serial order), default conv
                         contraction mode (see DTYPE_NAME); config.schedule says so.  --single-stream times the serial order instead
+
+A plain run does only this: set-up, W warm-up steps, the K timed steps, the outputs of the last timed step written to DIR
+(--dump-outputs, see timed_path_outputs), the line.  Every record below is measured in --full runs only:
+
   serial                the same workload in the serial launch order, right after the timed region (kernels of two streams share the
                         chip, so only serial steps give per-kernel durations): its steps bracket the dominant convolution kernel's launches
   roofline              dominant convolution kernel against the MFMA peak (live HIP events around its launches in the `serial` steps;
@@ -114,6 +118,35 @@ def synth_inputs(B_global, S, V, n_draws, rank, world, device):
         g = torch.Generator().manual_seed(1000 + k)
         alphas.append(torch.rand((B_global,), generator=g)[sl].contiguous().to(device))
     return images, labels, noises, alphas
+
+
+# --dump-outputs: an array is written whole up to this many elements and as a fixed seeded sample of this many above it (seven
+# arrays, five of which can be this large: at most 40 MiB in all)
+DUMP_MAX_ELEMS = 1 << 21
+
+
+def dump_sample(t, seed=0):
+    """t flattened to float32 on the host: whole up to DUMP_MAX_ELEMS elements, else the elements at DUMP_MAX_ELEMS sorted positions
+    drawn with replacement by a CPU generator seeded with `seed` - the same positions for every array of the same length."""
+    t = t.detach().reshape(-1)
+    if t.numel() > DUMP_MAX_ELEMS:
+        idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(seed)).sort().values
+        t = t[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def timed_path_outputs(gs):
+    """What a caller of the timed path holds after its last step, as {name: float32 array}: the losses of the last critic and the
+    last generator update (step.py: d_losses, g_losses), the generator's logits [B,3,V] of the last generator update, and per network
+    the parameters after its last Adam step and the gradients that step applied (every live tensor, in sorted TF-name order, so that
+    the arrays do not depend on the arena layout)."""
+    from sgg_amd.params import is_dead
+    out = {"d_losses": gs.d_losses, "g_losses": gs.g_losses, "fake_logits": gs.G.head.state(1, gs.B).OUT[0]}
+    for tag, net in (("G", gs.G), ("D", gs.D)):
+        names = sorted(n for n in net.arena.views if not is_dead(n))
+        out[tag + "_params"] = torch.cat([net.arena.views[n].reshape(-1) for n in names])
+        out[tag + "_grads"] = torch.cat([net.grads[n].reshape(-1) for n in names])
+    return {k: dump_sample(v) for k, v in out.items()}
 
 
 def summarise_timing(timing):
@@ -443,6 +476,13 @@ def main():
     ap.add_argument("--size", type=int, default=None)
     ap.add_argument("--vocab", type=int, default=None)
     ap.add_argument("--critic-iters", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (float32; timed_path_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything else the line can hold: serial leg, roofline, "
+                         "roofline_hbm, native_f32, critic_iters_10, cpu_baseline, parity, other_configs, rccl.  --cpu-rows, --f32-steps, "
+                         "--ci10-steps, --no-kernel-timing, --per-shape, --serial-steps, --other-configs, --other-oracle-rows and "
+                         "--bitwise-iters shape these legs and act in --full runs only")
     ap.add_argument("--cpu-rows", type=int, default=None, help="rows of the cpu_baseline / oracle-parity step (0 = skip; default: the "
                                                                "whole per-GPU batch up to 224x224, 16 rows at 448x448)")
     ap.add_argument("--f32-steps", type=int, default=10, help="steps of the native-f32 leg (0 = skip)")
@@ -472,6 +512,8 @@ def main():
                     help="N > 1: the ranks only meet (process group, one bucket-sized all-reduce through sgg_amd.dp, barrier) and rank 0 "
                          "prints the `rccl` record with value null - the launch path without a workload (CPU rehearsal over gloo)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -504,7 +546,10 @@ def main():
                  overlap_streams=two_stream, head_side_stream=None if args.head_side_stream is None else bool(args.head_side_stream))
     side_stream, head_stream = gs.side, gs.head_side
     kt = not args.no_kernel_timing
-    extra = (args.serial_steps + 2) + (2 if kt else 0) + (args.f32_steps + 1 if K.conv_precision != 0 else 0) + (4 if world > 1 else 0)
+    full = args.full
+    # (the draws are seeded per step index: the timed steps see the same inputs with and without --full)
+    extra = ((args.serial_steps + 2) + (2 if kt else 0) + (args.f32_steps + 1 if K.conv_precision != 0 else 0) + (4 if world > 1 else 0)
+             if full else 0)
     total_steps = args.warmup + args.steps
     images, labels, noises, alphas = synth_inputs(B * world, S, V, (total_steps + extra) * (CI + 1), rank, world, dev)
 
@@ -554,12 +599,17 @@ def main():
     dt, _ = timed(args.warmup, args.steps, False)
     d_losses, g_losses = gs.d_losses.cpu().tolist(), gs.g_losses.cpu().tolist()
     next_k = total_steps
+    if args.dump_outputs and rank == 0:       # (before any leg of --full changes the networks)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in timed_path_outputs(gs).items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
 
     # ---- the same workload in the serial launch order: per-kernel durations (kernels of two streams would share the chip).  One
     # step brackets every forward / dgrad convolution launch and names the dominant kernel (largest summed duration); the serial
     # steps then bracket only that kernel's launches (an event pair costs ~ 5 us); two more steps bracket every call.
     dt_ser, timing, timing_hbm, hbm_steps, dominant = None, None, None, 2, None
-    if args.serial_steps > 0:
+    if full and args.serial_steps > 0:
         set_schedule(False)
         if kt:
             torch.cuda.synchronize(dev)
@@ -630,7 +680,7 @@ def main():
                                     for k_, v in sorted(shp.items(), key=lambda kv: -kv[1][1])}
 
     # ---- N > 1: what RCCL saw, and how much of the gradient all-reduce is exposed (same ranks, reducer off) --------------
-    if world > 1:
+    if full and world > 1:
         import torch.distributed as dist
         gs.reducer = None
         one_step(next_k)
@@ -644,7 +694,7 @@ def main():
                            "ms_per_step_without_allreduce": ms_off, "allreduce_ms_exposed": ms_on - ms_off}
 
     # ---- the same workload in native f32 MFMA arithmetic, same run, same schedule (the reference arithmetic is IEEE fp32) ------
-    if K.conv_precision != 0 and args.f32_steps > 0:
+    if full and K.conv_precision != 0 and args.f32_steps > 0:
         main_prec = K.conv_precision
         st, _ = gs.generator_forward(images, noises[0])
         logits_main = st.OUT[0].clone()
@@ -678,7 +728,7 @@ def main():
                 "on": "generator logits [%d,3,%d] of the timed workload after the timed steps, same weights" % (B, V)}}
 
     # ---- secondary line: the reference flag's nominal CRITIC_ITERS = 10 (train.py:408): 10 critic updates + 1 generator update -----
-    if CI == 1 and args.ci10_steps > 0:
+    if full and CI == 1 and args.ci10_steps > 0:
         def iteration10(j):
             for i in range(10):
                 gs.critic_step(images, labels, noises[(j + i) % len(noises)], alphas[(j + i) % len(alphas)])
@@ -707,7 +757,7 @@ def main():
         default_workload = (B, S, V, CI) == CONFIGS[1] + (1,)
         del gs
         torch.cuda.empty_cache()
-        if world == 1 and rows > 0:
+        if full and world == 1 and rows > 0:
             try:
                 ncpu = len(os.sched_getaffinity(0))
             except AttributeError:
@@ -718,12 +768,12 @@ def main():
                                                head_side_stream=None if args.head_side_stream is None else bool(args.head_side_stream))
             out["cpu_baseline"] = cpu
             out.setdefault("parity", {}).update(par)
-        if world == 1 and two_stream and args.bitwise_iters > 0:
+        if full and world == 1 and two_stream and args.bitwise_iters > 0:
             bw = two_stream_bitwise_leg(K, B, S, V, iterations=args.bitwise_iters)
             out.setdefault("parity", {})["two_stream_bitwise_at_full_size"] = bw["equal"]
             out["parity"]["two_stream_bitwise_detail"] = bw
         # ---- the other single-GPU configs of BASELINE.json, observed in the same line (networks built and freed one after the other) --
-        if world == 1 and default_workload and args.other_configs > 0:
+        if full and world == 1 and default_workload and args.other_configs > 0:
             try:
                 ncpu = len(os.sched_getaffinity(0))
             except AttributeError:

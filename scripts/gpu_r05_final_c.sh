@@ -7,5 +7,5 @@ timeout -k 10 1000 python -m pytest tests -m gpu -q -x > gpurun_out/r05/pytest_g
 tail -2 gpurun_out/r05/pytest_gpu.log
 timeout -k 10 500 python bench.py --steps 20 --warmup 5 > gpurun_out/r05/bench_steps20_warmup5.json 2> gpurun_out/r05/bench_steps20_warmup5.err || { tail -20 gpurun_out/r05/bench_steps20_warmup5.err; echo "rc $?"; }
 head -c 250 gpurun_out/r05/bench_steps20_warmup5.json; echo
-timeout -k 10 500 python bench.py > gpurun_out/r05/bench.json 2> gpurun_out/r05/bench.err || { tail -20 gpurun_out/r05/bench.err; echo "rc $?"; }
+bash scripts/gpu_round.sh bench r05 > /dev/null || echo "rc $?"      # (the --full line, into bench.json of the same folder)
 head -c 250 gpurun_out/r05/bench.json; echo

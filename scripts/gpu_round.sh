@@ -15,11 +15,11 @@ case $STEP in
     timeout -k 10 1100 python -m pytest tests -m gpu -q -x -s > $O/pytest_gpu.log 2>&1 || { tail -40 $O/pytest_gpu.log; exit 1; }
     tail -5 $O/pytest_gpu.log ;;
   bench)
-    timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+    timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
     head -c 400 $O/bench.json ;;
   configs34)
-    timeout -k 10 500 python bench.py --config 3 > $O/bench_config3.json 2> $O/bench_config3.err || { tail -20 $O/bench_config3.err; exit 1; }
-    timeout -k 10 500 python bench.py --config 4 > $O/bench_config4.json 2> $O/bench_config4.err || { tail -20 $O/bench_config4.err; exit 1; }
+    timeout -k 10 500 python bench.py --full --config 3 > $O/bench_config3.json 2> $O/bench_config3.err || { tail -20 $O/bench_config3.err; exit 1; }
+    timeout -k 10 500 python bench.py --full --config 4 > $O/bench_config4.json 2> $O/bench_config4.err || { tail -20 $O/bench_config4.err; exit 1; }
     head -c 300 $O/bench_config3.json; echo; head -c 300 $O/bench_config4.json ;;
   stats)
     cd /tmp && export TMPDIR=/tmp

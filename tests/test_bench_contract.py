@@ -60,11 +60,41 @@ def test_exit_code_travels_in_the_json_line():
     assert bench.exit_code_from(1, None) == 1 and bench.exit_code_from(1, "not json") == 1 and bench.exit_code_from(0, json.dumps({"value": 1})) == 0
 
 
+def test_dump_outputs_are_the_last_step_and_fit_the_budget():
+    """--dump-outputs: float32 arrays of what the timed path holds after its last step (here one G+D step through the CPU reference
+    kernels); an array above DUMP_MAX_ELEMS elements becomes the same seeded sample every time, and all of them fit 64 MB at any size."""
+    import numpy as np
+    import torch
+    import sgg_amd  # noqa: F401
+    from oracle.kernels_ref import RefKernels
+    from sgg_amd.params import init_state_dict
+    from sgg_amd.step import GanStep
+    B, S, V = 2, 32, 11
+    gs = GanStep(RefKernels(), V, S, B, lam=10.0, g_state=init_state_dict("G", V, S), d_state=init_state_dict("D", V, S))
+    images, labels, noises, alphas = bench.synth_inputs(B, S, V, 2, 0, 1, "cpu")
+    gs.critic_step(images, labels, noises[0], alphas[0])
+    gs.generator_step(images, noises[1])
+    gs.flush()
+    out = bench.timed_path_outputs(gs)
+    assert sorted(out) == ["D_grads", "D_params", "G_grads", "G_params", "d_losses", "fake_logits", "g_losses"]
+    assert all(a.dtype == np.float32 and a.ndim == 1 and np.isfinite(a).all() for a in out.values())
+    assert np.array_equal(out["d_losses"], gs.d_losses.numpy()) and np.array_equal(out["g_losses"], gs.g_losses.numpy())
+    assert np.array_equal(out["fake_logits"], gs.G.head.state(1, B).OUT[0].reshape(-1).numpy())
+    assert len(out["G_params"]) == len(out["D_grads"]) == bench.DUMP_MAX_ELEMS < gs.G.arena.live_param_count()
+    assert float(np.abs(out["G_grads"]).max()) > 0 and float(np.abs(out["D_grads"]).max()) > 0
+    again = bench.timed_path_outputs(gs)
+    assert all(np.array_equal(out[k], again[k]) for k in out)
+    t = torch.arange(1000, dtype=torch.float32)
+    assert np.array_equal(bench.dump_sample(t), t.numpy())
+    # losses whole, the other five arrays at most DUMP_MAX_ELEMS float32 each
+    assert 2 * 4 * 4 + 5 * bench.DUMP_MAX_ELEMS * 4 <= 64e6
+
+
 def test_cli_contract_flags_exist():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup", "--config", "--critic-iters", "--cpu-rows", "--f32-steps", "--serial-steps", "--single-stream",
-                 "--other-configs", "--other-oracle-rows", "--bitwise-iters"):
+                 "--other-configs", "--other-oracle-rows", "--bitwise-iters", "--full", "--dump-outputs"):
         assert flag in out.stdout
 
 
@@ -102,7 +132,7 @@ def test_bench_line_names_its_schedule_and_measures_the_roofline_in_serial_steps
     """The headline is the product's default (two-stream) schedule and says so; `roofline` comes from the serial leg, whose dominant
     kernel's launches per step times their average duration must fit inside a serial step (a rehearsal-sized workload)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4", "--size", "64",
-                          "--vocab", "50", "--cpu-rows", "4", "--f32-steps", "1", "--ci10-steps", "0", "--serial-steps", "2"],
+                          "--vocab", "50", "--cpu-rows", "4", "--f32-steps", "1", "--ci10-steps", "0", "--serial-steps", "2", "--full"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -124,3 +154,33 @@ def test_bench_line_names_its_schedule_and_measures_the_roofline_in_serial_steps
     assert one.returncode == 0, one.stderr[-3000:]
     rec1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     assert rec1["config"]["schedule"].startswith("serial") and "roofline" not in rec1
+
+
+@pytest.mark.gpu
+def test_plain_run_times_only_and_dumps_its_last_step(tmp_path):
+    """Without --full the line holds the timed region only, even with every leg's option at its default; --dump-outputs writes the
+    outputs of the last timed step, and two runs with the same arguments (same seeded inputs) write the same arrays."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4", "--size", "64", "--vocab", "50"]
+    recs = []
+    for run in ("a", "b"):
+        out = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        recs.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["higher_is_better"] is True
+    assert rec["metric"] == "triples/sec (G+D step)" and rec["unit"] == "triples/sec" and rec["dtype"] == bench.DTYPE_NAME[2]
+    assert not set(rec) & {"serial", "roofline", "roofline_hbm", "native_f32", "critic_iters_10", "cpu_baseline", "parity", "other_configs",
+                           "rccl"}, sorted(rec)
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(k + ".npy" for k in ("d_losses", "g_losses", "fake_logits", "G_params", "G_grads", "D_params", "D_grads"))
+    total = 0
+    for f in names:
+        a, b = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f
+        assert np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64e6
+    d, g = np.load(str(tmp_path / "a" / "d_losses.npy")), np.load(str(tmp_path / "a" / "g_losses.npy"))
+    assert d[0] == np.float32(rec["losses"]["disc_cost"]) and -g[3] == np.float32(rec["losses"]["gen_cost"])
+    assert np.load(str(tmp_path / "a" / "fake_logits.npy")).shape == (4 * 3 * 50,)
