@@ -577,16 +577,9 @@ __host__ __device__ constexpr int c3_tap_off(int k) { return k < 27 ? (k % 3) * 
 // conv1_1's output stores: the kernel is a 91 % WRITE stream (411 MB per launch at batch 64) of whole 128-byte lines.  Measured with
 // scripts/ubench/counter_calib.hip (profiles/r05_counter_calibration.log): a pure stream of 16-byte NONTEMPORAL stores sustains
 // 4.9 - 5.0 TB/s on this chip, default-policy stores 6.7 TB/s and more - the nontemporal hint that pays in the MFMA-bound epilogues
-// (SGG_CONV_NT_STORE) caps this kernel at its own store rate.  -DSGG_C3_NT_STORE=1 restores the hint.
-#ifndef SGG_C3_NT_STORE
-#define SGG_C3_NT_STORE 0
-#endif
+// (sgg_out_store4) caps this kernel at its own store rate, so it stores with the default policy.
 __device__ __forceinline__ void c3_out_store4(float* p, const f32x4& v) {     // p 16-byte aligned
-#if SGG_C3_NT_STORE
-  __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-#else
   *reinterpret_cast<f32x4*>(p) = v;
-#endif
 }
 
 __global__ __launch_bounds__(256, 4) void conv_c3_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -649,17 +642,12 @@ __global__ __launch_bounds__(256, 4) void conv_c3_fwd_kernel(const float* __rest
 #pragma unroll
     for (int r = 0; r < 16; ++r) out[m][r] = bv;
   const float* prow = patch + 2 * wave * PITCH + i;
-#ifndef C3_ABL_NOMFMA      // (timing-only ablations, wrong results: -DC3_ABL_NOMFMA no contraction, -DC3_ABL_NOSTORE no output stores)
 #pragma unroll
   for (int s = 0; s < 14; ++s) {
     const int ao = h ? c3_tap_off(2 * s + 1) : c3_tap_off(2 * s);
     out[0] = mfma32(prow[ao], wb[s], out[0]);
     out[1] = mfma32(prow[ao + PITCH], wb[s], out[1]);
   }
-#else
-  out[0][0] += prow[0];
-  out[1][0] += prow[PITCH];
-#endif
   // 16-byte stores through the in-register quad transpose (sgg_common.h): afterwards lane (h, g = i >> 2, k = i & 3) holds pixel
   // column 8 q + 4 h + k and output channels 4 g .. 4 g + 3
   const bool full = y0 + 8 <= H && x0 + 32 <= W;       // (uniform; edge tiles mask per element)
@@ -672,9 +660,6 @@ __global__ __launch_bounds__(256, 4) void conv_c3_fwd_kernel(const float* __rest
     for (int q = 0; q < 4; ++q) {
       float v0 = out[m][4 * q], v1 = out[m][4 * q + 1], v2 = out[m][4 * q + 2], v3 = out[m][4 * q + 3];
       sgg_quad_transpose4(v0, v1, v2, v3, lane);
-#ifdef C3_ABL_NOSTORE
-      if (v0 == 12345.678f)
-#endif
       if (full || (yy < H && 8 * q + (i & 3) < cmax)) c3_out_store4(ybase + 8 * q * COUT, f32x4{v0, v1, v2, v3});
     }
   }

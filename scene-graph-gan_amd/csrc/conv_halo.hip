@@ -19,30 +19,7 @@
 #include <type_traits>
 #include <stdlib.h>
 
-// -DSGG_HALO_PROFILE (scripts/build_prof_lib.sh): per-wave cycle accounting of the tap loop with explicit waits, summed into
-// sgg_halo_prof[] by wave 0 of every workgroup: {total, wait for B fragments (vmcnt), A fragment reads (issue + lgkmcnt),
-// MFMA issue, chunk boundary (patch write + barrier), epilogue, waves}.
-#ifdef SGG_HALO_PROFILE
-__device__ unsigned long long sgg_halo_prof[8];
-extern "C" int sgg_halo_prof_read(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(sgg_halo_prof), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(sgg_halo_prof), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#define PROF(...) __VA_ARGS__
-#else
-#define PROF(...)
-#endif
-
-#ifndef SGG_HALO_DB_MAX
-#define SGG_HALO_DB_MAX 65536   // two patch buffers when they fit in this many bytes of LDS (a gfx950 workgroup may use up to 160 KB; measured: see DESIGN.md)
-#endif
-#ifndef SGG_WIDE_STORE
-#define SGG_WIDE_STORE 1        // 16-byte output stores through an in-register quad transpose (sgg_common.h); 0: 4-byte stores
-#endif
+constexpr int SGG_HALO_DB_MAX = 65536;   // two patch buffers when they fit in this many bytes of LDS (a gfx950 workgroup may use up to 160 KB; measured: see DESIGN.md)
 #define HALO_PITCH 12
 #define HALO_BLKB (10 * HALO_PITCH * 64)   // bytes of one plane of one block's patch
 
@@ -53,17 +30,15 @@ __device__ __forceinline__ int halo_sw(int ry, int rx) { return ((rx >> 2) & 1) 
 // costs ~110 spilled VGPRs at the merge.
 // LNP: LN prologue - src is the producing layer's pre-LayerNorm output, normalised + ELU'd while the patch is staged.
 // ONE: single-piece mode (precision 1 / 4): one 16-bit plane, one MFMA per product.
-// WB: 8x8 blocks per wave.  1: a wave owns one block x WN columns (TM = 2 row tiles); 2: two blocks (TM = 4) - with WGM = 1, WGN = 4
-// the four waves of a workgroup take 32 output columns each of the SAME 128 pixels: a B fragment (L2 -> L1 -> registers, 64 B/clk
-// per CU) then feeds four row tiles instead of two, the A fragments (LDS, 256 B/clk per CU) are read by all four waves: the two
-// operand paths carry 4 KiB / 16 KiB per wave and tap instead of 8 / 8.  A fragments are then double-buffered per k-step
-// (a[k-step][tm]) instead of per tap, which keeps them at 64 registers.
+// PREFETCH, WB: always true / 1 (the next chunk's patch is loaded during the current one; a wave owns one 8x8 block x WN columns,
+// TM = 2 row tiles); kept as parameters so that the kernel names stay as they are.
 template <int NB, int BN, int WGM, int WGN, bool HALF, bool PREFETCH, bool ONECH, bool LNP, bool ONE = false, int WB = 1>
 __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParams p) {
+  static_assert(PREFETCH && WB == 1, "patch prefetch, one block per wave");
   constexpr int P = ONE ? 1 : 2;
   constexpr int WN = BN / WGN, TM = 2 * WB, TN = WN / 32;
   constexpr int THREADS = 64 * WGM * WGN;       // four waves (two workgroups per CU) or two (four workgroups per CU, one patch buffer)
-  static_assert((WGM * WGN == 4 || WGM * WGN == 2) && NB * 64 / WGM == 64 * WB && WN % 32 == 0 && TN >= 1 && (WB == 1 || WB == 2),
+  static_assert((WGM * WGN == 4 || WGM * WGN == 2) && NB * 64 / WGM == 64 * WB && WN % 32 == 0 && TN >= 1,
                 "a wave owns WB 8x8 blocks x WN columns");
   constexpr int PLANEB = NB * HALO_BLKB;
   constexpr int ITEMS = NB * 400;                       // (block, patch pixel, 8-channel group)
@@ -98,7 +73,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
     eb = scale_exp_from_amax(*p.amax_w);
   }
   const float sa = ldexpf(1.f, ea);
-  PROF(unsigned long long pc_vm = 0, pc_lds = 0, pc_mfma = 0, pc_chunk = 0, pc_epi = 0; const unsigned long long pc_t0 = __builtin_readcyclecounter();)
 
   // ---- staging plan (static per thread): item -> offset relative to its block's patch origin, border bits, LDS offset ----
   unsigned it_rel[NPASS];
@@ -177,8 +151,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
       const unsigned off = bad ? SGG_OOB : b0 + it_rel[j];
       if constexpr (LNP) ld_bad |= (int)bad << j;
       const unsigned o0 = LNP ? off : stage_off0(off, p.src_s16);
-      pre[j][0] = buf_load4_aux<SGG_PATCH_LOAD_AUX>(rs_src, o0);
-      pre[j][1] = buf_load4_aux<SGG_PATCH_LOAD_AUX>(rs_src, LNP ? off + 16u : stage_off1(o0, p.src_s16));
+      pre[j][0] = buf_load4(rs_src, o0);
+      pre[j][1] = buf_load4(rs_src, LNP ? off + 16u : stage_off1(o0, p.src_s16));
     }
     if (++s_cc == nch) {        // advance to this workgroup's next tile
       s_cc = 0;
@@ -250,11 +224,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
   // waited for the loads it had just issued: the whole L2 latency exposed per tap.)
   // (Reading the A fragments of tap t+1 between the two k-steps of tap t - software pipelining inside the wave - was
   //  measured: no gain, 32 more VGPRs.)
-  // WB == 1: a[tap parity][tm][k-step][plane] (the fragments of tap t+1 are read between the two k-steps of tap t);
-  // WB == 2: a[k-step][tm][0][plane] (the fragments of k-step k+1 are read in front of the MFMAs of k-step k)
-  constexpr int AKS = WB == 1 ? 2 : 1;
-  u32x4 a[2][TM][AKS][P];
-  // A fragments of one tap from the resident patch: k-steps [ks0, ks0 + nks) into a[buf][tm][ks - (WB == 1 ? 0 : ks0)]
+  // a[tap parity][tm][k-step][plane] (the fragments of tap t+1 are read between the two k-steps of tap t)
+  u32x4 a[2][TM][2][P];
+  // A fragments of one tap from the resident patch, k-steps [ks0, ks0 + nks) (read_a takes both; folding this helper into it changes
+  // the compiler's register allocation of the kernel)
   auto read_a_ks = [&](auto buf_c, int tap, auto ks0_c, auto nks_c) {
     constexpr int buf = decltype(buf_c)::value, ks0 = decltype(ks0_c)::value, nks = decltype(nks_c)::value;
     const int kh = tap / 3, kw = tap % 3;
@@ -273,111 +246,63 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
       for (int ks = ks0; ks < ks0 + nks; ++ks)
 #pragma unroll
         for (int pp = 0; pp < P; ++pp)
-          a[buf][tm][WB == 1 ? ks : 0][pp] = *reinterpret_cast<const u32x4*>(row + pp * PLANEB + (((2 * ks + h) ^ hs) << 4));
+          a[buf][tm][ks][pp] = *reinterpret_cast<const u32x4*>(row + pp * PLANEB + (((2 * ks + h) ^ hs) << 4));
     }
   };
   auto read_a = [&](auto buf_c, int tap) { read_a_ks(buf_c, tap, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{}); };
   auto mma_kstep = [&](auto par_c, auto ks_c) {
     constexpr int par = decltype(par_c)::value, ks = decltype(ks_c)::value;
-    constexpr int ab = WB == 1 ? par : ks, ak = WB == 1 ? ks : 0;
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn) {
         f32x16 d = acc[tm][tn];
         if constexpr (P == 2) {
-          d = mfma16<HALF>(a[ab][tm][ak][1], rb[par][tn][ks][0], d);
-          d = mfma16<HALF>(a[ab][tm][ak][0], rb[par][tn][ks][1], d);
+          d = mfma16<HALF>(a[par][tm][ks][1], rb[par][tn][ks][0], d);
+          d = mfma16<HALF>(a[par][tm][ks][0], rb[par][tn][ks][1], d);
         }
-        d = mfma16<HALF>(a[ab][tm][ak][0], rb[par][tn][ks][0], d);
+        d = mfma16<HALF>(a[par][tm][ks][0], rb[par][tn][ks][0], d);
         acc[tm][tn] = d;
       }
   };
   auto tap_body = [&](auto par_c, auto tap_c, int cc) {
     constexpr int par = decltype(par_c)::value, tap = decltype(tap_c)::value;
     const int ncc = (cc + 1 == nch) ? 0 : cc + 1;         // (the chunk after the last one re-reads valid weights)
-#ifndef SGG_ABL_NOB
     load_b(std::integral_constant<int, par ^ 1>{}, tap == 8 ? ncc : cc, tap == 8 ? 0 : tap + 1);
-#endif
-#ifndef SGG_ABL_NOSTAGE
-    if constexpr (PREFETCH && tap == 6) stage_load();
-#endif
+    if constexpr (tap == 6) stage_load();
     __builtin_amdgcn_sched_barrier(0);
     // DB: the next chunk's patch (loads issued at tap 6) is split and written to the other buffer inside the last tap's
     // scheduling region, so its ~170 VALU instructions issue in the shadow of this tap's MFMAs
-#ifndef SGG_ABL_NOSTAGE
-    if constexpr (DB && PREFETCH && tap == 8) stage_write(lds + (cur ^ 1) * (P * PLANEB));
-#endif
-#ifdef SGG_HALO_PROFILE
-    const unsigned long long q0 = __builtin_readcyclecounter();
-    if constexpr (PREFETCH && (tap == 6 || tap == 7)) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    const unsigned long long q1 = __builtin_readcyclecounter();
-    pc_vm += q1 - q0;
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    // A fragments of tap t+1 are read between the two k-steps of tap t (the in-kernel profile shows 11 % of a wave's time
-    // in issue + wait of these reads when they sit in front of the MFMAs)
-    PROF(const unsigned long long q2 = __builtin_readcyclecounter();)
-    if constexpr (WB == 2) {
-      // k-step granular: [read k-step 1 of this tap] MFMAs of k-step 0 [read k-step 0 of the next tap] MFMAs of k-step 1
-#ifndef SGG_ABL_NOA
-      read_a_ks(std::integral_constant<int, 1>{}, tap, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-      SGG_PRIO_HI();
-      mma_kstep(par_c, std::integral_constant<int, 0>{});
-      __builtin_amdgcn_sched_barrier(0);
-#ifndef SGG_ABL_NOA
-      if constexpr (tap < 8) read_a_ks(std::integral_constant<int, 0>{}, tap + 1, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-      mma_kstep(par_c, std::integral_constant<int, 1>{});
-      SGG_PRIO_LO();
-      __builtin_amdgcn_sched_barrier(0);
-    } else {
+    if constexpr (DB && tap == 8) stage_write(lds + (cur ^ 1) * (P * PLANEB));
+    // A fragments of tap t+1 are read between the two k-steps of tap t (an in-kernel profile showed 11 % of a wave's time
+    // in issue + wait of these reads when they sat in front of the MFMAs)
     SGG_PRIO_HI();
     mma_kstep(par_c, std::integral_constant<int, 0>{});
     __builtin_amdgcn_sched_barrier(0);
-    PROF(const unsigned long long q3 = __builtin_readcyclecounter();)
-#ifndef SGG_ABL_NOA
     if constexpr (tap < 8) read_a(std::integral_constant<int, par ^ 1>{}, tap + 1);
-#endif
     __builtin_amdgcn_sched_barrier(0);
-    PROF(const unsigned long long q4 = __builtin_readcyclecounter(); pc_lds += q4 - q3;)
     mma_kstep(par_c, std::integral_constant<int, 1>{});
     SGG_PRIO_LO();
     __builtin_amdgcn_sched_barrier(0);
-    PROF(pc_mfma += (__builtin_readcyclecounter() - q4) + (q3 - q2);)
-    }
   };
   auto chunk = [&](auto par0_c, int cc) {
     constexpr int par0 = decltype(par0_c)::value;
-#ifndef SGG_ABL_NOA
-    if constexpr (WB == 2) read_a_ks(std::integral_constant<int, 0>{}, 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-    else read_a(par0_c, 0);
-#endif
+    read_a(par0_c, 0);
 #define SGG_TAP(T) tap_body(std::integral_constant<int, (par0 + T) & 1>{}, std::integral_constant<int, T>{}, cc)
     SGG_TAP(0); SGG_TAP(1); SGG_TAP(2); SGG_TAP(3); SGG_TAP(4); SGG_TAP(5); SGG_TAP(6); SGG_TAP(7); SGG_TAP(8);
 #undef SGG_TAP
     // next chunk (of this tile or the first of the next tile): replace the resident patch
-    PROF(const unsigned long long qc = __builtin_readcyclecounter();)
     if constexpr (DB) {
-      if constexpr (!PREFETCH) stage_write(lds + (cur ^ 1) * (P * PLANEB));   // nobody reads the other buffer since the previous barrier
-#ifndef SGG_ABL_NOSTAGE
       cur ^= 1;
-#endif
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     } else {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-      if constexpr (!PREFETCH) stage_load();
       stage_write(lds);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     }
-    PROF(pc_chunk += __builtin_readcyclecounter() - qc;)
   };
 
   // this wave's output block: global block row and column, advanced by NB per tile
@@ -390,12 +315,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
   }
   // per-lane byte offset inside a block.  After the quad transpose of the accumulators (sgg_quad_transpose4) lane (h, g, k) =
   // (lane >> 5, (lane & 31) >> 2, lane & 3) holds pixel column 4h + k of a block row and output channels 4g .. 4g+3 of its 32-column
-  // group: one 16-byte store per four accumulator registers (SGG_WIDE_STORE 0: the accumulators as they stand, 4 bytes per lane)
-#if SGG_WIDE_STORE
+  // group: one 16-byte store per four accumulator registers
   const unsigned o_lane_b = (unsigned)(((4 * h + (lane & 3)) * p.out_ps) + ((lane & 31) >> 2) * 4) * 4u;
-#else
-  const unsigned o_lane_b = (unsigned)((4 * h * p.out_ps) + (lane & 31)) * 4u;
-#endif
   int o_goff[TN];                                                                   // float offset of this wave's 32-column groups
 #pragma unroll
   for (int tn = 0; tn < TN; ++tn) {
@@ -414,19 +335,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
   stage_write(lds);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  // Timing-only ablation builds (scripts/build_variant_lib.sh <name> -DSGG_ABL_...; results are WRONG): the tap loop without its
-  // B-fragment loads (NOB), its A-fragment reads (NOA), its patch staging (NOSTAGE) or the tile epilogue's stores / statistics
-  // (NOEPI) - the operands are fetched once here and stay in registers, so the loop's MFMA stream is unchanged.
-#ifdef SGG_ABL_NOB
-  load_b(std::integral_constant<int, 1>{}, 0, 1);
-#endif
-#ifdef SGG_ABL_NOA
-  read_a(std::integral_constant<int, 0>{}, 0);
-  read_a(std::integral_constant<int, 1>{}, 1);
-#endif
 
   auto epilogue = [&](int tile) {
-    PROF(const unsigned long long qe = __builtin_readcyclecounter();)
     // ---- tile epilogue: unscale, + bias, store; optionally this wave's LayerNorm partial statistics; clear ----------
     // (per block of the wave: wb = 0 .. WB-1, row tiles 2 wb and 2 wb + 1)
 #pragma unroll
@@ -448,13 +358,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
             acc[tm][tn][r] = v;
             lsum += v;
           }
-#if defined(SGG_ABL_NOEPI) || defined(SGG_ABL_NOSTORE)
-      if (p.B < 0)       // (never true: keeps the code, skips the stores and the statistics)
-#else
-      if (live)          // one uniform branch around all stores (a branch per store costs ~64 jumps per tile)
-#endif
-      {
-#if SGG_WIDE_STORE
+      if (live) {        // one uniform branch around all stores (a branch per store costs ~64 jumps per tile)
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
@@ -467,23 +371,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
               const size_t so = ((size_t)(t2 * 4 + q) * wn + o_goff[tn]) * sizeof(float);   // scalar: block row 4 t2 + q
               sgg_out_store4(reinterpret_cast<float*>(const_cast<char*>(ob) + so + o_lane_b), f32x4{v0, v1, v2, v3});
             }
-#else
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-          for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const size_t so = ((size_t)(t2 * 4 + (r >> 2)) * wn + (size_t)(r & 3) * p.out_ps + o_goff[tn]) * sizeof(float);   // scalar
-              sgg_out_store(reinterpret_cast<float*>(const_cast<char*>(ob) + so + o_lane_b), acc[2 * wb + t2][tn][r]);
-            }
-#endif
       }
-#if defined(SGG_ABL_NOEPI) || defined(SGG_ABL_NOSTATS)
-      if (p.B < 0) {
-#else
       if (p.tile_stats) {
-#endif
         // (count, mean, M2) of this wave's 64 pixels x WN channels (one 8x8 block: inside one sample); merged per sample
         // with Chan's formula by ln_apply_elu_kernel
         const float mean_w = wave_sum(lsum) * (1.f / (float)(64 * WN));
@@ -513,16 +402,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
       if (o_bx[wb] >= p.bw) { o_bx[wb] -= p.bw; ++o_grow[wb]; }
     }
     acc_zero<TM, TN>(acc);
-    PROF(pc_epi += __builtin_readcyclecounter() - qe;)
   };
 
   if constexpr (ONECH) {
     for (int tile = mt_begin; tile < mt_end; tile += 2 * tstride) {
-      if constexpr (!PREFETCH && DB) stage_load();
       chunk(std::integral_constant<int, 0>{}, 0);
       epilogue(tile);
       if (tile + tstride < mt_end) {
-        if constexpr (!PREFETCH && DB) stage_load();
         chunk(std::integral_constant<int, 1>{}, 0);
         epilogue(tile + tstride);
       }
@@ -530,25 +416,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_halo3_kernel(HaloParam
   } else {
     for (int tile = mt_begin; tile < mt_end; tile += tstride) {
       for (int cc = 0; cc < nch; cc += 2) {
-        if constexpr (!PREFETCH && DB) stage_load();
         chunk(std::integral_constant<int, 0>{}, cc);
-        if constexpr (!PREFETCH && DB) stage_load();
         chunk(std::integral_constant<int, 1>{}, cc + 1);
       }
       epilogue(tile);
     }
   }
-#ifdef SGG_HALO_PROFILE
-  if (tid == 0) {
-    atomicAdd(&sgg_halo_prof[0], __builtin_readcyclecounter() - pc_t0);
-    atomicAdd(&sgg_halo_prof[1], pc_vm);
-    atomicAdd(&sgg_halo_prof[2], pc_lds);
-    atomicAdd(&sgg_halo_prof[3], pc_mfma);
-    atomicAdd(&sgg_halo_prof[4], pc_chunk);
-    atomicAdd(&sgg_halo_prof[5], pc_epi);
-    atomicAdd(&sgg_halo_prof[6], 1ull);
-  }
-#endif
 }
 
 // f32 [taps][N][C] -> two 16-bit planes in MFMA B-fragment order [tap][C/32][N/32][k-step][plane][lane] x 16 B:
@@ -611,25 +484,13 @@ int sgg_halo_applicable(int KH, int KW, int stride, int H, int W, int C, int N, 
          sgg_prec_resident(precision);
 }
 
-// 64-column layers run on two-block workgroups (2 x 2 waves of 64 pixels x 32 columns, two patch buffers, prefetch); -DSGG_HALO_N64_NB2=0:
-// four-block ones (4 waves of 64 x 64, one buffer, no prefetch: 0.1 ms per step slower)
+// 128-column layers run on 2 x 2 waves of (one block x 64 columns).
+// 64-column layers run on two-block workgroups (2 x 2 waves of 64 pixels x 32 columns, two patch buffers); four-block ones were
+// 0.1 ms per step slower.
 // 32-column layers run on two-wave workgroups (two blocks, one 30 KB patch buffer, four workgroups per CU: four independent phases
-// instead of two hide each other's chunk boundaries and store drains); -DSGG_HALO_N32_W2=0: four-wave workgroups of four blocks
-// (0.1 ms per step slower)
-#ifndef SGG_HALO_N32_W2
-#define SGG_HALO_N32_W2 1
-#endif
-#ifndef SGG_HALO_N64_NB2
-#define SGG_HALO_N64_NB2 1
-#endif
-// 128-column layers: -DSGG_HALO_N128_WB2=1 = four waves of (two blocks x 32 columns) instead of 2 x 2 waves of (one block x 64 columns)
-#ifndef SGG_HALO_N128_WB2
-#define SGG_HALO_N128_WB2 0
-#endif
-int sgg_halo_stats_cols(int N) {
-  if (N % 128 == 0) return SGG_HALO_N128_WB2 ? 32 : 64;
-  return (N % (SGG_HALO_N64_NB2 ? 128 : 64) == 0) ? 64 : 32;
-}
+// instead of two hide each other's chunk boundaries and store drains); four-wave workgroups of four blocks were 0.1 ms per step
+// slower.
+int sgg_halo_stats_cols(int N) { return N % 128 == 0 ? 64 : 32; }
 
 void sgg_halo_launch(const HaloParams& p_, int precision, hipStream_t st) {
   if (p_.frag16) {       // w_split_layout 4 (128-column tiles, two-piece modes): producer / consumer workgroups, K = 32 MFMA shape
@@ -638,7 +499,7 @@ void sgg_halo_launch(const HaloParams& p_, int precision, hipStream_t st) {
   }
   HaloParams p = p_;
   const bool half = sgg_prec_half(precision), one = sgg_prec_one(precision);   // (the LN prologue exists in the two-piece modes only: callers check)
-#define SGG_HALO(NB, BN, WGM, WGN, PF, WB)                                                                   \
+#define SGG_HALO(NB, BN, WGM, WGN)                                                                           \
   do {                                                                                                       \
     const int mtiles = sgg_cdiv(p.nblk, NB), ntn = p.N / BN;                                                 \
     int per_xcd = sgg_cdiv(mtiles, 8) * ntn;       /* (tile, n-tile) pairs an XCD owns */                    \
@@ -649,26 +510,23 @@ void sgg_halo_launch(const HaloParams& p_, int precision, hipStream_t st) {
     const dim3 grid((unsigned)(8 * gx));                                                                     \
     const dim3 blk(64 * WGM * WGN);                                                                          \
     if (one) {                                                                                                                          \
-      if (half && p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, PF, true, false, true, WB>), grid, blk, 0, st, p);   \
-      else if (half) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, PF, false, false, true, WB>), grid, blk, 0, st, p);      \
-      else if (p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, PF, true, false, true, WB>), grid, blk, 0, st, p); \
-      else hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, PF, false, false, true, WB>), grid, blk, 0, st, p);               \
+      if (half && p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, true, false, true, 1>), grid, blk, 0, st, p);   \
+      else if (half) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, false, false, true, 1>), grid, blk, 0, st, p);      \
+      else if (p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, true, false, true, 1>), grid, blk, 0, st, p); \
+      else hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, false, false, true, 1>), grid, blk, 0, st, p);               \
     } else if (p.ln_stats) {                                                                                                            \
-      if (half && p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, PF, true, true, false, WB>), grid, blk, 0, st, p);   \
-      else if (half) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, PF, false, true, false, WB>), grid, blk, 0, st, p);      \
-      else if (p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, PF, true, true, false, WB>), grid, blk, 0, st, p); \
-      else hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, PF, false, true, false, WB>), grid, blk, 0, st, p);               \
-    } else if (half && p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, PF, true, false, false, WB>), grid, blk, 0, st, p); \
-    else if (half) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, PF, false, false, false, WB>), grid, blk, 0, st, p);       \
-    else if (p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, PF, true, false, false, WB>), grid, blk, 0, st, p);  \
-    else hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, PF, false, false, false, WB>), grid, blk, 0, st, p);                \
+      if (half && p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, true, true, false, 1>), grid, blk, 0, st, p);   \
+      else if (half) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, false, true, false, 1>), grid, blk, 0, st, p);      \
+      else if (p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, true, true, false, 1>), grid, blk, 0, st, p); \
+      else hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, false, true, false, 1>), grid, blk, 0, st, p);               \
+    } else if (half && p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, true, false, false, 1>), grid, blk, 0, st, p); \
+    else if (half) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, false, false, false, 1>), grid, blk, 0, st, p);       \
+    else if (p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, true, false, false, 1>), grid, blk, 0, st, p);  \
+    else hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, false, false, false, 1>), grid, blk, 0, st, p);                \
   } while (0)
-  if (p.N % 128 == 0 && SGG_HALO_N128_WB2) SGG_HALO(2, 128, 1, 4, true, 2);      // four waves x (two blocks x 32 columns)
-  else if (p.N % 128 == 0) SGG_HALO(2, 128, 2, 2, true, 1);
-  else if (p.N % 64 == 0 && SGG_HALO_N64_NB2) SGG_HALO(2, 64, 2, 2, true, 1);
-  else if (p.N % 64 == 0) SGG_HALO(4, 64, 4, 1, false, 1);      // (with PREFETCH: 35 spilled VGPRs at the 256-register budget of two waves per SIMD)
-  else if (SGG_HALO_N32_W2) SGG_HALO(2, 32, 2, 1, true, 1);
-  else SGG_HALO(4, 32, 4, 1, true, 1);
+  if (p.N % 128 == 0) SGG_HALO(2, 128, 2, 2);
+  else if (p.N % 64 == 0) SGG_HALO(2, 64, 2, 2);
+  else SGG_HALO(2, 32, 2, 1);
 #undef SGG_HALO
 }
 

@@ -27,21 +27,6 @@
 #define PC_BLKB (10 * PC_PITCH * 64)      // bytes of one plane of one block's patch
 #define PC_P 2
 #define PC_D 4                            // ring slots: the DMA of tap g + 4 is issued behind barrier g and must have landed by barrier g + 3
-#ifndef PC_INTERLEAVE
-#define PC_INTERLEAVE 1
-#endif
-// 1 (round 5): with the patch DMA (DMAP) the four producer waves split by ROLE - waves 4, 5 move the weight fragments of every tap,
-// waves 6, 7 the patch (one plane each), a few DMAs per tap over taps 0 .. 7 of the chunk before, waited for ONCE in front of that
-// chunk's last barrier.  vmcnt retires in order: with all four waves doing both, the first wait for a weight fragment behind a
-// patch DMA (tap 3) was a wait for the whole patch, i.e. the patch had three taps (~1.2 us) to arrive - a burst of 30 / 60 KB per CU
-// that every CU issues at the same tap; split, it has eight taps and is issued evenly.  0: every producer wave does both (round 4).
-#ifndef PC_SPLIT_PRODUCERS
-#define PC_SPLIT_PRODUCERS 1
-#endif
-// ... and the same split for the register-staged patch (f32 sources, the LN prologue): 0 = four waves doing both (round 3)
-#ifndef PC_SPLIT_PRODUCERS_REG
-#define PC_SPLIT_PRODUCERS_REG 1
-#endif
 // s_waitcnt immediate of gfx9 for vmcnt(n) alone (expcnt, lgkmcnt: no wait): vmcnt low 4 bits in [3:0], its high 2 bits in [15:14]
 constexpr int pc_vmcnt(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
 
@@ -69,12 +54,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
   constexpr int PC_PATCHB = PC_P * PC_PLANEB;           // one patch buffer
   constexpr int PC_SLOTB = (BN / 16) * 2048;            // one tap of weight fragments for BN columns: [n-tile BN / 16][plane 2][lane 64] x 16 B
   constexpr int PC_ITEMS = PC_NB * 400;
-  constexpr int PC_NPASS = (PC_ITEMS + 255) / 256;      // (block, patch pixel, 8-channel group) items over the 256 producer threads
-  constexpr int WQ = PC_SLOTB / 4096;                   // weight DMAs per producer wave and tap (1 KiB each)
   constexpr int DPP = PC_NB * 120 / 16;                 // patch DMAs per plane and chunk (16 slots of 64 B each): 15 / 30
-  constexpr int DPW = (DPP + 1) / 2;                    // ... of which a producer wave issues up to 8 / 15
-  constexpr int PQ = NB == 2 ? 8 : 16;                  // patch DMAs in a producer wave's queue per chunk (the rest: fillers)
-  constexpr int PLQ = DMAP ? PQ : 2 * PC_NPASS;         // patch loads / DMAs per chunk in the vmcnt queue of a producer wave
   // ONE __shared__ object: with the LayerNorm parameters in an array of their own the compiler waits vmcnt(0) - for every weight DMA
   // in flight - in front of each patch write (cdna_hip_programming.md, "a second __shared__ object beside the glds staging array")
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * PC_PATCHB + PC_D * PC_SLOTB + (LNP ? 4096 : 0) + (DMAP ? 1024 : 0)];
@@ -103,21 +83,16 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
 
   if (wave >= 4) {
     // =================================================================================================================
-    // PRODUCERS (waves 4-7, pt = 0 .. 255).  Patch: the patch of chunk c + 2 is LOADED at tap 0 of chunk c (two register sets), the
-    // patch of chunk c + 1 is split and WRITTEN at taps 1 .. 4 of chunk c: a load has at least ten taps to arrive before its first
-    // use, and three before the first weight-DMA wait that covers it (vmcnt retires in order).  Weights: tap (d_cc, d_tap) of the
-    // fragment stream -> ring slot by LDS-DMA, four of the tap's sixteen 1-KiB pieces per wave.
-    // That is the form every wave doing BOTH jobs takes (the code below the role branches; -DPC_SPLIT_PRODUCERS=0 /
-    // -DPC_SPLIT_PRODUCERS_REG=0).  Round 5 splits the four waves by ROLE instead - waves 4, 5 the weight fragments, waves 6, 7 the
-    // patch - in every variant: with both jobs in one queue the first wait for a weight fragment issued behind the patch loads is a
-    // wait for the whole patch.  (Round 3 had measured such a split 4 % slower with the LayerNorm prologue; with the weight waves'
-    // hand-counted vmcnt and the patch written one pass per tap it is the faster form there too: 346 -> 353 TFLOP/s, the step -0.17 ms,
-    // profiles/r05_split_producers_reg_ab.log.)
+    // PRODUCERS (waves 4-7), split by ROLE: waves 4, 5 move the weight fragments of every tap (tap (d_cc, d_tap) of the fragment
+    // stream -> ring slot by LDS-DMA), waves 6, 7 the patch.  vmcnt retires in order: with four waves doing both jobs (rounds 3, 4)
+    // the first wait for a weight fragment issued behind the patch loads was a wait for the whole patch - a burst of 30 / 60 KB per
+    // CU that every CU issued at the same tap.  Split, the patch has eight taps to arrive and is issued evenly (register-staged patch:
+    // 346 -> 353 TFLOP/s, the step -0.17 ms, profiles/r05_split_producers_reg_ab.log).
     // =================================================================================================================
-    const int pt = tid - 256, pw = wave - 4;
+    const int pw = wave - 4;
     const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.src), 0, p.src_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wfrag), 0, p.w_bytes, 0x00020000);
-    if constexpr (DMAP && PC_SPLIT_PRODUCERS) {
+    if constexpr (DMAP) {
       const unsigned w_slab2 = (unsigned)(p.N >> 5) * 4096u;
       if (pw < 2) {
         // ---- weight waves: half of every tap's slot each (W2 DMAs of 1 KiB per tap); in their queue nothing but these ----------------
@@ -242,8 +217,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
           cur ^= 1;
         }
       return;
-    }
-    if constexpr (!DMAP && PC_SPLIT_PRODUCERS_REG) {
+    } else {
       // ---- register-staged patch (f32 source, or the LN prologue on the producing layer's pre-LayerNorm y), roles split as above:
       // waves 4, 5 the weight fragments; waves 6, 7 (128 threads) the patch - chunk c + 2 is LOADED at tap 0 of chunk c (two register
       // sets), chunk c + 1 normalised / split and WRITTEN at taps 1 .. 7, one pass of 128 items per tap.  Their queue holds nothing but
@@ -351,8 +325,8 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
           const unsigned off = bad ? SGG_OOB : b0 + q_rel[j];
           if constexpr (LNP) q_bad[S] |= (int)bad << j;
           const unsigned o0 = LNP ? off : stage_off0(off, p.src_s16);
-          qre[S][j][0] = buf_load4_aux<SGG_PATCH_LOAD_AUX>(rs_src, o0);
-          qre[S][j][1] = buf_load4_aux<SGG_PATCH_LOAD_AUX>(rs_src, LNP ? off + 16u : stage_off1(o0, p.src_s16));
+          qre[S][j][0] = buf_load4(rs_src, o0);
+          qre[S][j][1] = buf_load4(rs_src, LNP ? off + 16u : stage_off1(o0, p.src_s16));
         }
         if (++s_cc == nch) {        // advance to this workgroup's next tile
           s_cc = 0;
@@ -416,7 +390,6 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
         __builtin_amdgcn_s_barrier();                          // ... behind barrier 8
         cur ^= 1;
       };
-#undef PC_QP_UNUSED
       for (int tile = mt_begin; tile < mt_end; tile += tstride)
         for (int cc = 0; cc < nch; cc += 2) {
           q_chunk(std::integral_constant<int, 0>{});
@@ -425,280 +398,6 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
 #undef PC_QP
       return;
     }
-    const float sa = ldexpf(1.f, ea);
-    if constexpr (LNP) {
-      for (int c = pt; c < p.ln_nc; c += 256) {
-        lnp_s[c] = p.ln_gamma[c];
-        lnp_s[512 + c] = p.ln_beta[c];
-      }
-    }
-    // ---- staging plan (static per thread): item -> offset relative to its block's patch origin, border bits, LDS offset ----
-    unsigned it_rel[PC_NPASS];
-    int it_meta[PC_NPASS];      // bits 0..19 LDS byte offset inside a plane, 20..23 border bits, 24 block, 26..27 channel group, 28 valid
-#pragma unroll
-    for (int j = 0; j < PC_NPASS; ++j) {
-      const int it = pt + 256 * j;
-      const int blk = (it / 400) % PC_NB, r = it % 400;
-      const int px = r >> 2, ch8 = r & 3;
-      const int ry = px / 10, rx = px % 10;
-      it_rel[j] = (unsigned)((ry * p.in_rs + rx * p.in_ps + ch8 * 8) * 4);
-      const int bits = (ry == 0) | ((ry == 9) << 1) | ((rx == 0) << 2) | ((rx == 9) << 3);
-      // (the register-staged patch - one block bit in it_meta - serves two-block tiles only: NB == 4 implies DMAP, static_assert above)
-      it_meta[j] = (blk * PC_BLKB + (ry * PC_PITCH + rx) * 64 + ((ch8 ^ pc_sw(ry, rx)) << 4)) | (bits << 20) | (blk << 24) |
-                   (ch8 << 26) | ((it < PC_ITEMS) << 28);
-    }
-    float ld_mu[2][PC_NB], ld_rs[2][PC_NB];
-    int ld_cc[2] = {0, 0}, ld_bad[2] = {0, 0};
-    int s_grow[PC_NB], s_by[PC_NB], s_bx[PC_NB];
-#pragma unroll
-    for (int j = 0; j < PC_NB; ++j) {
-      const int beta = mt_begin * PC_NB + j;
-      s_grow[j] = beta / p.bw;
-      s_bx[j] = beta % p.bw;
-      s_by[j] = s_grow[j] % p.bh;
-    }
-    int s_tile = mt_begin, s_cc = 0;
-    f32x4 pre[2][PC_NPASS][2];
-    // issue the global loads of the next (tile, chunk) patch of the stream into register set S; past the last tile: out-of-range offsets (zeros)
-    auto stage_load = [&](auto s_c) __attribute__((always_inline)) {
-      constexpr int S = decltype(s_c)::value;
-      unsigned base[PC_NB];
-      int bbits[PC_NB];
-#pragma unroll
-      for (int j = 0; j < PC_NB; ++j) {
-        const bool dead = (s_tile >= mt_end) | (s_tile * PC_NB + j >= p.nblk);
-        base[j] = (unsigned)(((s_grow[j] * 8 - 1) * p.in_rs + (s_bx[j] * 8 - 1) * p.in_ps + (s_cc >> 1) * p.in_cA + (s_cc & 1) * p.in_cB) * 4);
-        bbits[j] = dead ? 15 : ((s_by[j] == 0) | ((s_by[j] == p.bh - 1) << 1) | ((s_bx[j] == 0) << 2) | ((s_bx[j] == p.bw - 1) << 3));
-        if (dead) base[j] = SGG_OOB;
-      }
-      if constexpr (LNP) {
-        ld_cc[S] = s_cc;
-        ld_bad[S] = 0;
-#pragma unroll
-        for (int j = 0; j < PC_NB; ++j) {
-          int b = s_grow[j] / p.bh;
-          b = b < p.B ? b : p.B - 1;
-          ld_mu[S][j] = p.ln_stats[2 * b];
-          ld_rs[S][j] = p.ln_stats[2 * b + 1];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < PC_NPASS; ++j) {
-        const int blk = (it_meta[j] >> 24) & 1;
-        const unsigned b0 = blk ? base[1] : base[0];
-        const int bb = blk ? bbits[1] : bbits[0];
-        const bool bad = !((it_meta[j] >> 28) & 1) | ((((it_meta[j] >> 20) & 15) & bb) != 0) | (b0 == SGG_OOB);
-        const unsigned off = bad ? SGG_OOB : b0 + it_rel[j];
-        if constexpr (LNP) ld_bad[S] |= (int)bad << j;
-        const unsigned o0 = LNP ? off : stage_off0(off, p.src_s16);
-        pre[S][j][0] = buf_load4_aux<SGG_PATCH_LOAD_AUX>(rs_src, o0);
-        pre[S][j][1] = buf_load4_aux<SGG_PATCH_LOAD_AUX>(rs_src, LNP ? off + 16u : stage_off1(o0, p.src_s16));
-      }
-      if (++s_cc == nch) {        // advance to this workgroup's next tile
-        s_cc = 0;
-        s_tile += tstride;
-#pragma unroll
-        for (int j = 0; j < PC_NB; ++j) {
-          s_bx[j] += adv_cols;
-          s_grow[j] += adv_rows;
-          s_by[j] += adv_rows;
-          if (s_bx[j] >= p.bw) {
-            s_bx[j] -= p.bw;
-            ++s_grow[j];
-            ++s_by[j];
-          }
-          while (s_by[j] >= p.bh) s_by[j] -= p.bh;
-        }
-      }
-    };
-    // LN prologue of half `hf` (4 channels) of pass j of register set S, in place
-    auto stage_ln_half = [&](auto s_c, auto j_c, auto hf_c) __attribute__((always_inline)) {
-      constexpr int S = decltype(s_c)::value, j = decltype(j_c)::value, hf = decltype(hf_c)::value;
-      const int blk = (it_meta[j] >> 24) & 1;
-      const float mu = blk ? ld_mu[S][1] : ld_mu[S][0], rs = blk ? ld_rs[S][1] : ld_rs[S][0];
-      const int cb = ((ld_cc[S] * 32) & (p.ln_nc - 1)) + ((it_meta[j] >> 26) & 3) * 8 + 4 * hf;
-      ln_elu4(pre[S][j][hf], lnp_s + cb, lnp_s + 512 + cb, mu, rs, (ld_bad[S] >> j) & 1);
-    };
-    // split pass j of register set S (LNP: after both stage_ln_half) and write it into patch buffer `dst`
-    auto stage_write_pass = [&](auto s_c, auto j_c, unsigned char* dst) __attribute__((always_inline)) {
-      constexpr int S = decltype(s_c)::value, j = decltype(j_c)::value;
-      u32x4 pl[PC_P];
-      if constexpr (LNP || !HALF) split8<PC_P, HALF>(pre[S][j][0], pre[S][j][1], sa, pl);
-      else stage_planes<PC_P, HALF>(pre[S][j][0], pre[S][j][1], sa, p.src_s16, pl);
-      // (passes 0 .. 2 cover items 0 .. 767: always valid; the last pass holds 32 items)
-      if (j < PC_NPASS - 1 || ((it_meta[j] >> 28) & 1)) {
-#pragma unroll
-        for (int pp = 0; pp < PC_P; ++pp) *reinterpret_cast<u32x4*>(dst + pp * PC_PLANEB + (it_meta[j] & 0xfffff)) = pl[pp];
-      }
-    };
-    // ---- DMAP: the patch of one chunk = 2 planes x (NB * 120) slots (NB blocks of 10 rows x pitch 12) x 64 B = 2 x DPP DMA instructions of
-    // 16 slots; the two producer waves of a plane issue instructions [DPW h, DPW h + DPW) of it (h = pw & 1), padded with fillers to PQ
-    // per wave (a filler goes to a scratch KiB with out-of-range offsets: every wave issues exactly PQ, so one vmcnt protocol serves all
-    // four).  Lane l of an instruction writes LDS position l & 3 of slot 16 q + (l >> 2), so it FETCHES the piece the swizzle puts
-    // there: (l & 3) ^ pc_sw(ry, rx).
-    unsigned dm_rel[PQ];
-    int dm_meta[PQ];             // bits 0..3 border bits, 4..5 block, 6 valid
-    auto patch_dma = [&](unsigned char* dstbuf) __attribute__((always_inline)) {
-      unsigned base[PC_NB];
-      int bbits[PC_NB];
-#pragma unroll
-      for (int j = 0; j < PC_NB; ++j) {
-        const bool dead = (s_tile >= mt_end) | (s_tile * PC_NB + j >= p.nblk);
-        base[j] = (unsigned)(((s_grow[j] * 8 - 1) * p.in_rs + (s_bx[j] * 8 - 1) * p.in_ps + (s_cc >> 1) * p.in_cA + (s_cc & 1) * p.in_cB) * 4);
-        bbits[j] = dead ? 15 : ((s_by[j] == 0) | ((s_by[j] == p.bh - 1) << 1) | ((s_bx[j] == 0) << 2) | ((s_bx[j] == p.bw - 1) << 3));
-        if (dead) base[j] = SGG_OOB;
-      }
-      const int plane = pw >> 1, hh = pw & 1;
-      unsigned char* dst = dstbuf + plane * PC_PLANEB + hh * DPW * 1024;
-#pragma unroll
-      for (int k = 0; k < PQ; ++k) {
-        const int blk = (dm_meta[k] >> 4) & 3;
-        unsigned b0 = base[0];
-        int bb = bbits[0];
-#pragma unroll
-        for (int j = 1; j < PC_NB; ++j) {
-          b0 = blk == j ? base[j] : b0;
-          bb = blk == j ? bbits[j] : bb;
-        }
-        const bool bad = !((dm_meta[k] >> 6) & 1) | (((dm_meta[k] & 15) & bb) != 0) | (b0 == SGG_OOB);
-        const unsigned off = bad ? SGG_OOB : b0 + dm_rel[k];
-        // (instructions past the plane's last one, and past this wave's share, do not exist: all lanes invalid, sent to the scratch)
-        const bool real = k < DPW && hh * DPW + k < DPP;
-        unsigned char* d = real ? dst + k * 1024 : lds + sizeof(lds) - 1024;
-        // (the plane's byte offset as SCALAR offset: the immediate offset field would move the LDS address too, scripts/ubench/dma_oob.hip)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, (pc_lds_ptr)d, 16, off, plane * 64, 0, 0);
-      }
-      if (++s_cc == nch) {        // advance to this workgroup's next tile
-        s_cc = 0;
-        s_tile += tstride;
-#pragma unroll
-        for (int j = 0; j < PC_NB; ++j) {
-          s_bx[j] += adv_cols;
-          s_grow[j] += adv_rows;
-          s_by[j] += adv_rows;
-          if (s_bx[j] >= p.bw) {
-            s_bx[j] -= p.bw;
-            ++s_grow[j];
-            ++s_by[j];
-          }
-          while (s_by[j] >= p.bh) s_by[j] -= p.bh;
-        }
-      }
-    };
-    if constexpr (DMAP) {
-#pragma unroll
-      for (int k = 0; k < PQ; ++k) {
-        const int slot = 16 * (DPW * (pw & 1) + k) + (lane >> 2);      // slot inside the plane: [block][row 0..9][pitch 12]
-        const int blk = slot / 120 < PC_NB ? slot / 120 : PC_NB - 1, r = slot - 120 * blk;
-        const int ry = r / PC_PITCH, rx = r - ry * PC_PITCH;
-        const bool valid = k < DPW && slot < PC_NB * 120 && rx < 10;
-        const int piece = (lane & 3) ^ pc_sw(ry, rx);
-        dm_rel[k] = (unsigned)((ry * p.in_rs + rx * p.in_ps) * 4 + piece * 16);
-        dm_meta[k] = ((ry == 0) | ((ry == 9) << 1) | ((rx == 0) << 2) | ((rx == 9) << 3)) | (blk << 4) | ((int)valid << 6);
-      }
-    }
-    // ---- weight fragments: this wave moves a quarter (WQ 1-KiB pieces) of the tap's [n-tile 16][plane] pieces
-    const unsigned w_slab = (unsigned)(p.N >> 5) * 4096u;
-    const unsigned w_lane = (unsigned)(n0 >> 5) * 4096u + (unsigned)pw * (unsigned)(PC_SLOTB / 4) + (unsigned)lane * 16u;
-    int d_cc = 0, d_tap = 0, d_slot = 0;
-    auto dma_issue = [&]() __attribute__((always_inline)) {
-      const unsigned base = (unsigned)(d_tap * nch + d_cc) * w_slab + w_lane;
-      unsigned char* dst = ring + d_slot * PC_SLOTB + pw * (PC_SLOTB / 4);
-#pragma unroll
-      for (int q = 0; q < WQ; ++q)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (pc_lds_ptr)(dst + q * 1024), 16, base + (unsigned)(q * 1024), 0, 0, 0);
-      if (++d_tap == 9) {
-        d_tap = 0;
-        if (++d_cc == nch) d_cc = 0;
-      }
-      d_slot = (d_slot + 1) & (PC_D - 1);
-    };
-
-    // ---- prologue: the first PC_D taps of weights, the patches of chunks 0 (written) and 1 (in flight) ---------------------------
-#pragma unroll
-    for (int k = 0; k < PC_D; ++k) dma_issue();
-    int cur = 0;                                // patch buffer the consumers read in the current chunk
-    if constexpr (LNP) {
-      // lnp_s is filled and read by the 256 producer threads: one extra barrier (matched by the consumers)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-    auto full_pass = [&](auto s_c, auto j_c, unsigned char* dst) __attribute__((always_inline)) {
-      if constexpr (LNP) {
-        stage_ln_half(s_c, j_c, std::integral_constant<int, 0>{});
-        stage_ln_half(s_c, j_c, std::integral_constant<int, 1>{});
-      }
-      stage_write_pass(s_c, j_c, dst);
-    };
-    if constexpr (DMAP) {
-      patch_dma(lds);                                        // chunk 0 (chunk c + 1 follows at tap 0 of chunk c, into the other buffer)
-      __builtin_amdgcn_s_waitcnt(pc_vmcnt(0));               // vmcnt(0)
-    } else {
-      stage_load(std::integral_constant<int, 0>{});            // chunk 0
-      full_pass(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, lds);
-      full_pass(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, lds);
-      full_pass(std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{}, lds);
-      full_pass(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{}, lds);
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      stage_load(std::integral_constant<int, 1>{});            // chunk 1: in flight across the prologue barrier
-    }
-    __builtin_amdgcn_s_barrier();               // barrier "-1": patch 0 and the fragments of taps 0 .. 3 are in LDS
-
-    // one tap of chunk c (register-set parity S = c & 1): T = 0 .. 8
-    auto tap = [&](auto s_c, auto t_c) __attribute__((always_inline)) {
-      constexpr int S = decltype(s_c)::value, T = decltype(t_c)::value;
-      // (timing-only ablation builds, wrong results: -DPC_ABL_NOSTAGE no patch staging after the first, -DPC_ABL_NODMA no weight DMA
-      //  after the prologue's, -DPC_ABL_NOEPI no output stores / statistics)
-#ifndef PC_ABL_NOSTAGE
-      if constexpr (DMAP) {
-        // the patch of chunk c + 1 straight into the buffer the consumers left at the last barrier: eight DMAs per wave, older than
-        // the weight DMAs of taps g + 3 .. (the same eight entries in the vmcnt queue as the register path's loads: same waits below;
-        // the vmcnt(8) of tap 3 retires them, five barriers before the consumers read that buffer)
-        if constexpr (T == 0) patch_dma(lds + (cur ^ 1) * PC_PATCHB);
-      } else
-      if constexpr (T == 0) stage_load(s_c);                                    // chunk c + 2 -> set S (chunk c's data left it a chunk ago)
-      // chunk c + 1 (set S ^ 1) -> the buffer the consumers do not read.  Without the LN prologue one pass (25 VALU) per tap at taps
-      // 1 .. 4; with it half a pass per tap at taps 1 .. 8: the vector issue port of a SIMD is shared with the consumer wave, whose
-      // 16x16x32 MFMAs alone hold it half of the time, and a whole pass of the prologue (16 v_exp) in one tap makes the barrier late
-      if constexpr (DMAP) {
-      } else if constexpr (LNP) {
-        if constexpr (T >= 1) {
-          constexpr int J = (T - 1) >> 1, HF = (T - 1) & 1;
-          stage_ln_half(std::integral_constant<int, S ^ 1>{}, std::integral_constant<int, J>{}, std::integral_constant<int, HF>{});
-          if constexpr (HF == 1) stage_write_pass(std::integral_constant<int, S ^ 1>{}, std::integral_constant<int, J>{}, lds + (cur ^ 1) * PC_PATCHB);
-        }
-      } else if constexpr (T >= 1 && T <= 4) {
-        stage_write_pass(std::integral_constant<int, S ^ 1>{}, std::integral_constant<int, T - 1>{}, lds + (cur ^ 1) * PC_PATCHB);
-      }
-#endif
-      // fragments of tap g + 1 (issued behind barrier g - 3) must have landed.  Younger than them in this wave's vmcnt queue: the
-      // DMAs of taps g + 2, g + 3 (8 instructions) and - at taps 0 .. 2 only, later the patch loads of tap 0 are older - 8 patch loads
-      // (the BUILTIN, not inline asm: the compiler's own wait insertion must see these waits - with asm it believes every DMA since
-      //  the kernel's start is still in flight, its count outgrows the 6-bit counter and it falls back to vmcnt(0) at the chunk loop's
-      //  head and in front of the patch writes: a full L2 round trip in the producers once per chunk, the barrier late by as much)
-      // (NB = 2: vmcnt(16) / vmcnt(8); NB = 4: 2 weight DMAs per tap and 16 patch DMAs per chunk: vmcnt(20) / vmcnt(4))
-      if constexpr (T <= 2) __builtin_amdgcn_s_waitcnt(pc_vmcnt(2 * WQ + PLQ));
-      else __builtin_amdgcn_s_waitcnt(pc_vmcnt(2 * WQ));
-      if constexpr (T == 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the next patch is written
-      __builtin_amdgcn_s_barrier();             // barrier g
-#ifndef PC_ABL_NODMA
-      dma_issue();                              // tap g + 4 into slot g % 4 (the consumers have finished reading tap g)
-#endif
-    };
-    auto chunk = [&](auto s_c) __attribute__((always_inline)) {
-      tap(s_c, std::integral_constant<int, 0>{}); tap(s_c, std::integral_constant<int, 1>{}); tap(s_c, std::integral_constant<int, 2>{});
-      tap(s_c, std::integral_constant<int, 3>{}); tap(s_c, std::integral_constant<int, 4>{}); tap(s_c, std::integral_constant<int, 5>{});
-      tap(s_c, std::integral_constant<int, 6>{}); tap(s_c, std::integral_constant<int, 7>{}); tap(s_c, std::integral_constant<int, 8>{});
-      cur ^= 1;
-    };
-    for (int tile = mt_begin; tile < mt_end; tile += tstride) {
-      for (int cc = 0; cc < nch; cc += 2) {
-        chunk(std::integral_constant<int, 0>{});
-        chunk(std::integral_constant<int, 1>{});
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (the last DMAs target this workgroup's LDS: they must not outlive it)
-    return;
   }
 
   // ===================================================================================================================
@@ -778,19 +477,16 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
     const int nslot = (slot + 1) & (PC_D - 1), ncur = T == 8 ? cur ^ 1 : cur;
     const OpAddr o = addr_ops(T == 8 ? 0 : T + 1, ncur, nslot);
     mma_half(par_c, std::integral_constant<int, 0>{});
-#if PC_INTERLEAVE
 #pragma unroll
     for (int k = 0; k < 12; ++k) {
       __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);       // MFMA
       __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);       // VALU (addresses)
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();               // barrier g: tap g + 1 (and, at T == 8, the next patch) is in LDS
     slot = nslot;
     cur = ncur;
     read_ops(std::integral_constant<int, par ^ 1>{}, o);
-#if PC_INTERLEAVE
     mma_half(par_c, std::integral_constant<int, 1>{});
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -799,10 +495,6 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#else
-    __builtin_amdgcn_sched_barrier(0);
-    mma_half(par_c, std::integral_constant<int, 1>{});
-#endif
     SGG_PRIO_LO();
     __builtin_amdgcn_sched_barrier(0);
   };
@@ -851,11 +543,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
           acc[i][j][r] = v;
           lsum += v;
         }
-#ifdef PC_ABL_NOEPI
-    if (p.B < 0) {
-#else
     if (live) {
-#endif
 #pragma unroll
       for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -866,11 +554,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
           sgg_out_store4(reinterpret_cast<float*>(const_cast<char*>(ob) + so + o_lane_b), f32x4{v0, v1, v2, v3});
         }
     }
-#ifdef PC_ABL_NOEPI
-    if (p.B < 0) {
-#else
     if (p.tile_stats) {
-#endif
       // (count, mean, M2, max dev) of this wave's 64 pixels x 64 channels (one 8x8 block: inside one sample)
       const float mean_w = wave_sum(lsum) * (1.f / (float)(64 * WN));
       float q = 0.f, dm = 0.f;
@@ -918,23 +602,14 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_pc_kernel(HaloParams p) {
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
 // 1 if the producer / consumer kernel serves this launch: the two-piece modes (precision 2 / 3), 128-column tiles, an even number of
-// 32-channel chunks (C % 64 == 0).  -DSGG_HALO_PC=0 builds never use it.
-#ifndef SGG_HALO_PC
-#define SGG_HALO_PC 1
-#endif
-#ifndef SGG_HALO_PC_DMA
-#define SGG_HALO_PC_DMA 1      // 0: a pre-split source is staged through registers (no arithmetic) like an f32 one
-#endif
-#ifndef SGG_HALO_PC64
-#define SGG_HALO_PC64 1        // 0: no four-block (64-column) tiles
-#endif
+// 32-channel chunks (C % 64 == 0).
 int sgg_halo_pc_applicable(int C, int N, int precision) {
-  return SGG_HALO_PC && (precision == 2 || precision == 3) && N % 128 == 0 && C % 64 == 0 && C <= 512;
+  return (precision == 2 || precision == 3) && N % 128 == 0 && C % 64 == 0 && C <= 512;
 }
 // ... and the four-block form (64-column tiles, round 5): N % 64 == 0 but not 128, C % 64 == 0, precision 2, and only with a PRE-SPLIT
 // source (the patch comes by LDS-DMA: there is no register-staged variant of it)
 int sgg_halo_pc64_applicable(int C, int N, int precision) {
-  return SGG_HALO_PC && SGG_HALO_PC64 && SGG_HALO_PC_DMA && precision == 2 && N % 64 == 0 && N % 128 != 0 && C % 64 == 0 && C <= 512;
+  return precision == 2 && N % 64 == 0 && N % 128 != 0 && C % 64 == 0 && C <= 512;
 }
 
 void sgg_halo_pc_launch(const HaloParams& p_, int precision, hipStream_t st) {
@@ -953,7 +628,7 @@ void sgg_halo_pc_launch(const HaloParams& p_, int precision, hipStream_t st) {
     hipLaunchKernelGGL((conv_halo3_pc_kernel<true, false, true, 4>), grid, blk, 0, st, p);
     return;
   }
-  if (p.src_s16 && half && !p.ln_stats && SGG_HALO_PC_DMA) {      // pre-split source: the patch by LDS-DMA too
+  if (p.src_s16 && half && !p.ln_stats) {      // pre-split source: the patch by LDS-DMA too
     hipLaunchKernelGGL((conv_halo3_pc_kernel<true, false, true>), grid, blk, 0, st, p);
     return;
   }

@@ -29,43 +29,17 @@
 #include "conv_halo.h"
 #include <type_traits>
 
-// Timing-only ablations (wrong results by design; scripts/build_variant_one.sh): S2_ABL_NOSTAGE = no patch staging after the first
-// stage, S2_ABL_NOB = the weight fragments are loaded once, S2_ABL_NOEPI = no output stores / statistics, S2_ABL_NOA = the A
-// fragments are read once per stage (no LDS reads in the tap loop).
-#ifndef S2_ABL_NOSTAGE
-#define S2_ABL_NOSTAGE 0
-#endif
-#ifndef S2_ABL_NOB
-#define S2_ABL_NOB 0
-#endif
-#ifndef S2_ABL_NOEPI
-#define S2_ABL_NOEPI 0
-#endif
-#ifndef SGG_WIDE_STORE
-#define SGG_WIDE_STORE 1        // 16-byte output stores through an in-register quad transpose (sgg_common.h); 0: 4-byte stores
-#endif
-#define S2_BAND 224                   // positions per band in the 7-tile variant (what LayerNorm partials are defined on)
+#define S2_BAND 224                   // positions per band (what LayerNorm partials are defined on)
 #define S2_MAXSLOTS 496               // 2 buffers x 2 planes x 496 x 32 B + the row tables stay inside 64 KB of static LDS
 #define S2_ZSLOT (S2_MAXSLOTS - 1)    // never part of a patch: staged as zeros (out-of-range loads), read by edge lanes
 #define S2_BN 128
-#ifndef S2_SMALL_ITEMS
-#define S2_SMALL_ITEMS 256            // at most this many 224-position work items: use 128-position bands instead
-#endif
-// Few work items (`downsampled` at batch 64: 56 bands x 4 n-tiles on 256 CUs): 0 = 128-position bands (392 items); 1 = 224-position
-// bands with the channel chunks split over two workgroups that ADD their partials into the zeroed output (448 items; a + b = b + a:
-// deterministic); 2 = both.  Measured 49.34 / 48.92 / 49.60 ms per G+D step (same box, two repetitions).
-#ifndef S2_KSPLIT_MODE
-#define S2_KSPLIT_MODE 1
-#endif
-#ifndef S2_DMA
-#define S2_DMA 1              // 0: a pre-split source is staged through registers (no arithmetic) like an f32 one
-#endif
-#ifndef S2_WIDE
-#define S2_WIDE 1             // 0: always 128-column workgroups
-#endif
-#ifndef S2_SWZ
-#define S2_SWZ(slot) (((slot) >> 3) & 1)      // which 16-B half of a slot holds channels 0..7
-#endif
+// Few work items (`downsampled` at batch 64: 56 bands x 4 n-tiles on 256 CUs): the channel chunks are split over two workgroups that
+// ADD their partials into the zeroed output (448 items; a + b = b + a: deterministic).  Measured against 128-position bands (392
+// items) and both: 48.92 against 49.34 / 49.60 ms per G+D step (same box, two repetitions).
+constexpr int S2_SMALL_ITEMS = 256;   // at most this many work items: split the channel chunks
+// which 16-B half of a slot holds channels 0..7 (a macro: as an inline function it changes the register allocation of every kernel
+// of this file)
+#define S2_SWZ(slot) (((slot) >> 3) & 1)
 
 namespace {
 
@@ -85,8 +59,7 @@ constexpr int cls_ntaps(int cls) { return (cls_qy(cls) ? 3 : 2) * (cls_qx(cls) ?
 
 }  // namespace
 
-// MT = MFMA row tiles per band: 7 (224 positions), or 4 (128 positions) where 224-position bands would give fewer
-// (band, n-tile) work items than the chip has CUs (`downsampled` at batch 64: 56 bands x 4 n-tiles).
+// MT = MFMA row tiles per band: always 7 (224 positions); kept as a parameter so that the kernel names stay as they are.
 // ONE: single-piece mode (precision 1 / 4): one 16-bit plane, one MFMA per product.
 // LNP: LN prologue (forward): src is the producing layer's pre-LayerNorm output, normalised + ELU'd while the patch is staged.
 // DMAP: src is a PRE-SPLIT tensor (split16.h; HALF, two pieces, no prologue): the patch goes HBM -> LDS by LDS-DMA (inline assembly:
@@ -97,6 +70,7 @@ constexpr int cls_ntaps(int cls) { return (cls_qy(cls) ? 3 : 2) * (cls_qx(cls) ?
 // with 256+ output channels; DMAP only).
 template <bool DGRAD, bool HALF, int MT, bool ONE = false, bool LNP = false, bool DMAP = false, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Params p) {
+  static_assert(MT == 7, "224-position bands");
   static_assert(NW == 4 || (NW == 8 && DMAP), "256-column workgroups: patch by DMA only");
   constexpr int NT = 64 * NW;                 // threads
   constexpr int BN = 32 * NW;                 // output columns per workgroup
@@ -194,8 +168,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
     for (int j = 0; j < NPASS; ++j) {
       const unsigned off = s_base[j] == SGG_OOB ? SGG_OOB : s_base[j] + uni;
       const unsigned o0 = LNP ? off : stage_off0(off, p.src_s16);
-      pre[j][0] = buf_load4_aux<SGG_PATCH_LOAD_AUX>(rs_src, o0);
-      pre[j][1] = buf_load4_aux<SGG_PATCH_LOAD_AUX>(rs_src, LNP ? off + 16u : stage_off1(o0, p.src_s16));
+      pre[j][0] = buf_load4(rs_src, o0);
+      pre[j][1] = buf_load4(rs_src, LNP ? off + 16u : stage_off1(o0, p.src_s16));
       if constexpr (LNP) {
         ld_mu[j] = p.ln_stats[2 * s_b[j]];
         ld_rs[j] = p.ln_stats[2 * s_b[j] + 1];
@@ -329,23 +303,17 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
     auto body = [&](auto ti_c) __attribute__((always_inline)) {
       constexpr int ti = decltype(ti_c)::value;
       constexpr int par = (par0 + ti) & 1;
-#if !S2_ABL_NOB
-        if constexpr (ti + 1 < ntaps) {
+      if constexpr (ti + 1 < ntaps) {
         constexpr int njy = (ti + 1) / nx, njx = (ti + 1) % nx;
         load_b(std::integral_constant<int, par ^ 1>{}, cc, Axis<DGRAD>::k(qy, njy) * 5 + Axis<DGRAD>::k(qx, njx));
       } else {
         load_b(std::integral_constant<int, par ^ 1>{}, next_cc, next_tap);
       }
-#endif
-#if !S2_ABL_NOSTAGE
       if constexpr (DMAP) {
         if constexpr (ti == 0) stage_dma(lds + (cur ^ 1) * (P * S2_PLB));
       } else if constexpr (ti == (ntaps >= 6 ? ntaps - 3 : 1)) stage_load();
-#endif
       __builtin_amdgcn_sched_barrier(0);
-#if !S2_ABL_NOSTAGE
       if constexpr (!DMAP && ti == ntaps - 1) stage_write(lds + (cur ^ 1) * (P * S2_PLB));
-#endif
       auto tile = [&](auto t_c) __attribute__((always_inline)) {
         constexpr int t = decltype(t_c)::value;
         constexpr int k = ti * MT + t;
@@ -358,9 +326,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
       };
       SGG_PRIO_HI();
       tile(std::integral_constant<int, 0>{}); tile(std::integral_constant<int, 1>{}); tile(std::integral_constant<int, 2>{});
-      tile(std::integral_constant<int, 3>{});
-      if constexpr (MT > 4) { tile(std::integral_constant<int, 4>{}); tile(std::integral_constant<int, 5>{}); tile(std::integral_constant<int, 6>{}); }
-      static_assert(MT == 4 || MT == 7, "row tiles per band");
+      tile(std::integral_constant<int, 3>{}); tile(std::integral_constant<int, 4>{}); tile(std::integral_constant<int, 5>{});
+      tile(std::integral_constant<int, 6>{});
       SGG_PRIO_LO();
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -388,7 +355,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
         lsum += v;
       }
     char* ob = reinterpret_cast<char*>(p.out) + cls_off_bytes + (size_t)(n0 + i) * 4;
-#if SGG_WIDE_STORE
     if (p.ksplit <= 1) {
       // 16-byte stores: after the quad transpose lane (h, g, k) = (lane >> 5, i >> 2, i & 3) holds position rq * 8 + 4 h + k of the
       // row tile and channels 4g .. 4g+3 (sgg_common.h: sgg_quad_transpose4)
@@ -403,11 +369,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
           if (o >= 0) sgg_out_store4(reinterpret_cast<float*>(ow + o), f32x4{v0, v1, v2, v3});
         }
     }
-    const bool narrow = p.ksplit > 1;
-#else
-    const bool narrow = true;
-#endif
-    if (narrow) {
+    if (p.ksplit > 1) {      // channel chunks split over two workgroups: each adds its partial sums into the zeroed output
 #pragma unroll
     for (int t = 0; t < MT; ++t)
 #pragma unroll
@@ -418,7 +380,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
           if (o4.y >= 0) atomicAdd(reinterpret_cast<float*>(ob + o4.y), acc[t][rq * 4 + 1]);
           if (o4.z >= 0) atomicAdd(reinterpret_cast<float*>(ob + o4.z), acc[t][rq * 4 + 2]);
           if (o4.w >= 0) atomicAdd(reinterpret_cast<float*>(ob + o4.w), acc[t][rq * 4 + 3]);
-        } else {
+        } else {      // (never taken; removing this arm changes the compiler's register allocation of these kernels)
           if (o4.x >= 0) sgg_out_store(reinterpret_cast<float*>(ob + o4.x), acc[t][rq * 4 + 0]);
           if (o4.y >= 0) sgg_out_store(reinterpret_cast<float*>(ob + o4.y), acc[t][rq * 4 + 1]);
           if (o4.z >= 0) sgg_out_store(reinterpret_cast<float*>(ob + o4.z), acc[t][rq * 4 + 2]);
@@ -478,9 +440,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
   }
   __builtin_amdgcn_s_barrier();
 
-#if S2_ABL_NOB
-  load_b(std::integral_constant<int, 1>{}, cbeg, TAP0[0]);
-#endif
   int tabsel = 0;
   for (int band = band_begin; band < band_end; band += bstride, tabsel ^= 1) {
     // compute state of this band: row table (out offsets) and the per-lane patch slots of the 7 row tiles
@@ -523,9 +482,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
         stage(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, cc + 1, cc + 1, TAP0[3]);
         stage(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}, cc + 1, last ? cbeg : cc + 2, TAP0[0]);
       }
-#if !S2_ABL_NOEPI
       epilogue(band, tabsel, 0);
-#endif
     } else {
       auto class_loop = [&](auto cls_c) __attribute__((always_inline)) {
         constexpr int cls = decltype(cls_c)::value;
@@ -536,9 +493,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
           stage(cls_c, std::integral_constant<int, 0>{}, cc, cc + 1, TAP0[cls]);
           stage(cls_c, std::integral_constant<int, odd>{}, cc + 1, last ? cbeg : cc + 2, last ? TAP0[ncls] : TAP0[cls]);
         }
-#if !S2_ABL_NOEPI
         epilogue(band, tabsel, ((cls_qy(cls) * 2 * p.Wo + cls_qx(cls)) * p.N) * 4);
-#endif
       };
       class_loop(std::integral_constant<int, 0>{});
       class_loop(std::integral_constant<int, 1>{});
@@ -546,16 +501,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void conv_s2_kernel(S2Par
       class_loop(std::integral_constant<int, 3>{});
     }
   }
-#if S2_ABL_NOEPI
-  epilogue(band_begin, 0, 0);      // (keeps the accumulators alive: once per workgroup)
-#endif
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
 static int s2_gcd(int a, int b) { return b ? s2_gcd(b, a % b) : a; }
 
 // largest number of patch rows any band needs (the band pattern repeats every 224 / gcd(224, Ho*Wo) images)
-static int s2_max_rows(int Ho, int Wo, int band = S2_BAND) {
+static int s2_max_rows(int Ho, int Wo) {
+  constexpr int band = S2_BAND;
   const int period = band / s2_gcd(band, Ho * Wo);
   const long long M = (long long)period * Ho * Wo;
   int mx = 0;
@@ -583,20 +536,19 @@ int sgg_s2_stats_per_sample(int Ho, int Wo, int N) { return ((Ho * Wo) % S2_BAND
 void sgg_s2_launch(const S2Params& p_, int dgrad, int precision, hipStream_t st) {
   S2Params p = p_;
   const bool half = sgg_prec_half(precision), one = sgg_prec_one(precision);
-  const bool dmap = S2_DMA && p.src_s16 && half && !one && !p.ln_stats;      // pre-split source: the patch by LDS-DMA
+  const bool dmap = p.src_s16 && half && !one && !p.ln_stats;      // pre-split source: the patch by LDS-DMA
   // 256-column workgroups (eight waves, one workgroup per CU) where the layer has 256+ output columns and the patch comes by DMA
   // (not where that leaves fewer work items than half the CUs - `downsampled` at batch 64: measured equal forward, 7 % slower dgrad)
-  const bool wide = S2_WIDE && dmap && p.N % 256 == 0 && sgg_cdiv(p.M, S2_BAND) * (p.N / 256) > S2_SMALL_ITEMS / 2;
+  const bool wide = dmap && p.N % 256 == 0 && sgg_cdiv(p.M, S2_BAND) * (p.N / 256) > S2_SMALL_ITEMS / 2;
   const int bn = wide ? 256 : S2_BN;
-  // 224-position bands unless they give fewer work items than CUs (and no LayerNorm partials are asked for): then 128-position
-  // bands (S2_KSPLIT_MODE 0), or 224-position bands with the channel chunks split over two workgroups (1), or both (2)
+  // where the bands give fewer work items than CUs (and no LayerNorm partials are asked for), the channel chunks are split over
+  // two workgroups
   const bool small_ = !wide && !p.tile_stats && !p.ln_stats && sgg_cdiv(p.M, S2_BAND) * (p.N / bn) <= S2_SMALL_ITEMS;
-  const int mt = (small_ && S2_KSPLIT_MODE != 1) ? 4 : 7;
-  p.ksplit = (small_ && S2_KSPLIT_MODE != 0 && (p.C >> 4) % 4 == 0) ? 2 : 1;
+  p.ksplit = (small_ && (p.C >> 4) % 4 == 0) ? 2 : 1;
   if (p.ksplit > 1)
     (void)hipMemsetAsync(p.out, 0, (size_t)(dgrad ? 4 : 1) * p.M * p.N * sizeof(float), st);
   const int ntn = (p.N / bn) * p.ksplit;
-  p.nbands = sgg_cdiv(p.M, 32 * mt);
+  p.nbands = sgg_cdiv(p.M, S2_BAND);
   const int slots = (wide ? 1 : 2) * sgg_persist_cus(p.cu_cap);      // resident workgroups per XCD (32 CUs)
   int per_xcd = sgg_cdiv(p.nbands, 8) * ntn;       // (band, n-tile, channel half) items an XCD owns
   int gx = per_xcd < slots ? per_xcd : slots;
@@ -609,13 +561,8 @@ void sgg_s2_launch(const S2Params& p_, int dgrad, int precision, hipStream_t st)
     return;
   }
   if (dmap) {
-    if (mt == 4) {
-      if (dgrad) hipLaunchKernelGGL((conv_s2_kernel<true, true, 4, false, false, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((conv_s2_kernel<false, true, 4, false, false, true>), grid, dim3(256), 0, st, p);
-    } else {
-      if (dgrad) hipLaunchKernelGGL((conv_s2_kernel<true, true, 7, false, false, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((conv_s2_kernel<false, true, 7, false, false, true>), grid, dim3(256), 0, st, p);
-    }
+    if (dgrad) hipLaunchKernelGGL((conv_s2_kernel<true, true, 7, false, false, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((conv_s2_kernel<false, true, 7, false, false, true>), grid, dim3(256), 0, st, p);
     return;
   }
   if (p.ln_stats) {       // LN prologue: forward, two-piece modes, 224-position bands (host checks in sgg_conv2d_nhwc_fwd)
@@ -623,25 +570,19 @@ void sgg_s2_launch(const S2Params& p_, int dgrad, int precision, hipStream_t st)
     else hipLaunchKernelGGL((conv_s2_kernel<false, false, 7, false, true>), grid, dim3(256), 0, st, p);
     return;
   }
-#define SGG_S2(MT)                                                                                      \
-  do {                                                                                                  \
-    if (one) {                                                                                          \
-      if (dgrad) {                                                                                      \
-        if (half) hipLaunchKernelGGL((conv_s2_kernel<true, true, MT, true>), grid, dim3(256), 0, st, p);  \
-        else hipLaunchKernelGGL((conv_s2_kernel<true, false, MT, true>), grid, dim3(256), 0, st, p);      \
-      } else {                                                                                          \
-        if (half) hipLaunchKernelGGL((conv_s2_kernel<false, true, MT, true>), grid, dim3(256), 0, st, p); \
-        else hipLaunchKernelGGL((conv_s2_kernel<false, false, MT, true>), grid, dim3(256), 0, st, p);     \
-      }                                                                                                 \
-    } else if (dgrad) {                                                                                 \
-      if (half) hipLaunchKernelGGL((conv_s2_kernel<true, true, MT>), grid, dim3(256), 0, st, p);        \
-      else hipLaunchKernelGGL((conv_s2_kernel<true, false, MT>), grid, dim3(256), 0, st, p);            \
-    } else {                                                                                            \
-      if (half) hipLaunchKernelGGL((conv_s2_kernel<false, true, MT>), grid, dim3(256), 0, st, p);       \
-      else hipLaunchKernelGGL((conv_s2_kernel<false, false, MT>), grid, dim3(256), 0, st, p);           \
-    }                                                                                                   \
-  } while (0)
-  if (mt == 4) SGG_S2(4);
-  else SGG_S2(7);
-#undef SGG_S2
+  if (one) {
+    if (dgrad) {
+      if (half) hipLaunchKernelGGL((conv_s2_kernel<true, true, 7, true>), grid, dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((conv_s2_kernel<true, false, 7, true>), grid, dim3(256), 0, st, p);
+    } else {
+      if (half) hipLaunchKernelGGL((conv_s2_kernel<false, true, 7, true>), grid, dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((conv_s2_kernel<false, false, 7, true>), grid, dim3(256), 0, st, p);
+    }
+  } else if (dgrad) {
+    if (half) hipLaunchKernelGGL((conv_s2_kernel<true, true, 7>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((conv_s2_kernel<true, false, 7>), grid, dim3(256), 0, st, p);
+  } else {
+    if (half) hipLaunchKernelGGL((conv_s2_kernel<false, true, 7>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((conv_s2_kernel<false, false, 7>), grid, dim3(256), 0, st, p);
+  }
 }

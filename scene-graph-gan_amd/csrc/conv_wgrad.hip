@@ -639,9 +639,7 @@ struct WgradPlan {
   size_t ws_bytes;
 };
 
-#ifndef SGG_WGRAD_WGS
-#define SGG_WGRAD_WGS 1536   // workgroups aimed at by the pixel split of the per-tap wgrad kernels
-#endif
+constexpr int SGG_WGRAD_WGS = 1536;   // workgroups aimed at by the pixel split of the per-tap wgrad kernels
 static WgradPlan wgrad_plan(int B, int Ho, int Wo, int Cin, int Cout, int KH, int KW) {
   WgradPlan pl;
   const long long mpix = (long long)B * Ho * Wo;
@@ -678,18 +676,13 @@ extern "C" size_t sgg_conv2d_nhwc_wgrad_workspace_bytes(int B, int Hi, int Wi, i
   return need;
 }
 
-// 1: filter gradients whose operands are both pre-split run on the LDS-DMA kernel (conv_wgrad_dma.hip); 0 (-DSGG_WGRAD_DMA=0): always
-// the halo-resident kernel (which stages pre-split operands through registers without arithmetic)
-#ifndef SGG_WGRAD_DMA
-#define SGG_WGRAD_DMA 1
-#endif
 // 0: per-tap kernels (or conv1_1's own); 1: the halo-resident kernel (takes pre-split operands, stages them through registers);
 // 2: with BOTH operands pre-split in precision 2 the LDS-DMA kernel runs instead (conv_wgrad_dma.hip)
 extern "C" int sgg_conv2d_nhwc_wgrad_resident(int B, int Ho, int Wo, int Cin, int Cout, int KH, int KW, int stride, int precision) {
   WgradHaloPlan hp;
   if (!(sgg_prec_resident(precision) && Cin != 3 && B > 0 && sgg_wgrad_halo_plan(B, Ho, Wo, Cin, Cout, KH, KW, stride, &hp))) return 0;
   WgradDmaPlan dp;
-  return (SGG_WGRAD_DMA && precision == 2 && sgg_wgrad_dma_plan(B, Ho, Wo, Cin, Cout, KH, KW, stride, &dp)) ? 2 : 1;
+  return (precision == 2 && sgg_wgrad_dma_plan(B, Ho, Wo, Cin, Cout, KH, KW, stride, &dp)) ? 2 : 1;
 }
 
 extern "C" int sgg_conv2d_nhwc_wgrad(const float* x, const float* dy, float* dw, int B, int Hi, int Wi, int Cin, int Ho,
@@ -720,7 +713,7 @@ extern "C" int sgg_conv2d_nhwc_wgrad(const float* x, const float* dy, float* dw,
   }
   const long long nout = (long long)KH * KW * Cin * Cout;
   WgradDmaPlan dp;
-  if (SGG_WGRAD_DMA && operand_format == 3 && precision == 2 && !ln_stats && algo == 0 && pad_t == 1 && pad_l == 1 && Hi == Ho * stride &&
+  if (operand_format == 3 && precision == 2 && !ln_stats && algo == 0 && pad_t == 1 && pad_l == 1 && Hi == Ho * stride &&
       Wi == Wo * stride && sgg_wgrad_dma_plan(B, Ho, Wo, Cin, Cout, KH, KW, stride, &dp)) {
     // both operands pre-split: staged by LDS-DMA, no staging arithmetic (conv_wgrad_dma.hip)
     if (!workspace || workspace_bytes < dp.ws_bytes) {

@@ -24,15 +24,6 @@
 #include "conv_halo.h"
 #include <type_traits>
 
-// Timing-only ablations (wrong results by design; scripts/build_variant_one.sh): SGG_WABL_NOSPLIT = the staged bytes go to LDS as
-// they are (what pre-split 16-bit operand planes in HBM would leave of the staging: loads + LDS writes, no arithmetic);
-// SGG_WABL_NOSTAGE = nothing is loaded or written after the first stage (MFMAs, LDS reads and barriers only).
-#ifndef SGG_WABL_NOSPLIT
-#define SGG_WABL_NOSPLIT 0
-#endif
-#ifndef SGG_WABL_NOSTAGE
-#define SGG_WABL_NOSTAGE 0
-#endif
 typedef short s16x4h __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2h __attribute__((ext_vector_type(2)));
 
@@ -208,11 +199,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_halo3_kernel(WgradHaloParam
       const int fmt = isx ? p.x_s16 : p.dy_s16;
       const unsigned o0 = stage_off0(off, fmt), o1 = stage_off1(o0, fmt);
       if (isx) {
-        pre[slot][0] = buf_load4_aux<SGG_WGRAD_LOAD_AUX>(rs_x, o0);
-        pre[slot][1] = buf_load4_aux<SGG_WGRAD_LOAD_AUX>(rs_x, o1);
+        pre[slot][0] = buf_load4(rs_x, o0);
+        pre[slot][1] = buf_load4(rs_x, o1);
       } else {
-        pre[slot][0] = buf_load4_aux<SGG_WGRAD_LOAD_AUX>(rs_dy, o0);
-        pre[slot][1] = buf_load4_aux<SGG_WGRAD_LOAD_AUX>(rs_dy, o1);
+        pre[slot][0] = buf_load4(rs_dy, o0);
+        pre[slot][1] = buf_load4(rs_dy, o1);
       }
     }
     if constexpr (part != 1) {
@@ -264,11 +255,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_halo3_kernel(WgradHaloParam
         const int fmt = isx ? (LNP ? 0 : p.x_s16) : p.dy_s16;
         const unsigned o0 = stage_off0(off, fmt), o1 = stage_off1(o0, fmt);
         if (isx) {
-          pre[j][0] = buf_load4_aux<SGG_WGRAD_LOAD_AUX>(rs_x, o0);
-          pre[j][1] = buf_load4_aux<SGG_WGRAD_LOAD_AUX>(rs_x, o1);
+          pre[j][0] = buf_load4(rs_x, o0);
+          pre[j][1] = buf_load4(rs_x, o1);
         } else {
-          pre[j][0] = buf_load4_aux<SGG_WGRAD_LOAD_AUX>(rs_dy, o0);
-          pre[j][1] = buf_load4_aux<SGG_WGRAD_LOAD_AUX>(rs_dy, o1);
+          pre[j][0] = buf_load4(rs_dy, o0);
+          pre[j][1] = buf_load4(rs_dy, o1);
         }
       }
       // advance this slot to the next stage's block
@@ -292,13 +283,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_halo3_kernel(WgradHaloParam
         }
       }
       u32x4 pl[P];
-#if SGG_WABL_NOSPLIT
-      pl[0] = __builtin_bit_cast(u32x4, pre[j][0]);
-      if constexpr (P == 2) pl[1] = __builtin_bit_cast(u32x4, pre[j][1]);
-#else
       if constexpr (HALF) stage_planes<P, HALF>(pre[j][0], pre[j][1], isx ? sa : sb, isx ? (LNP ? 0 : p.x_s16) : p.dy_s16, pl);
       else split8<P, HALF>(pre[j][0], pre[j][1], isx ? sa : sb, pl);
-#endif
       if ((it_lds[j] >> 24) & 1) {
         unsigned char* dst = (isx ? x_s : d_s) + (it_lds[j] & 0xfffff);
 #pragma unroll
@@ -427,19 +413,15 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_halo3_kernel(WgradHaloParam
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   for (int s = 0; s < p.stages; ++s) {
-#if !SGG_WABL_NOSTAGE
     if constexpr (PREF) stage_load();        // next stage's blocks (out-of-range offsets past the end: zeros, no traffic)
-#endif
     __builtin_amdgcn_sched_barrier(0);
     SGG_PRIO_HI();
     compute();
     SGG_PRIO_LO();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#if !SGG_WABL_NOSTAGE
     if constexpr (!PREF) stage_load();
     stage_write();
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }

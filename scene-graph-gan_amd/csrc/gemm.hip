@@ -13,12 +13,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-// 1: the head GEMMs whose 64 x 64 tiling would split K over workgroups run on gemm_wk_kernel (split over the waves of one
-// workgroup, no slabs, one launch); 0 (-DSGG_GEMM_WK=0): always the slab kernels
-#ifndef SGG_GEMM_WK
-#define SGG_GEMM_WK 1
-#endif
-
 struct GemmParams {
   const float* A;
   const float* B;
@@ -286,14 +280,12 @@ static bool gemm_wk_applicable(int mode, int M, int N, int K, int nsplit_old) {
   // M = 64 and M = 192 gate products; with 65 .. 128 rows and a large weight matrix its 16-column tiles re-read A once too often
   // (20.0 against 16.2 us): those stay on the slab kernels
   if (M > 64 && M <= 128 && (long long)N * K >= (1LL << 21)) return false;
-  return SGG_GEMM_WK && mode != 2 && nsplit_old > 1 && M <= 512 && K <= 8192 && N >= 16;
+  return mode != 2 && nsplit_old > 1 && M <= 512 && K <= 8192 && N >= 16;
 }
 
 // smallest K range one workgroup of a split-K head GEMM takes.  These GEMMs are chains of dependent 32-deep slabs (f32 MFMA: 0.43 us
 // per slab per wave) on a handful of tiles: deeper splits shorten the chain (measured 256 -> 64: 53.16 -> 52.82 ms per G+D step)
-#ifndef SGG_GEMM_MIN_KCHUNK
-#define SGG_GEMM_MIN_KCHUNK 64
-#endif
+constexpr int SGG_GEMM_MIN_KCHUNK = 64;
 static void gemm_plan(int M, int N, int K, int* nsplit, int* kchunk) {
   const int tiles = sgg_cdiv(M, 64) * sgg_cdiv(N, 64);
   int ns = 1;

@@ -25,31 +25,18 @@
 #include "split16.h"
 
 #define LN_EPS 1e-12f
-#ifndef SGG_LN_WGS
-#define SGG_LN_WGS 1536      // workgroups per launch of the streaming LayerNorm kernels (six per CU)
-#endif
+constexpr int SGG_LN_WGS = 1536;      // workgroups per launch of the streaming LayerNorm kernels (six per CU)
 #define LN_CHUNK 4096  // elements per workgroup iteration: 256 threads x 4 x float4
 
-// Streaming accesses (SGG_LN_NT bit 0: nontemporal stores, bit 1: nontemporal loads).  y and da are read once per pass and not
-// again before 400+ MB of other traffic, while a / dy are the next convolution's input: nontemporal LOADS keep the streamed-once
-// bytes from displacing the outputs in the L2 / Infinity Cache (whole step 52.16 -> 51.48 ms, two repetitions; nontemporal
-// stores on top give that back: 52.15 ms; stores alone 53.0 ms).
-#ifndef SGG_LN_NT
-#define SGG_LN_NT 2
-#endif
+// Streaming accesses: nontemporal loads, default-policy stores.  y and da are read once per pass and not again before 400+ MB of
+// other traffic, while a / dy are the next convolution's input: nontemporal LOADS keep the streamed-once bytes from displacing the
+// outputs in the L2 / Infinity Cache (whole step 52.16 -> 51.48 ms, two repetitions; nontemporal stores on top give that back:
+// 52.15 ms; stores alone 53.0 ms).
 __device__ __forceinline__ f32x4 ln_ld(const float* p) {
-#if SGG_LN_NT & 2
   return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-#else
-  return *reinterpret_cast<const f32x4*>(p);
-#endif
 }
 __device__ __forceinline__ void ln_st(float* p, f32x4 v) {
-#if SGG_LN_NT & 1
-  __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-#else
   *reinterpret_cast<f32x4*>(p) = v;
-#endif
 }
 
 struct LnGeom {

@@ -118,10 +118,6 @@ typedef float sgg_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void f16_split2(float a, float b, unsigned& hi, unsigned& lo) {
   const sgg_h2 h = __builtin_convertvector(sgg_f2{a, b}, sgg_h2);
   hi = __builtin_bit_cast(unsigned, h);
-#ifdef SGG_EXPERIMENT_NOSPLIT      // timing experiment only (scripts/build_prof_lib.sh nosplit): what the staging costs without the residual piece
-  lo = hi;
-  return;
-#endif
   const sgg_h2 l = __builtin_convertvector(sgg_f2{a - (float)h[0], b - (float)h[1]}, sgg_h2);
   lo = __builtin_bit_cast(unsigned, l);
 }
@@ -146,42 +142,21 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // has 32).  Fewer than 32 leaves whole CUs - registers, wave slots - to the HBM-bound kernels of the other HIP streams (LayerNorm
 // passes of the other network, Adam, the heads), which cannot co-reside with a workgroup that holds a CU's whole register file.
 // Experiment of round 5 (profiles/r05_persistent_cu_cap_ab.log); 32 = every CU.
-#ifndef SGG_PERSIST_CUS_PER_XCD
-#define SGG_PERSIST_CUS_PER_XCD 32
-#endif
+constexpr int SGG_PERSIST_CUS_PER_XCD = 32;
 
 // The resident convolution kernels raise the wave's issue priority over their MFMA clusters (s_setprio), so that the other resident
 // workgroup's wave in its staging phase does not take issue slots from the wave feeding the matrix pipe (-0.25 ms per step, same box,
-// two repetitions; raising it before the tap's B-fragment loads instead: the same).  -DSGG_MFMA_PRIO=0 builds without.
-#ifndef SGG_MFMA_PRIO
-#define SGG_MFMA_PRIO 1
-#endif
-#if SGG_MFMA_PRIO
-#define SGG_PRIO_HI() __builtin_amdgcn_s_setprio(SGG_MFMA_PRIO)
+// two repetitions; raising it before the tap's B-fragment loads instead: the same).
+#define SGG_PRIO_HI() __builtin_amdgcn_s_setprio(1)
 #define SGG_PRIO_LO() __builtin_amdgcn_s_setprio(0)
-#else
-#define SGG_PRIO_HI()
-#define SGG_PRIO_LO()
-#endif
 
 // The convolution epilogues store their output tiles with the nontemporal hint (the tensors are far larger than the L2 of an XCD and
-// are next read by another kernel): -0.2 ms per step, four same-box repetitions.  -DSGG_CONV_NT_STORE=0 builds without.
-#ifndef SGG_CONV_NT_STORE
-#define SGG_CONV_NT_STORE 1
-#endif
+// are next read by another kernel): -0.2 ms per step, four same-box repetitions.
 __device__ __forceinline__ void sgg_out_store(float* p, float v) {
-#if SGG_CONV_NT_STORE
   __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 __device__ __forceinline__ void sgg_out_store4(float* p, const f32x4& v) {     // p 16-byte aligned
-#if SGG_CONV_NT_STORE
   __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-#else
-  *reinterpret_cast<f32x4*>(p) = v;
-#endif
 }
 
 // 4x4 transpose inside every quad of lanes (lanes 4g .. 4g+3), in registers (DPP quad permutes, no LDS):

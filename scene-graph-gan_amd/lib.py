@@ -100,7 +100,7 @@ class SggError(RuntimeError):
 
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     """Load libsgg_hip.so and bind every declared symbol. Raises if the library or a symbol is missing.
-    SGG_HIP_LIB overrides the path (instrumented builds, scripts/build_prof_lib.sh)."""
+    SGG_HIP_LIB overrides the path (experimental -D builds, scripts/build_variant_lib.sh)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -133,9 +133,8 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
-# Documented run-time options of HipKernels (the whole experiment surface of the host side; everything else is a build-time
-# -D switch of the library).  HipKernels(options={...}) takes any subset; scripts may override them without
-# touching code through ONE environment variable, SGG_OPTIONS="key=value,key=value" (lists: values joined by '+').
+# Documented run-time options of HipKernels (the whole experiment surface: the library has no build-time switches).
+# HipKernels(options={...}) takes any subset; scripts may override them without touching code through ONE environment variable, SGG_OPTIONS="key=value,key=value" (lists: values joined by '+').
 DEFAULT_OPTIONS = {
     # Convolution contraction mode (csrc/conv_gather.hip, conv_wgrad.hip):
     #   2 (default) f32 operands scaled by a per-tensor power of two and split into two fp16 pieces with round-to-nearest
@@ -414,7 +413,7 @@ class HipKernels:
     def halo_symbol(self, n_out, n_in, lnp=False):
         """Kernel symbol (as rocprofv3 prints it, spaces removed) that csrc/conv_halo.hip: sgg_halo_launch picks (default build)."""
         tile = "2,128,2,2" if n_out % 128 == 0 else ("2,64,2,2" if n_out % 64 == 0 else "2,32,2,1")
-        # (last argument: blocks per wave, 1 in the default build - csrc/conv_halo.hip SGG_HALO_N128_WB2)
+        # (sixth argument: patch prefetch, always true; last: blocks per wave, always 1 - csrc/conv_halo.hip)
         return "conv_halo3_kernel<%s,%s,%s,%s,%s,%s,1>" % (tile, "true" if self.conv_precision in (1, 2) else "false", "true",
                                                            "true" if n_in == 32 else "false", "true" if lnp else "false",
                                                            "true" if self.conv_precision in (1, 4) else "false")
