@@ -4,6 +4,7 @@ Same import path, constructor and method signatures as the reference (discrimina
     Discriminator(vocab_size, embedding_matrix)
     Discriminator.build_discriminator(input_triples, images, is_training=True) -> critic logits [B, 3, 1]
     Discriminator.attentionMechanism(cell_state) -> z_hat [B, 512]
+Added (evaluation): Discriminator.score_samples(input_triples [N, B, 3, vocab], images) -> [N, B, 3, 1] on one encoder pass.
 `input_triples` is float32 [B, 3, vocab]: one-hot real triples or raw generator logits (train.py:173, 242).
 `embedding_matrix` [vocab, 300] is created by the trainer and trained by the critic's optimiser
 (train.py:68-72, 263); here its storage moves into the critic's parameter arena and `self.embedding_matrix`
@@ -39,3 +40,18 @@ class Discriminator(NetworkHandle):
         net.head.forward(st, ctx, [input_triples.contiguous()])
         self._publish(ctx, st)
         return st.OUT[0]
+
+    def score_samples(self, input_triples, images):
+        """Critic outputs of N triples per image on ONE encoder pass: input_triples [N, B, 3, vocab] (one-hots or generator
+        logits, e.g. Generator.sample's output), images [B, S, S, 3] -> [N, B, 3, 1].  Row k*B + b reads image b; the returned
+        tensor is a view of the head's rows (the next call overwrites it)."""
+        net = self._ensure(images)
+        B = int(images.shape[0])
+        N = int(input_triples.shape[0])
+        assert tuple(input_triples.shape) == (N, B, 3, self.vocab_size), input_triples.shape
+        ctx = net.trunk.forward(images.contiguous(), for_backward=False)
+        net.head.precompute(ctx)
+        st = net.head.sample_state(N * B)
+        net.head.forward(st, ctx, [input_triples.contiguous().view(N * B, 3, self.vocab_size)])
+        self._publish(ctx, st)
+        return st.OUT[0].view(N, B, 3, 1)

@@ -5,6 +5,7 @@ Same import path, constructor and method signatures as the reference (generator_
     Generator.build_generator(images, is_training=True) -> logits [B, 3, vocab]      (raw logits, no softmax)
     Generator.attentionMechanism(cell_state)            -> z_hat  [B, 512]           (cell_state = (c, h), c is used)
     attributes after a build: downsampled, flattened_context, partially_flattened_context, alpha
+Added (evaluation): Generator.sample(images, num_samples, noise=None) -> logits [N, B, 3, vocab] on one encoder pass.
 In the reference these methods add TensorFlow ops to a graph; here they run eagerly on the GPU: every arithmetic
 op is a hand-written HIP kernel behind the C ABI of libsgg_hip.so (include/sgg_hip.h).  Repeated builds share one
 set of weights, as `reuse=tf.AUTO_REUSE` does (train.py:86).  `is_training` is accepted and ignored, as in the
@@ -44,3 +45,19 @@ class Generator(NetworkHandle):
         net.head.forward(st, ctx, noise)
         self._publish(ctx, st)
         return st.OUT[0]
+
+    def sample(self, images, num_samples, noise=None):
+        """num_samples generator samples of each image on ONE encoder pass: images [B, S, S, 3] (standardised) -> logits
+        [N, B, 3, vocab].  Sample k of image b is head row k*B + b (the returned tensor is a view of the head's rows; the next
+        call overwrites it).  `noise` [N, B, 512] (torch.randn if None)."""
+        net = self._ensure(images)
+        B, N = int(images.shape[0]), int(num_samples)
+        if noise is None:
+            noise = torch.randn((N, B, 512), device=images.device, dtype=torch.float32)
+        assert tuple(noise.shape) == (N, B, 512), noise.shape
+        ctx = net.trunk.forward(images.contiguous(), for_backward=False)
+        net.head.precompute(ctx)
+        st = net.head.sample_state(N * B)
+        net.head.forward(st, ctx, noise.contiguous().view(N * B, 512))
+        self._publish(ctx, st)
+        return st.OUT[0].view(N, B, 3, self.vocab_size)

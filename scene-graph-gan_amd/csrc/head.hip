@@ -12,6 +12,7 @@
 // Dual tensors are two planes (real, dual). For cotangent tensors: real plane = cotangent of the tangent,
 // dual plane = cotangent of the primal (dual.h).
 #include "dual.h"
+#include "mma_f32.h"
 #include <stdlib.h>
 
 #define HEAD_LN_EPS 1e-12f
@@ -87,6 +88,109 @@ __global__ __launch_bounds__(256) void attn_step_fwd_kernel(const float* __restr
     const T zz = (part[tid] + part[256 + tid]) + (part[512 + tid] + part[768 + tid]);
     Sc<T>::st(z_r, z_d, (size_t)r * ldz + c0 + tid, zz);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// attention step forward for many rows per image (float planes): the N = R / B rows r = b + k*B of image b share one
+// feature map, so the per-row kernel above streams ctx[b] N times.  Here one workgroup per (image b, tile of TR rows of b,
+// 128-channel slice): softmax one wave per row into LDS (32-location slabs in the [TR][SGG_LDK] KC layout, zero padded to a
+// multiple of 32 locations), then z[tile, slice] = alpha . ctx[b][:, slice] on v_mfma_f32_32x32x2_f32 with the feature-map
+// slice staged through LDS in double-buffered 32-location chunks (one read of ctx[b] per row tile).
+// ---------------------------------------------------------------------------------------------------
+#define ATTN_ROWS_CS 128                  // channels per workgroup
+#define ATTN_ROWS_MIN_RATIO 32            // R / B from which sgg_attn_step_fwd takes this kernel (profiles/attn_rows_threshold.log)
+#define ATTN_ROWS_MAX_LDS (160 * 1024)
+
+static size_t attn_rows_lds_bytes(int tr, int L) {
+  return ((size_t)((L + 31) / 32) * tr * SGG_LDK + 2 * 32 * ATTN_ROWS_CS) * sizeof(float);
+}
+
+template <int TR>
+__global__ __launch_bounds__(256) void attn_step_fwd_rows_kernel(const float* __restrict__ P, const float* __restrict__ ec, int ldec,
+                                                                 const float* __restrict__ ctx, float* __restrict__ al,
+                                                                 float* __restrict__ z, int ldz, int B, int N, int L, int C) {
+  constexpr int CS = ATTN_ROWS_CS, WM = TR / 32, WN = 4 / WM, TN = CS / 32 / WN;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int nslab = (L + 31) >> 5;
+  float* al_s = sm;                                          // [nslab][TR][SGG_LDK]
+  float* cx_s = sm + (size_t)nslab * TR * SGG_LDK;           // [2][32][CS]
+  const int b = blockIdx.x, k0 = blockIdx.y * TR, c0 = blockIdx.z * CS;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* Pb = P + (size_t)b * L;
+  // ---- softmax over L, one wave per row; location l of row i sits at slab l / 32, [i][l % 32]; a lane only revisits its own
+  //      locations, so the passes need no barrier.  Rows past N get alpha = 0 (their z is not stored).
+  for (int i = wave; i < TR; i += 4) {
+    float* arow = al_s + i * SGG_LDK;
+    const int k = k0 + i;
+    if (k >= N) {
+      for (int l = lane; l < nslab * 32; l += 64) arow[(l >> 5) * TR * SGG_LDK + (l & 31)] = 0.f;
+      continue;
+    }
+    const size_t r = (size_t)b + (size_t)k * B;
+    const float* er = ec + r * ldec;
+    float mx = -3.0e38f;
+    for (int l = lane; l < L; l += 64) {
+      const float e = Pb[l] + er[l];
+      arow[(l >> 5) * TR * SGG_LDK + (l & 31)] = e;
+      mx = fmaxf(mx, e);
+    }
+    mx = wave_max(mx);
+    float s = 0.f;
+    for (int l = lane; l < L; l += 64) {
+      float* p = arow + (l >> 5) * TR * SGG_LDK + (l & 31);
+      const float ex = exp_(*p - mx);
+      *p = ex;
+      s += ex;
+    }
+    s = wave_sum(s);
+    const float inv = recip_(s);
+    for (int l = lane; l < nslab * 32; l += 64) {
+      float* p = arow + (l >> 5) * TR * SGG_LDK + (l & 31);
+      if (l < L) {
+        const float a = *p * inv;
+        *p = a;
+        if (blockIdx.z == 0) al[r * L + l] = a;
+      } else {
+        *p = 0.f;
+      }
+    }
+  }
+  // ---- z = alpha . ctx[b][:, c0 .. c0 + CS): 32-location chunks of the slice, 256 threads x 4 float4 each
+  const float* cb = ctx + (size_t)b * L * C + c0;
+  f32x4 stg[4];
+  auto load = [&](int s) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + 256 * q, l = s * 32 + (idx >> 5);
+      stg[q] = l < L ? *reinterpret_cast<const f32x4*>(cb + (size_t)l * C + (idx & 31) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  auto store = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int idx = tid + 256 * q;
+      *reinterpret_cast<f32x4*>(cx_s + buf * 32 * CS + (idx >> 5) * CS + (idx & 31) * 4) = stg[q];
+    }
+  };
+  const int wm0 = (wave % WM) * 32, wn0 = (wave / WM) * TN * 32;
+  f32x16 acc[1][TN];
+  acc_zero(acc);
+  load(0);
+  store(0);
+  __syncthreads();                                           // (also publishes alpha)
+  for (int s = 0; s < nslab; ++s) {
+    if (s + 1 < nslab) load(s + 1);
+    mma_slab_kc_mc<1, TN>(al_s + (size_t)s * TR * SGG_LDK, cx_s + (s & 1) * 32 * CS, CS, wm0, wn0, lane, acc);
+    if (s + 1 < nslab) store((s + 1) & 1);                   // (that buffer was last read before the previous barrier)
+    __syncthreads();
+  }
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int k = k0 + wm0 + acc_row(q, lane);
+      if (k < N) z[((size_t)b + (size_t)k * B) * ldz + c0 + wn0 + tn * 32 + acc_col(lane)] = acc[0][tn][q];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -533,6 +637,22 @@ extern "C" int sgg_attn_step_fwd(const float* P, const float* ec, const float* e
   int rc = attn_check("sgg_attn_step_fwd", R, B, L, C);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
+  // many float rows per image (evaluation: N samples of each image): one read of the feature map per tile of rows.  64-row tiles
+  // while alpha fits beside the staging buffers with room to spare, 32-row tiles up to the LDS size, the per-row kernel beyond.
+  const int N = R / B, tr = attn_rows_lds_bytes(64, L) <= 112 * 1024 ? 64 : 32;
+  if (!ec_dual && N >= ATTN_ROWS_MIN_RATIO && attn_rows_lds_bytes(tr, L) <= ATTN_ROWS_MAX_LDS) {
+    const size_t smb = attn_rows_lds_bytes(tr, L);
+    const dim3 grid(B, sgg_cdiv(N, tr), C / ATTN_ROWS_CS);
+    if (tr == 64) {
+      (void)hipFuncSetAttribute((const void*)attn_step_fwd_rows_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smb);
+      hipLaunchKernelGGL(attn_step_fwd_rows_kernel<64>, grid, dim3(256), smb, st, P, ec, ldec, ctx, alpha, z, ldz, B, N, L, C);
+    } else {
+      (void)hipFuncSetAttribute((const void*)attn_step_fwd_rows_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smb);
+      hipLaunchKernelGGL(attn_step_fwd_rows_kernel<32>, grid, dim3(256), smb, st, P, ec, ldec, ctx, alpha, z, ldz, B, N, L, C);
+    }
+    SGG_LAUNCH_CHECK("sgg_attn_step_fwd");
+    return SGG_OK;
+  }
   const int cs = (R < 256 && C % 512 == 0) ? 2 : 1;      // two workgroups per row (256 channels each) while the rows do not fill the chip
   if (ec_dual) {
     SGG_CHECK_ARG(alpha_dual && z_dual, "sgg_attn_step_fwd: dual outputs missing");

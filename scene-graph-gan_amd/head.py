@@ -35,12 +35,13 @@ def flat2(t):
 
 
 class HeadState:
-    """Activation / cotangent buffers of one head pass with R rows and np planes."""
+    """Activation / cotangent buffers of one head pass with R rows and np planes.  forward_only: activations alone (no backward
+    will run on this state; the cotangent buffers would be ~8 GB at 8192 rows and V = 70 000)."""
 
-    def __init__(self, head, np_, R):
+    def __init__(self, head, np_, R, forward_only=False):
         dev, dt = head.device, head.dtype
         z = lambda *s: torch.zeros(s, device=dev, dtype=dt)
-        self.np, self.R = np_, R
+        self.np, self.R, self.forward_only = np_, R, forward_only
         W, L, Vout = head.width, head.L, head.Vout
         self.C = [z(np_, R, H) for _ in range(T_STEPS + 1)]
         self.XH = [z(np_, R, W) for _ in range(T_STEPS + 1)]
@@ -48,6 +49,8 @@ class HeadState:
         self.AL = [z(np_, R, L) for _ in range(T_STEPS)]
         self.G = [z(np_, R, 4 * H) for _ in range(T_STEPS)]
         self.OUT = z(np_, R, T_STEPS, Vout)
+        if forward_only:
+            return
         self.dOUT = z(np_, R, T_STEPS, Vout)
         self.dXH = [z(np_, R, W) for _ in range(T_STEPS + 1)]
         self.dC = [z(np_, R, H) for _ in range(T_STEPS + 1)]
@@ -118,6 +121,14 @@ class Head:
         key = (np_, R, tag)
         if key not in self._states:
             self._states[key] = HeadState(self, np_, R)
+        return self._states[key]
+
+    def sample_state(self, R):
+        """Forward-only fp32 state for R = N x B sample rows (row k*B + b reads image b): evaluation, never shared with a
+        training state (its own key; backward() would fail on it)."""
+        key = (1, R, "forward-only")
+        if key not in self._states:
+            self._states[key] = HeadState(self, 1, R, forward_only=True)
         return self._states[key]
 
     # ------------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@ sys.path.append(os.getcwd())
 import argparse
 import json
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -258,7 +259,19 @@ class SceneGraphGAN(object):
         self.step = GanStep(kernels_for(self.device), V, S, B, lam=self.LAMBDA, G=g_net, D=d_net, reducer=reducer,
                             overlap_streams=self.two_streams)
 
-    def train(self, max_iterations=None, log_every=10, save_every=0, validate_every=None, test_at_end=None, patience=3):
+    def load_checkpoint(self):
+        """Build both networks and load the checkpoint in checkpoints_dir (weights, Adam state, iteration) as --resume does;
+        False if there is none."""
+        if not os.path.exists(self._ckpt_path()):
+            return False
+        if self.step is None:
+            images, _ = self._next_batch(0)
+            self._constructOps(images)
+        self._loadModel()
+        return True
+
+    def train(self, max_iterations=None, log_every=10, save_every=0, validate_every=None, test_at_end=None, patience=3,
+              test_max_images=None):
         """train.py:341-388.  Every `validate_every` iterations (default: the reference's len(train) / 50 on real data, off in
         synthetic mode) the critic's cost on a validation batch is compared with the previous one: `patience` (3) consecutive
         increases end the training (train.py:375-384); afterwards the model is evaluated (`print "Testing"; self.test(sess)`,
@@ -319,7 +332,7 @@ class SceneGraphGAN(object):
         self._saveModel()
         if test_at_end:
             print("Testing")                                                            # train.py:387-388
-            return self.test()
+            return self.test(max_images=test_max_images)
 
     ############################################################
     ## Testing (train.py:294-335)
@@ -356,16 +369,22 @@ class SceneGraphGAN(object):
         that literally.  The mode in force is written into recalls.txt (third line) and returned with the details.
         Uses the trained weights (the reference's test ops use an untrained copy).
         items: optional list of (image [S,S,3] float tensor, true triples [[s,p,o], ...]) replacing the test split.
-        return_details: also return, per image, the sampled tokens [N,3], their scores [N] and the two recalls."""
+        return_details: also return, per image, the sampled tokens [N,3], their scores [N] and the two recalls.
+
+        Schedule: TEST_BATCH_SIZE distinct images per encoder pass (the last batch padded with its last image, whose results are
+        dropped), all N samples of those images as one head pass of N x TEST_BATCH_SIZE rows (Generator.sample ->
+        Discriminator.score_samples), tokens and critic outputs copied to the host once per batch.  Same samples as the reference's
+        protocol: sample k = pass * TEST_BATCH_SIZE + j of an image uses row j of that image's pass-th [TEST_BATCH_SIZE, 512] noise
+        draw, drawn image after image.  Test-split images are decoded by a thread pool while the previous batch runs."""
         if self.step is None:
             images, _ = self._next_batch(0)
             self._constructOps(images)
         self.step.flush()
         K = kernels_for(self.device)
-        # TEST_BATCH_MULTIPLIER runs of TEST_BATCH_SIZE copies of the image (train.py:139-150, 311-318), at that batch size
-        B = max(1, self.TEST_BATCH_SIZE)
+        TB = max(1, self.TEST_BATCH_SIZE)
         passes = self.TEST_BATCH_MULTIPLIER
-        n_samples = passes * B
+        n_samples = passes * TB
+        decode = None
         if items is not None:
             items = list(items)[:max_images]
         elif self.dataset is None:
@@ -373,25 +392,42 @@ class SceneGraphGAN(object):
             items = [(torch.randn((self.image_size, self.image_size, 3), generator=g),
                       torch.randint(0, len(self.vocab), (5, 3), generator=g).tolist()) for _ in range(max_images or 2)]
         else:
-            items = [(self._parseFunction(k), t) for k, t in self.test_items[:max_images]]
+            items, decode = list(self.test_items[:max_images]), self._parseFunction
+        nb = min(TB, len(items))                        # images per encoder pass
+        pool = ThreadPoolExecutor(max_workers=min(16, nb)) if decode is not None else None
+
+        def fetch(i0):
+            chunk = items[i0:i0 + nb]
+            return [pool.submit(decode, k) for k, _ in chunk] if pool is not None else [im for im, _ in chunk]
+
         gen = torch.Generator().manual_seed(self.seed + 123)
-        toks = torch.empty((B, 3), dtype=torch.int64, device=self.device)
+        toks = torch.empty((n_samples, nb, 3), dtype=torch.int64, device=self.device)
         r50, r100, details = [], [], []
-        for image, triples in items:
-            images = image.unsqueeze(0).expand(B, -1, -1, -1).contiguous().to(self.device)
-            fakes, scores = [], []
-            for _ in range(passes):
-                noise = torch.randn((B, 512), generator=gen).to(self.device)
-                logits = self.g.build_generator(images, False, noise)
+        try:
+            pending = fetch(0) if items else None
+            for i0 in range(0, len(items), nb):
+                imgs = [f.result() for f in pending] if pool is not None else pending
+                pending = fetch(i0 + nb) if i0 + nb < len(items) else None
+                n = len(imgs)
+                images = torch.stack(imgs + [imgs[-1]] * (nb - n)).to(self.device)
+                noise = torch.zeros((n_samples, nb, 512))
+                for j in range(n):
+                    for p in range(passes):
+                        noise[p * TB:(p + 1) * TB, j] = torch.randn((TB, 512), generator=gen)
+                logits = self.g.sample(images, n_samples, noise.to(self.device))
                 K.argmax_rows(logits, toks.view(-1))
-                d = self.d.build_discriminator(logits, images, False)
-                fakes.append(toks.cpu().numpy().copy())
-                scores.append(d.mean(dim=1).reshape(-1).cpu().numpy())
-            fake, score = np.concatenate(fakes)[:n_samples], np.concatenate(scores)[:n_samples]
-            a, b = self.recalls(fake, score, triples, reference_literal)
-            r50.append(a)
-            r100.append(b)
-            details.append({"tokens": fake, "scores": score, "r50": a, "r100": b})
+                d = self.d.score_samples(logits, images)
+                tok_h, d_h = toks.cpu().numpy(), d.cpu().numpy()
+                score_h = d_h.mean(axis=2).reshape(n_samples, nb)
+                for j in range(n):
+                    fake, score = tok_h[:, j].copy(), score_h[:, j].copy()
+                    a, b = self.recalls(fake, score, items[i0 + j][1], reference_literal)
+                    r50.append(a)
+                    r100.append(b)
+                    details.append({"tokens": fake, "scores": score, "r50": a, "r100": b})
+        finally:
+            if pool is not None:
+                pool.shutdown(wait=True, cancel_futures=True)
         res = (float(np.mean(r50)), float(np.mean(r100)))
         ordering = "reference_literal ([N,1] argsort: sample 0 repeated)" if reference_literal else "ascending mean critic score"
         if self.rank == 0 and out_path:
@@ -444,6 +480,9 @@ if __name__ == "__main__":
                                                                          "len(train) / 50 on real data as train.py:162, off with --synthetic)")
     parser.add_argument("--recompute_generator_encoder", action="store_true",
                         help="run G's encoder in every update like the reference graph (default: once per iteration, same result)")
+    parser.add_argument("--test_only", action="store_true",
+                        help="load the checkpoint in --checkpoints_dir, compute R@50 / R@100 (recalls.txt) and exit; no training")
+    parser.add_argument("--max_test_images", default=None, type=int, help="evaluate the first N test images only")
     args = parser.parse_args()
     params = vars(args)
 
@@ -457,4 +496,12 @@ if __name__ == "__main__":
                         critic_iters=params["critic_iters"], batch_size=params["batch_size"], lambda_=params["lambda"],
                         resume=params["resume"], synthetic=synthetic, two_streams=not params["single_stream"],
                         reuse_g_encoder=not params["recompute_generator_encoder"], shuffle_buffer=not params["no_shuffle_buffer"])
-    gan.train(max_iterations=params["max_iterations"], validate_every=params["validate_every"])
+    if params["test_only"]:
+        if not gan.load_checkpoint():
+            print("--test_only: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
+                  file=sys.stderr)
+            sys.exit(2)
+        gan.test(max_images=params["max_test_images"])
+    else:
+        gan.train(max_iterations=params["max_iterations"], validate_every=params["validate_every"],
+                  test_max_images=params["max_test_images"])
