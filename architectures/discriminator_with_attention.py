@@ -5,6 +5,8 @@ Same import path, constructor and method signatures as the reference (discrimina
     Discriminator.build_discriminator(input_triples, images, is_training=True) -> critic logits [B, 3, 1]
     Discriminator.attentionMechanism(cell_state) -> z_hat [B, 512]
 Added (evaluation): Discriminator.score_samples(input_triples [N, B, 3, vocab], images) -> [N, B, 3, 1] on one encoder pass.
+Added (input gradients): Discriminator.input_gradients(input_triples, images, d_scores [B, 3, 1]) -> (d_triples [B, 3, vocab],
+d_images [B, S, S, 3]), the vector-Jacobian product of build_discriminator (tf.gradients(disc_fake, [inputs, images], d_scores)).
 `input_triples` is float32 [B, 3, vocab]: one-hot real triples or raw generator logits (train.py:173, 242).
 `embedding_matrix` [vocab, 300] is created by the trainer and trained by the critic's optimiser
 (train.py:68-72, 263); here its storage moves into the critic's parameter arena and `self.embedding_matrix`
@@ -19,6 +21,7 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 import sgg_amd  # noqa: E402,F401
+from sgg_amd import grad  # noqa: E402
 from sgg_amd.api import NetworkHandle  # noqa: E402
 
 
@@ -55,3 +58,16 @@ class Discriminator(NetworkHandle):
         net.head.forward(st, ctx, [input_triples.contiguous().view(N * B, 3, self.vocab_size)])
         self._publish(ctx, st)
         return st.OUT[0].view(N, B, 3, 1)
+
+    def input_gradients(self, input_triples, images, d_scores):
+        """Gradients of <d_scores, build_discriminator(input_triples, images)>: input_triples [B, 3, vocab] (one-hots or logits),
+        images [B, S, S, 3], d_scores [B, 3, 1] -> (d_triples [B, 3, vocab], d_images [B, S, S, 3]), new tensors.  A data-only
+        backward (sgg_amd/grad.py): the weights, their gradients and the optimiser state are not touched."""
+        net = self._ensure(images)
+        B = int(images.shape[0])
+        assert tuple(input_triples.shape) == (B, 3, self.vocab_size), input_triples.shape
+        assert tuple(d_scores.shape) == (B, 3, 1), d_scores.shape
+        d_tri, d_img, st, ctx = grad.discriminator_input_gradients(net, input_triples.contiguous(), images.contiguous(),
+                                                                   d_scores.contiguous())
+        self._publish(ctx, st)
+        return d_tri, d_img

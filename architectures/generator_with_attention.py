@@ -6,6 +6,8 @@ Same import path, constructor and method signatures as the reference (generator_
     Generator.attentionMechanism(cell_state)            -> z_hat  [B, 512]           (cell_state = (c, h), c is used)
     attributes after a build: downsampled, flattened_context, partially_flattened_context, alpha
 Added (evaluation): Generator.sample(images, num_samples, noise=None) -> logits [N, B, 3, vocab] on one encoder pass.
+Added (input gradients): Generator.image_gradient(images, d_logits, noise=None) -> [B, S, S, 3], the vector-Jacobian product of
+build_generator with respect to the images (what tf.gradients(fake_inputs, images, d_logits) gives in the reference graph).
 In the reference these methods add TensorFlow ops to a graph; here they run eagerly on the GPU: every arithmetic
 op is a hand-written HIP kernel behind the C ABI of libsgg_hip.so (include/sgg_hip.h).  Repeated builds share one
 set of weights, as `reuse=tf.AUTO_REUSE` does (train.py:86).  `is_training` is accepted and ignored, as in the
@@ -22,6 +24,7 @@ if _ROOT not in sys.path:
 import torch  # noqa: E402
 
 import sgg_amd  # noqa: E402,F401
+from sgg_amd import grad  # noqa: E402
 from sgg_amd.api import NetworkHandle  # noqa: E402
 
 
@@ -61,3 +64,28 @@ class Generator(NetworkHandle):
         net.head.forward(st, ctx, noise.contiguous().view(N * B, 512))
         self._publish(ctx, st)
         return st.OUT[0].view(N, B, 3, self.vocab_size)
+
+    def image_gradient(self, images, d_logits, noise=None):
+        """d <d_logits, build_generator(images, noise)> / d images: images [B, S, S, 3] (standardised), d_logits [B, 3, vocab] ->
+        [B, S, S, 3] (a new tensor).  `noise` [B, 512] as in build_generator (torch.randn if None).  A data-only backward
+        (sgg_amd/grad.py): the weights, their gradients and the optimiser state are not touched.  The build's attributes
+        (downsampled, alpha, alphas) are published as by build_generator."""
+        net = self._ensure(images)
+        B = int(images.shape[0])
+        if noise is None:
+            noise = torch.randn((B, 512), device=images.device, dtype=torch.float32)
+        assert tuple(d_logits.shape) == (B, 3, self.vocab_size), d_logits.shape
+        dimages, st, ctx = grad.generator_image_gradient(net, images.contiguous(), noise.contiguous(), d_logits.contiguous())
+        self._publish(ctx, st)
+        return dimages
+
+    def saliency_gradients(self, images, noise=None):
+        """The generator's argmax triple and, per word t, d logit[b, t, token_bt] / d image[b] - three data-only backwards from ONE
+        forward (one noise draw for all three words).  Returns (tokens [B, 3] int64, grads [3, B, S, S, 3], noise); the attention of
+        the three steps is published in `alphas`."""
+        net = self._ensure(images)
+        if noise is None:
+            noise = torch.randn((images.shape[0], 512), device=images.device, dtype=torch.float32)
+        tokens, grads, st, ctx = grad.generator_saliency(net, images.contiguous(), noise.contiguous())
+        self._publish(ctx, st)
+        return tokens, grads, noise

@@ -180,14 +180,28 @@ int sgg_layernorm_hwc_elu_bwd_sums(const float* y, const float* da, const float*
 /* conv1_1's filter gradient FUSED with the apply half of the LayerNorm backward of its output (generator_with_attention.py:29-30
  * under optimizer.minimize, train.py:265-266): dW [3][3][3][32] = Conv2DBackpropFilter(x, dy) with
  *   dy = rstd * (da * ELU'(n) * gamma - m1 - xhat * m2),  xhat = (y - mean) * rstd,  n = xhat * gamma + beta
- * computed from (y, da) [B][H][W][32] inside the kernel - conv1_1's filter gradient is the only consumer of that dy (no image
- * gradient is taken, the bias gradient comes from the LayerNorm reductions), so it is never written: one read of y and da replaces
- * the apply pass (read y, read da, write dy) and the filter gradient's read of dy.  stats [B][2] = (mean, rstd) of the forward,
+ * computed from (y, da) [B][H][W][32] inside the kernel - in the training step conv1_1's filter gradient is the only consumer of
+ * that dy (the step takes no image gradient, the bias gradient comes from the LayerNorm reductions; an image gradient reads it
+ * through sgg_conv2d_nhwc_dgrad_c3_ln), so it is never written: one read of y and da replaces the apply pass (read y, read da,
+ * write dy) and the filter gradient's read of dy.  stats [B][2] = (mean, rstd) of the forward,
  * means [B][2] from sgg_layernorm_hwc_elu_bwd_sums; exact f32 MFMA arithmetic as sgg_conv2d_nhwc_wgrad with Cin == 3; workspace as
  * sgg_conv2d_nhwc_wgrad_workspace_bytes(B, H, W, 3, H, W, 32, 3, 3). */
 int sgg_conv2d_nhwc_wgrad_c3_ln(const float* x, const float* y, const float* da, const float* gamma, const float* beta,
                                 const float* stats, const float* means, float* dw, int B, int H, int W, int pad_t, int pad_l,
                                 void* workspace, size_t workspace_bytes, void* stream);
+/* conv1_1's INPUT gradient: Conv2DBackpropInput of the first convolution (architectures/generator_with_attention.py:29, the same
+ * layer in the critic), the last link of an image gradient (saliency maps, input perturbations; sgg_amd/grad.py):
+ *   dx [B][H][W][3] = sum_{kh,kw,co} dy[b, y+1-kh, x+1-kw, co] * w_hwio[kh][kw][ci][co]      3x3, stride 1, SAME (pad_t = pad_l = 1)
+ * from dy [B][H][W][32].  Exact f32 (fmaf chains) in every precision mode, fixed summation order (two calls are bit-equal); any
+ * B, H, W.  sgg_conv2d_nhwc_dgrad rejects Cin == 3. */
+int sgg_conv2d_nhwc_dgrad_c3(const float* dy, const float* w_hwio, float* dx, int B, int H, int W, int pad_t, int pad_l, void* stream);
+/* The same with dy COMPUTED inside the kernel from the LayerNorm backward's operands, as sgg_conv2d_nhwc_wgrad_c3_ln does:
+ *   dy = rstd * (da * ELU'(n) * gamma - m1 - xhat * m2),  xhat = (y - mean) * rstd,  n = xhat * gamma + beta
+ * y, da [B][H][W][32]; stats [B][2] = (mean, rstd) of the forward; means [B][2] from sgg_layernorm_hwc_elu_bwd_sums.  dy is never
+ * written: one read of y and da replaces the apply pass and the plain kernel's read of dy.  Whole planes only. */
+int sgg_conv2d_nhwc_dgrad_c3_ln(const float* y, const float* da, const float* gamma, const float* beta, const float* stats,
+                                const float* means, const float* w_hwio, float* dx, int B, int H, int W, int pad_t, int pad_l,
+                                void* stream);
 
 /* dgamma == dbeta == NULL in sgg_layernorm_hwc_elu_bwd DEFERS the parameter-gradient reductions (dgamma, dbeta, dbias_prev): the
  * partial sums stay in `workspace` (give every layer its own), and one launch of sgg_layernorm_hwc_bwd_finalize reduces up to 16

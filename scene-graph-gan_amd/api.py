@@ -80,6 +80,12 @@ class NetworkHandle(object):
         self.flattened_context = ctx.view(B, L * FEAT_C)
         self.partially_flattened_context = ctx
         self.alpha = st.AL[-1][0]
+        self._alphas = st.AL
+
+    @property
+    def alphas(self):
+        """[B, 3, L]: the attention of each of the three steps of the last build (alpha is the last step's, as in the reference)."""
+        return torch.stack([a[0] for a in self._alphas], dim=1)
 
     def _attention(self, cell_state):
         """attentionMechanism: z_hat for an arbitrary (c, h) state on the current feature map."""

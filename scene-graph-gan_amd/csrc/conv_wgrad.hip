@@ -494,7 +494,8 @@ __device__ __forceinline__ void c3w_lds_barrier() {
 // pre-LayerNorm y, the gradient da of the activation, gamma, beta, the per-sample (mean, rstd) and the two per-sample means m1 =
 // mean(dxhat), m2 = mean(dxhat * xhat) of sgg_layernorm_hwc_elu_bwd_sums), with the arithmetic of ln_bwd_apply_kernel
 // (csrc/layernorm.hip):  dy = rstd * (da * ELU'(n) * gamma - m1 - xhat * m2),  xhat = (y - mean) * rstd,  n = xhat * gamma + beta.
-// conv1_1's filter gradient is the ONLY consumer of that dy (no image gradient is needed, the bias gradient comes from the
+// in the training step conv1_1's filter gradient is the ONLY consumer of that dy (the step takes no image gradient - an image
+// gradient computes it the same way in conv_c3_dgrad_kernel<true>, csrc/conv_dgrad_c3.hip - and the bias gradient comes from the
 // LayerNorm reductions), so the LayerNorm backward's apply pass - 411 MB read twice and 411 MB written at batch 64, on the tail of
 // every encoder backward where nothing else can run - and this kernel's 411 MB read of dy become ONE read of y and da.
 struct C3LnArgs {

@@ -186,11 +186,16 @@ class Head:
             K.gemm_tn(X[0][:R_w], dY[1][:R_w], dW, accumulate=True)
             K.gemm_tn(X[1][:R_w], dY[0][:R_w], dW, accumulate=True)
 
-    def backward(self, st, ctx, u, R_w, labels=None, label_rows=None):
+    def backward(self, st, ctx, u, R_w, labels=None, label_rows=None, param_grads=True):
         """Backward of `forward` from st.dOUT. Rows [0, R_w) contribute to parameter / dP / dctx gradients (all
         accumulated); every row gets its data cotangents (st.dXH[t][:, :, 512:in] = cotangent of u_t).
-        labels / label_rows as in forward: the embedding gradient of the one-hot rows is a row scatter-add."""
+        labels / label_rows as in forward: the embedding gradient of the one-hot rows is a row scatter-add.
+        param_grads=False (data-only backward, sgg_amd/grad.py): EVERY row feeds dP / dctx and the spatial-mean backward (R_w is
+        ignored) and no parameter gradient is computed - the gradient arena is not touched, nothing goes to the side stream."""
         K, np_, R, ind = self.K, st.np, st.R, self.in_dim
+        if not param_grads:
+            self._data_backward(st, ctx)
+            return
         import contextlib
         on = lambda strm: torch.cuda.stream(strm) if strm is not None else contextlib.nullcontext()
         pc = np_ - 1                                    # plane holding cotangents of real quantities
@@ -253,10 +258,31 @@ class Head:
                 for fn in deferred:
                     fn()
 
-    def finish_backward(self, ctx):
-        """Gradients that flow through the step-invariant score P (after every head pass of the step)."""
+    def _data_backward(self, st, ctx):
+        """backward(..., param_grads=False): the chain of backward() with every row in the dP / dctx rows and no parameter gradient."""
+        K, np_, R, ind = self.K, st.np, st.R, self.in_dim
+        pc = np_ - 1
+        for t in range(T_STEPS - 1, -1, -1):
+            dout = st.dOUT[:, :, t, :]
+            dh = st.dXH[t + 1][:, :, ind:]
+            dG, dE = st.dG[t], st.dE[t]
+            for pl in range(np_):
+                K.gemm_nt(dout[pl], self.W_dec, dh[pl], accumulate=(t < T_STEPS - 1))
+            K.lstm_bwd(st.G[t], st.C[t], self.ln, dh, st.dC[t + 1] if t < T_STEPS - 1 else None, dG, st.dC[t],
+                       st.pgrad[t * R:(t + 1) * R])
+            K.gemm_nt(flat2(dG), self.Kk, flat2(st.dXH[t]))
+            K.attn_step_bwd(ctx, st.AL[t], st.dXH[t][:, :, :C], dE, self.dP, self.dctx, True)
+            K.gemm_nt(flat2(dE), self.W_c, flat2(st.dC[t]), accumulate=True)
+        K.spatial_mean_bwd(st.dC[0][pc], st.dXH[0][pc][:, ind:], self.dctx, True)
+
+    def finish_backward(self, ctx, param_grads=True):
+        """Gradients that flow through the step-invariant score P (after every head pass of the step).
+        param_grads=False: the data path only (attn_ctx_dgrad; no bias column sum, no attn_ctx_wgrad)."""
         K, B, L = self.K, self.B, self.L
         ctx_flat = ctx.view(B, L * C)
+        if not param_grads:
+            K.attn_ctx_dgrad(self.dP, self.W_ctx, self.dctx.view(B, L * C), accumulate=True)
+            return self.dctx
         # the parameter gradients (79 MB of attention weights) beside the dgrad that the encoder backward waits for; joined by
         # join() before the gradients are read (GanStep: before the all-reduce / Adam step)
         side = self._fork()

@@ -56,6 +56,8 @@ SIGNATURES = {
     "sgg_gemm_skinny_wgrad": (_i, [_i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
     "sgg_layernorm_hwc_elu_bwd_sums": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "sgg_conv2d_nhwc_wgrad_c3_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "sgg_conv2d_nhwc_dgrad_c3": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sgg_conv2d_nhwc_dgrad_c3_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sgg_attn_ctx_gemm_fwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgg_attn_ctx_gemm_dgrad": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "sgg_attn_ctx_gemm_wgrad": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
@@ -572,6 +574,34 @@ class HipKernels:
         self._check(self._timed("conv_c3_wgrad_ln(call: LN-backward apply fused + slab reduce)", flops, lambda: self.lib.sgg_conv2d_nhwc_wgrad_c3_ln(
             _p(x), _p(y), _p(da), _p(gamma), _p(beta), _p(stats), _p(means), _p(dw), B, H, W, 1, 1, _p(ws), ws.numel(), self._stream()), nb),
             "sgg_conv2d_nhwc_wgrad_c3_ln")
+
+    def conv_c3_dgrad(self, dy, w_hwio, dx):
+        """conv1_1's input gradient: dx [B,H,W,3] = Conv2DBackpropInput(dy [B,H,W,32], w [3,3,3,32]), 3x3 stride 1 SAME, exact f32."""
+        self._dev(dy, w_hwio, dx)
+        B, H, W, _ = dx.shape
+        if tuple(dy.shape) != (B, H, W, 32) or tuple(w_hwio.shape) != (3, 3, 3, 32) or tuple(dx.shape) != (B, H, W, 3):
+            raise SggError("conv_c3_dgrad: shapes dy %s, w %s, dx %s (want [B,H,W,32], [3,3,3,32], [B,H,W,3])"
+                           % (tuple(dy.shape), tuple(w_hwio.shape), tuple(dx.shape)))
+        assert dy.is_contiguous() and w_hwio.is_contiguous() and dx.is_contiguous()
+        flops = 2.0 * B * H * W * 32 * 27
+        nb = 4.0 * (dy.numel() + dx.numel())
+        self._check(self._timed("conv_c3_dgrad_kernel<false>", flops, lambda: self.lib.sgg_conv2d_nhwc_dgrad_c3(
+            _p(dy), _p(w_hwio), _p(dx), B, H, W, 1, 1, self._stream()), nb), "sgg_conv2d_nhwc_dgrad_c3")
+
+    def conv_c3_dgrad_ln(self, y, da, gamma, beta, stats, means, w_hwio, dx):
+        """conv_c3_dgrad with dy = LayerNormBackward(y, da) computed inside the kernel (means from ln_elu_bwd_sums; include/sgg_hip.h)."""
+        self._dev(y, da, gamma, beta, stats, means, w_hwio, dx)
+        B, H, W, _ = dx.shape
+        if (tuple(y.shape) != (B, H, W, 32) or tuple(da.shape) != (B, H, W, 32) or tuple(w_hwio.shape) != (3, 3, 3, 32)
+                or tuple(dx.shape) != (B, H, W, 3) or tuple(stats.shape) != (B, 2) or tuple(means.shape) != (B, 2)):
+            raise SggError("conv_c3_dgrad_ln: shapes y %s, da %s, stats %s, means %s, w %s, dx %s" % tuple(
+                tuple(t.shape) for t in (y, da, stats, means, w_hwio, dx)))
+        assert all(t.is_contiguous() for t in (y, da, gamma, beta, stats, means, w_hwio, dx))
+        flops = 2.0 * B * H * W * 32 * 27
+        nb = 4.0 * (y.numel() + da.numel() + dx.numel())
+        self._check(self._timed("conv_c3_dgrad_kernel<true>", flops, lambda: self.lib.sgg_conv2d_nhwc_dgrad_c3_ln(
+            _p(y), _p(da), _p(gamma), _p(beta), _p(stats), _p(means), _p(w_hwio), _p(dx), B, H, W, 1, 1, self._stream()), nb),
+            "sgg_conv2d_nhwc_dgrad_c3_ln")
 
     def ln_workspace_bytes(self, shape):
         B, H, W, C = shape

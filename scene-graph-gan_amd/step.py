@@ -56,6 +56,7 @@ class Network:
             self.opt = {"t": 0, "pending": None}
         self.trunk = Trunk(K, self.arena, self.grads, B, S)
         self.head = Head(K, kind, self.arena, self.grads, B, self.trunk.L)
+        self.data_passes = 0                 # input-gradient passes on this network's buffers (sgg_amd/grad.py; GanStep._g_early_stream)
 
     adam_t = property(lambda self: self.opt["t"], lambda self, v: self.opt.__setitem__("t", v))
     pending = property(lambda self: self.opt["pending"], lambda self, v: self.opt.__setitem__("pending", v))
@@ -152,6 +153,9 @@ class GanStep:
         # stream, unordered against the main stream's writes
         if ev_images[2] != (self.G.arena.version, self.G.adam_t):
             return None
+        # ... and only if no input-gradient pass (sgg_amd/grad.py) has used G's encoder buffers on the main stream since then
+        if ev_images[3] != self.G.data_passes:
+            return None
         if getattr(self, "xs", None) is None:
             self.xs = torch.cuda.Stream(device=images.device)
         self.xs.wait_event(ev)
@@ -240,7 +244,7 @@ class GanStep:
             # G's encoder buffers are free from here on, and this critic update does not touch G's weights (_g_early_stream)
             self._ev_g_free = torch.cuda.Event()
             self._ev_g_free.record()
-            self._ev_g_images = (images, images._version, (self.G.arena.version, self.G.adam_t))
+            self._ev_g_images = (images, images._version, (self.G.arena.version, self.G.adam_t), self.G.data_passes)
         self._join_side()
         fake_rows.copy_(gst.OUT[0])
         K.onehot(labels, real_rows)

@@ -425,14 +425,28 @@ class Trunk:
         if stream is not None and getattr(self, "_dY2", None) is None:
             self._dY2 = torch.empty_like(self._dY)
 
-    def backward(self, dctx):
-        """dctx [B, L, 512]: gradient w.r.t. `downsampled`. Writes every live conv / LN parameter gradient."""
+    def _pg_scratch(self, lay):
+        """(dgamma, dbeta, dbias) scratch of a LayerNorm layer for a data-only backward on kernels that write the LayerNorm's
+        parameter gradients with its backward (no deferred finalize): nothing of the gradient arena is touched."""
+        if "pg_scratch" not in lay:
+            lay["pg_scratch"] = tuple(torch.empty_like(t) for t in (lay["ggamma"], lay["gbeta"], lay["gb"]))
+        return lay["pg_scratch"]
+
+    def backward(self, dctx, param_grads=True, dimages=None):
+        """dctx [B, L, 512]: gradient w.r.t. `downsampled`. Writes every live conv / LN parameter gradient.
+
+        param_grads=False (data-only backward, sgg_amd/grad.py): no filter gradient, no bias column sum, no LayerNorm finalize, no
+        write to the gradient arena (LayerNorm backwards that insist on writing dgamma / dbeta / dbias get scratch), everything on the
+        current stream.  dimages [B, S, S, 3]: the loop continues into conv1_1's input gradient, the gradient w.r.t. the images given
+        to forward() (on a canvas: taken on the canvas and cropped to the image window, outside which the LayerNorm wrote zeros)."""
         K, B = self.K, self.B
         assert getattr(self, "_fwd_for_backward", True), "the last forward was run with for_backward=False"
+        if not param_grads and dimages is None:
+            return                                 # (nothing to compute)
         dy = dctx.view(B, self.Hf, self.Wf, FEAT_C)
         n = len(self.layers)
         f16 = self._f16()
-        side = getattr(self, "wgrad_stream", None)
+        side = getattr(self, "wgrad_stream", None) if param_grads else None
         main = torch.cuda.current_stream() if side is not None else None
         dybufs = [self._dY, self._dY2] if side is not None else [self._dY]
         reader_done = [None] * len(dybufs)        # event: the wgrad that reads this dY buffer has finished
@@ -485,12 +499,12 @@ class Trunk:
                         reader_done[cur] = torch.cuda.Event()
                         reader_done[cur].record(side)
             late = side is not None and j > 0 and bool(getattr(K, "wgrad_late", False))
-            if side is None:
+            if param_grads and side is None:
                 wgrad()
-            elif not late:
+            elif param_grads and not late:
                 side.wait_stream(main)            # dy_j (and its amax word) are complete
                 wgrad_on_side()
-            if not lay["has_ln"] and side is None:
+            if not lay["has_ln"] and side is None and param_grads:
                 # last conv: BiasAddGrad = column sums of dy (LN layers get theirs from ln_elu_bwd below)
                 K.colsum(dy_f32.view(-1, lay["cout"]), lay["gb"], False)
             if j == 0:
@@ -521,7 +535,8 @@ class Trunk:
                 wgrad_on_side()
             nxt_s16 = bool(prev.get("dy_s16")) and prev.get("ws_mode") == getattr(K, "conv_precision", 0) and self._ln_fin is not None
             if (j == 1 and prev["cin"] == 3 and prev["region"] is None and self._ln_fin is not None and hasattr(K, "conv_c3_wgrad_ln")
-                    and getattr(K, "c3_ln_bwd_fused", False) and prev["out_shape"][3] == 32):
+                    and getattr(K, "c3_ln_bwd_fused", False) and prev["out_shape"][3] == 32
+                    and (dimages is None or hasattr(K, "conv_c3_dgrad_ln"))):
                 # conv1_1's LayerNorm: the reductions only.  Its dy has ONE consumer, conv1_1's filter gradient, which computes it
                 # from (y, dA) itself (sgg_conv2d_nhwc_wgrad_c3_ln): no apply pass, no dy tensor.  dA stays untouched until then
                 # (the loop ends with that filter gradient; the next backward on this encoder is ordered behind it).
@@ -537,16 +552,41 @@ class Trunk:
             elif self._ln_fin is not None:
                 K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, None, None, None, self._am(1, j - 1) if f16 else None,
                              region=prev["region"], ws=prev["ln_ws"])
-            elif prev["region"] is not None:
-                K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, prev["ggamma"], prev["gbeta"], prev["gb"],
-                             *([self._am(1, j - 1)] if f16 else []), region=prev["region"])
-            elif f16:
-                K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, prev["ggamma"], prev["gbeta"], prev["gb"],
-                             self._am(1, j - 1))
             else:
-                K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, prev["ggamma"], prev["gbeta"], prev["gb"])
+                pg = (prev["ggamma"], prev["gbeta"], prev["gb"]) if param_grads else self._pg_scratch(prev)
+                if prev["region"] is not None:
+                    K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, *pg, *([self._am(1, j - 1)] if f16 else []),
+                                 region=prev["region"])
+                elif f16:
+                    K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, *pg, self._am(1, j - 1))
+                else:
+                    K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, *pg)
             dy, cur, dy_s16 = dYp, nxt, nxt_s16
-        if self._ln_fin is not None:
+        if dimages is not None:
+            self._image_grad(dy, c3_fused, dimages)
+        if self._ln_fin is not None and param_grads:
             K.ln_bwd_finalize(self._ln_fin)       # dgamma, dbeta and the conv bias gradients of all eleven LayerNorms
         if side is not None:
             main.wait_stream(side)                # every filter gradient is complete before the optimiser / all-reduce reads it
+
+    def _image_grad(self, dy0, c3_fused, dimages):
+        """conv1_1's input gradient (Conv2DBackpropInput) into dimages [B, S, S, 3] from its dy (dy0), or - when the LayerNorm
+        backward ran without its apply pass (c3_fused = dA of layer 0) - from the LayerNorm backward's operands."""
+        K, lay = self.K, self.layers[0]
+        assert tuple(dimages.shape) == (self.B, self.S, self.S, 3), dimages.shape
+        direct = self.img_canvas is None and dimages.is_contiguous()
+        if direct:
+            dx = dimages
+        else:
+            if getattr(self, "_dimg", None) is None:
+                self._dimg = torch.empty(lay["in_shape"], device=lay["y"].device, dtype=lay["y"].dtype)
+            dx = self._dimg
+        if c3_fused is not None:
+            K.conv_c3_dgrad_ln(lay["y"], c3_fused, lay["gamma"], lay["beta"], lay["stats"], self._ln0_means, lay["w"], dx)
+        elif hasattr(K, "conv_c3_dgrad"):
+            K.conv_c3_dgrad(dy0, lay["w"], dx)
+        else:
+            K.conv_dgrad(dy0, lay["w"], dx, lay["s"])
+        if not direct:
+            o = self.img_off
+            dimages.copy_(dx[:, o:o + self.S, o:o + self.S])

@@ -1,6 +1,7 @@
 """Entry point mirroring the reference's train.py (class SceneGraphGAN + the same CLI flags), MI355X-native.
 
     python train.py --synthetic 64,224,1000 --max_iterations 20           # no Visual Genome files needed
+    python train.py --checkpoints_dir ckpt --saliency_dir maps             # per-word saliency maps of the test split
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -444,6 +445,64 @@ class SceneGraphGAN(object):
         kernels_for(images.device).argmax_rows(logits, toks.view(-1))
         return toks, [[self.reverse_vocab.get(int(i), "UNK") for i in row] for row in toks.cpu()]
 
+    ############################################################
+    ## Saliency (input gradients, sgg_amd/grad.py)
+    ############################################################
+    def saliency(self, images, noise=None):
+        """Which pixels drove each word of the generator's triple: images [B, S, S, 3] (standardised), noise [B, 512] (torch.randn if
+        None).  Returns a dict of device tensors: tokens [B, 3] (argmax, as sample_triples), words, attention [B, 3, Hf, Wf] (the
+        attention of each step), saliency [B, 3, S, S] = max over channels of |d logit[b, t, token_bt] / d image[b]| (Simonyan et
+        al. 2014), and the noise used.  All three words share one noise draw and one forward pass; each word's gradient is its own
+        data-only backward from that pass (Generator.saliency_gradients).  The weights and optimiser state are not touched."""
+        if self.step is not None:
+            self.step.flush()
+        tokens, grads, noise = self.g.saliency_gradients(images, noise)
+        B, S = int(images.shape[0]), int(images.shape[1])
+        al = self.g.alphas
+        side = int(round(al.shape[-1] ** 0.5))
+        words = [[self.reverse_vocab.get(int(i), "UNK") for i in row] for row in tokens.cpu()]
+        return {"tokens": tokens, "words": words, "attention": al.view(B, 3, side, side),
+                "saliency": grads.abs().amax(dim=-1).permute(1, 0, 2, 3).contiguous(), "noise": noise}
+
+    def _saliency_items(self, max_images=None):
+        """(key, image or path) of the images --saliency_dir covers: the test split, or with --synthetic the synthetic test images of
+        test() (same seed)."""
+        if self.dataset is None:
+            g = torch.Generator().manual_seed(self.seed + 99)
+            out = []
+            for i in range(max_images or 2):
+                out.append((str(i), torch.randn((self.image_size, self.image_size, 3), generator=g)))
+                torch.randint(0, len(self.vocab), (5, 3), generator=g)      # (test()'s true triples: same image sequence)
+            return out
+        return [(k, k) for k, _ in self.test_items[:max_images]]
+
+    def write_saliency(self, out_dir, max_images=None):
+        """Saliency maps of the test images, TEST_BATCH_SIZE images per call, seeded noise: one <index>.npz per image (tokens, words,
+        attention, saliency, noise) and index.json (image path or index -> npz file and words)."""
+        os.makedirs(out_dir, exist_ok=True)
+        items = self._saliency_items(max_images)
+        nb = max(1, min(self.TEST_BATCH_SIZE, len(items)))
+        gen = torch.Generator().manual_seed(self.seed + 321)
+        index = {}
+        for i0 in range(0, len(items), nb):
+            chunk = items[i0:i0 + nb]
+            imgs = [self._parseFunction(x) if isinstance(x, str) else x for _, x in chunk]
+            n = len(imgs)
+            images = torch.stack(imgs + [imgs[-1]] * (nb - n)).to(self.device)      # (the last batch padded with its last image)
+            noise = torch.randn((nb, 512), generator=gen).to(self.device)
+            r = self.saliency(images, noise)
+            tok, att, sal, nz = (r[k].cpu().numpy() for k in ("tokens", "attention", "saliency", "noise"))
+            for j in range(n):
+                name = "%06d.npz" % (i0 + j)
+                np.savez(os.path.join(out_dir, name), tokens=tok[j], words=np.array(r["words"][j]), attention=att[j], saliency=sal[j],
+                         noise=nz[j])
+                index[chunk[j][0]] = {"file": name, "words": r["words"][j]}
+        with open(os.path.join(out_dir, "index.json"), "w") as f:
+            json.dump(index, f, indent=1)
+        if self.rank == 0:
+            print({"saliency_dir": out_dir, "images": len(items)})
+        return index
+
 
 def _str2bool(v):
     """--resume of the reference is `type=bool` (train.py:410), which makes every non-empty string - "False" included - true."""
@@ -483,6 +542,9 @@ if __name__ == "__main__":
     parser.add_argument("--test_only", action="store_true",
                         help="load the checkpoint in --checkpoints_dir, compute R@50 / R@100 (recalls.txt) and exit; no training")
     parser.add_argument("--max_test_images", default=None, type=int, help="evaluate the first N test images only")
+    parser.add_argument("--saliency_dir", default=None,
+                        help="load the checkpoint in --checkpoints_dir, write per-word saliency maps of the test images (one .npz per "
+                             "image + index.json) to this directory and exit; no training")
     args = parser.parse_args()
     params = vars(args)
 
@@ -496,7 +558,13 @@ if __name__ == "__main__":
                         critic_iters=params["critic_iters"], batch_size=params["batch_size"], lambda_=params["lambda"],
                         resume=params["resume"], synthetic=synthetic, two_streams=not params["single_stream"],
                         reuse_g_encoder=not params["recompute_generator_encoder"], shuffle_buffer=not params["no_shuffle_buffer"])
-    if params["test_only"]:
+    if params["saliency_dir"]:
+        if not gan.load_checkpoint():
+            print("--saliency_dir: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
+                  file=sys.stderr)
+            sys.exit(2)
+        gan.write_saliency(params["saliency_dir"], max_images=params["max_test_images"])
+    elif params["test_only"]:
         if not gan.load_checkpoint():
             print("--test_only: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
                   file=sys.stderr)
