@@ -25,6 +25,16 @@ def _rowmap(R, B, device=None):
 class RefKernels:
     name = "ref"
 
+    # The run-time options of sgg_amd.lib.DEFAULT_OPTIONS as a kernel set WITHOUT resident kernels, operand formats or streams means
+    # them (sgg_amd.trunk / step read them as attributes): plain f32 convolutions, every LayerNorm a pass of its own, one stream.
+    conv_precision = 0
+    conv_halo = halo_pc = halo_pc64 = False
+    ln_fusion = 0
+    ln_fusion_skip = ln_fusion_force = ln_fusion_force_bwd = ln_fusion_skip_bwd = ()
+    presplit = presplit_head_grad = False
+    wgrad_late = c3_ln_bwd_fused = False
+    side_priority = g_early = g_early_cus = d_side_cus = fwd_cus = 0
+
     def __init__(self, device="cpu"):
         self.device = torch.device(device)
 
@@ -32,22 +42,29 @@ class RefKernels:
     def hwio_to_hwoi(self, w, wt):
         wt.copy_(w.permute(0, 1, 3, 2))
 
-    def conv_fwd(self, x, w_hwio, w_fwd, bias, y, stride):
+    # The five encoder ops take the optional operands of HipKernels at the same positions.  The amax words, weight layouts, workspaces,
+    # pq words and cu_cap only steer HOW the device computes and are ignored; what would change WHAT is computed must be off.
+    def conv_fwd(self, x, w_hwio, w_fwd, bias, y, stride, w_split=None, amax_x=None, amax_w=None, tile_stats=None, w_split_layout=0,
+                 ln=None, x_s16=False, cu_cap=0):
+        assert w_split is None and tile_stats is None and ln is None and not x_s16
         y.copy_(O.conv2d_same(x, w_hwio, bias, stride))
 
-    def conv_dgrad(self, dy, w_hwio, dx, stride):
+    def conv_dgrad(self, dy, w_hwio, dx, stride, w_split=None, amax_dy=None, amax_w=None, w_split_layout=0, dy_s16=False):
+        assert w_split is None and not dy_s16
         x0 = torch.zeros_like(dx, requires_grad=True)
         y = O.conv2d_same(x0, w_hwio, torch.zeros(w_hwio.shape[3], dtype=dx.dtype), stride)
         (g,) = torch.autograd.grad(y, x0, dy)
         dx.copy_(g)
 
-    def conv_wgrad(self, x, dy, dw, stride):
+    def conv_wgrad(self, x, dy, dw, stride, amax_x=None, amax_dy=None, ln=None, x_s16=False, dy_s16=False):
+        assert ln is None and not x_s16 and not dy_s16
         w0 = torch.zeros_like(dw, requires_grad=True)
         y = O.conv2d_same(x, w0, torch.zeros(dw.shape[3], dtype=dw.dtype), stride)
         (g,) = torch.autograd.grad(y, w0, dy)
         dw.copy_(g)
 
-    def ln_elu_fwd(self, y, gamma, beta, a, stats, region=None):
+    def ln_elu_fwd(self, y, gamma, beta, a, stats, amax_out=None, tile_stats=None, region=None, out_s16=False):
+        assert tile_stats is None and not out_s16
         if region is not None:      # valid window of a canvas (sgg_hip.h): normalise the window, zeros elsewhere
             r0, c0, hv, wv = region
             a.zero_()
@@ -58,7 +75,9 @@ class RefKernels:
         stats[:, 0] = mean
         stats[:, 1] = torch.rsqrt(var + O.LN_EPS)
 
-    def ln_elu_bwd(self, y, da, gamma, beta, stats, dy, dgamma, dbeta, dbias_prev, region=None):
+    def ln_elu_bwd(self, y, da, gamma, beta, stats, dy, dgamma, dbeta, dbias_prev, amax_out=None, region=None, ws=None, out_s16=False,
+                   pq=None):
+        assert dgamma is not None and dbeta is not None and not out_s16      # (no deferred parameter gradients: no ln_bwd_finalize here)
         if region is not None:
             r0, c0, hv, wv = region
             dy.zero_()

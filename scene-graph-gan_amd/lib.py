@@ -156,10 +156,10 @@ DEFAULT_OPTIONS = {
     "halo_pc64": True,
     # LayerNorm + ELU applied by the consuming convolution's patch staging (LN prologue): 1 (default) = per layer and per KIND of
     # encoder pass (forward-only / followed by a backward) where the measured cost models (trunk.ln_fusion_pays, pc_ln_fusion_pays) say it pays
-    # (trunk._plan_ln_fusion: with pre-split activations 20 of the 44 apply passes of a step at configs[1] run as prologues, 24 as
+    # (trunk._plan: with pre-split activations 20 of the 44 apply passes of a step at configs[1] run as prologues, 24 as
     # standalone passes - DESIGN.md "The LN prologue"); 2 = wherever the kernels allow (slower: DESIGN.md); 0 = never
     "ln_fusion": 1,
-    # True: the LayerNorm kernels write their outputs pre-split for the convolutions that consume them (trunk._plan_s16; fp16 modes)
+    # True: the LayerNorm kernels write their outputs pre-split for the convolutions that consume them (trunk._plan; fp16 modes)
     "presplit": True,
     # True (with presplit): the gradient the attention head hands to the last convolution is converted to the pre-split format once
     # per backward (sgg_presplit16), so that `downsampled`'s dgrad and filter gradient stage it by DMA as well
@@ -192,6 +192,17 @@ DEFAULT_OPTIONS = {
     "ln_fusion_force_bwd": (),
     "ln_fusion_skip_bwd": (),
 }
+
+
+# What each option means for a kernel set that does not declare it - one without resident kernels, operand formats or streams, such as
+# the CPU reference kernels or a stub in a test: plain f32 convolutions, every LayerNorm a pass of its own, one stream.  The ONE set of
+# off-values of the host schedule (trunk.py, step.py read every option through `option`).
+OFF_OPTIONS = {key: () if isinstance(val, tuple) else type(val)(0) for key, val in DEFAULT_OPTIONS.items()}
+
+
+def option(K, name):
+    """Option `name` of the kernel set K: its attribute (HipKernels sets every one), else the off-value."""
+    return getattr(K, name, OFF_OPTIONS[name])
 
 
 def options_from_env(base=None):
@@ -350,7 +361,7 @@ class HipKernels:
         layout 4 (the four-block form of the producer / consumer kernel; option halo_pc64).  Such a launch must pass x_s16 / dy_s16."""
         if not self.conv_halo:
             return 0
-        if not (self.halo_pc and getattr(self, "halo_pc64", True)):
+        if not (self.halo_pc and self.halo_pc64):
             return self.conv_wsplit_layout(k, stride, H, W, cin, cout)
         return self.lib.sgg_conv_wsplit_layout_presplit(k, k, stride, H, W, cin, cout, self.conv_precision)
 
@@ -431,6 +442,20 @@ class HipKernels:
                                                          "true" if dma else "false",
                                                          8 if dma and n_out % 256 == 0 and -(-m_positions // 224) * (n_out // 256) > 128 else 4)
 
+    def conv_symbol(self, dgrad, layout, n_out, n_in, m_positions, split, stats=False, lnp=False, presplit=False):
+        """Kernel symbol of a forward (dgrad False) or dgrad launch with this w_split_layout; n_out / n_in: the channels the launch
+        produces / contracts over (dgrad: Cin / Cout of the layer); split: pre-split weights were passed; stats, lnp, presplit: the
+        launch emits tile statistics / applies the LN prologue / reads a pre-split source."""
+        if layout == 4:
+            return self.halo_pc_symbol(lnp, presplit, n_out)
+        if layout == 1:
+            return self.halo_symbol(n_out, n_in, lnp)
+        if layout == 3:         # conv1_3 through the space-to-depth view: four times the channels on its full-resolution side
+            return self.halo_symbol(4 * n_out, n_in, lnp) if dgrad else self.halo_symbol(n_out, 4 * n_in, lnp)
+        if layout == 2:
+            return self.s2_symbol(dgrad, m_positions, n_out, stats, lnp, presplit)
+        return self.gather_symbol(n_out, split)
+
     def conv_fwd(self, x, w_hwio, w_fwd, bias, y, stride, w_split=None, amax_x=None, amax_w=None, tile_stats=None, w_split_layout=0,
                  ln=None, x_s16=False, cu_cap=0):
         """y = conv2d_same(x, w) + bias. w_fwd: HWOI transpose of w_hwio (or w_hwio itself when Cin == 3).
@@ -444,11 +469,8 @@ class HipKernels:
         d = self._conv_dims(x.shape, w_hwio.shape, stride)
         assert tuple(y.shape) == (d[0], d[4], d[5], d[6]) and x.is_contiguous() and y.is_contiguous()
         flops = 2.0 * d[0] * d[4] * d[5] * d[6] * d[7] * d[8] * d[3]
-        sym = "conv_c3_fwd_kernel" if d[3] == 3 else (self.halo_pc_symbol(ln is not None, x_s16, d[6]) if w_split_layout == 4 else
-                                                             self.halo_symbol(d[6], d[3], ln is not None) if w_split_layout == 1 else
-                                                             self.halo_symbol(d[6], 4 * d[3], ln is not None) if w_split_layout == 3 else
-                                                             self.s2_symbol(False, d[0] * d[4] * d[5], d[6], tile_stats is not None, ln is not None, x_s16) if w_split_layout == 2 else
-                                                             self.gather_symbol(d[6], w_split is not None))
+        sym = "conv_c3_fwd_kernel" if d[3] == 3 else self.conv_symbol(False, w_split_layout, d[6], d[3], d[0] * d[4] * d[5], w_split is not None,
+                                                                      tile_stats is not None, ln is not None, x_s16)
         nb = 0.0
         if d[3] != 3:
             amax_x, amax_w = self._amax_or_compute(x, amax_x, 0), self._amax_or_compute(w_fwd, amax_w, 1)
@@ -466,9 +488,7 @@ class HipKernels:
         assert tuple(dy.shape) == (d[0], d[4], d[5], d[6]) and dy.is_contiguous() and dx.is_contiguous()
         flops = 2.0 * d[0] * d[4] * d[5] * d[6] * d[7] * d[8] * d[3]
         amax_dy, amax_w = self._amax_or_compute(dy, amax_dy, 0), self._amax_or_compute(w_hwio, amax_w, 1)
-        sym = self.halo_pc_symbol(False, dy_s16, d[3]) if w_split_layout == 4 else self.halo_symbol(d[3], d[6]) if w_split_layout == 1 else (self.halo_symbol(4 * d[3], d[6]) if w_split_layout == 3 else
-                                                                          self.s2_symbol(True, d[0] * d[4] * d[5], d[3], False, False, dy_s16) if w_split_layout == 2 else
-                                                                          self.gather_symbol(d[3], w_split is not None))
+        sym = self.conv_symbol(True, w_split_layout, d[3], d[6], d[0] * d[4] * d[5], w_split is not None, presplit=dy_s16)
         self._check(self._timed(sym, flops, lambda: self.lib.sgg_conv2d_nhwc_dgrad(
             _p(dy), _p(w_hwio), _p(w_split), _p(dx), *d, self.conv_precision, w_split_layout, _p(amax_dy), _p(amax_w),
             int(bool(dy_s16)), self._stream())), "sgg_conv2d_nhwc_dgrad")

@@ -21,6 +21,7 @@ import contextlib
 import torch
 
 from .head import Head
+from .lib import option
 from .params import ADAM_B1, ADAM_B2, ADAM_EPS, ADAM_LR, EMBED_DIM, FEAT_C, NUM_UNITS, T_STEPS, ParamArena
 from .trunk import Trunk
 
@@ -113,7 +114,7 @@ class GanStep:
         # default because concurrent kernels make per-kernel durations (the roofline measurement) meaningless.
         self._g_reuse, self._g_reuse_armed = None, False       # (images, ctx) of G's encoder within one train_iteration
         # (option side_priority: priority of the side streams - everything on them is off the critical chain of the main stream)
-        prio = int(getattr(K, "side_priority", 0))
+        prio = int(option(K, "side_priority"))
         self.side = torch.cuda.Stream(device=dev, priority=prio) if (overlap_streams and dev.type == "cuda") else None
         if self.side is not None:
             # backward: filter gradients beside the dgrad -> LayerNorm-backward chain (trunk.enable_wgrad_overlap)
@@ -141,7 +142,7 @@ class GanStep:
         43.17 / 43.15 against 43.60 / 43.73 ms per step (profiles/r04_g_early_ab.log)."""
         ev, ev_images = getattr(self, "_ev_g_free", None), getattr(self, "_ev_g_images", None)
         self._ev_g_free = self._ev_g_images = None
-        if self.side is None or ev is None or not getattr(self.K, "g_early", 0) or self.G.pending is not None or self._g_reuse is not None:
+        if self.side is None or ev is None or not option(self.K, "g_early") or self.G.pending is not None or self._g_reuse is not None:
             return None
         # only for the minibatch tensor the critic update ran on, unmodified (train.py:175-190 repeats each batch for every update of an
         # iteration): the early stream waits for nothing the main stream enqueued after that update's G head, so a tensor produced there
@@ -150,8 +151,8 @@ class GanStep:
             return None
         # ... and only for the parameters that critic update left: a state-dict load or an optimiser step through another batch size's
         # Network on the shared arena since then would make trunk.forward re-derive the weight formats (refresh_weights) on the early
-        # stream, unordered against the main stream's writes
-        if ev_images[2] != (self.G.arena.version, self.G.adam_t):
+        # stream, unordered against the main stream's writes - as would an option of K changed since the encoder made its plan
+        if ev_images[2] != (self.G.arena.version, self.G.adam_t) or not self.G.trunk.plan_current():
             return None
         # ... and only if no input-gradient pass (sgg_amd/grad.py) has used G's encoder buffers on the main stream since then
         if ev_images[3] != self.G.data_passes:
@@ -180,43 +181,38 @@ class GanStep:
         else:
             keep = for_backward or self._g_reuse_armed
             if early is not None:        # (the caller made `early` wait for everything this forward depends on)
-                cap = int(getattr(self.K, "g_early_cus", 0))
-                kw = {"cu_cap": cap} if cap else {}
-                with torch.cuda.stream(early):
-                    ctx = G.trunk.forward(images, keep, **kw) if keep is False else G.trunk.forward(images, **kw)
-                    G.head.precompute(ctx)
+                ctx = self._encode(G, images, keep, early, int(option(self.K, "g_early_cus")))
                 torch.cuda.current_stream().wait_stream(early)
             else:
-                ctx = G.trunk.forward(images, keep) if keep is False else G.trunk.forward(images)
-                G.head.precompute(ctx)
+                ctx = self._encode(G, images, keep)
             if self._g_reuse_armed:
                 self._g_reuse = (images, ctx, (images.data_ptr(), images._version, G.adam_t))
         st = G.head.state(1, self.B)
         G.head.forward(st, ctx, noise)
         return st, ctx
 
+    @staticmethod
+    def _encode(net, images, for_backward, stream=None, cu_cap=0):
+        """Run this network's encoder: trunk forward (for_backward, cu_cap: Trunk.forward) and the step-invariant attention product of
+        its head, on `stream` when one is given (the caller orders it); returns ctx."""
+        kw = {"cu_cap": cu_cap} if cu_cap else {}
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ctx = net.trunk.forward(images, for_backward, **kw)
+            net.head.precompute(ctx)
+        return ctx
+
     def _d_encoder_on_side_stream(self, images, zero_grads, for_backward=True):
         """D.finish_update (pending all-reduce + Adam), D's encoder forward and the step-invariant attention product,
-        enqueued on the side stream; returns ctx. Call _join_side() before anything on the main stream reads them."""
-        D = self.D
-        if self.side is None:
+        enqueued on the side stream (where there is one); returns ctx. Call _join_side() before anything on the main stream reads them."""
+        D, cap = self.D, 0
+        if self.side is not None:
+            self.side.wait_stream(torch.cuda.current_stream())
+            cap = int(option(self.K, "d_side_cus"))                 # (option d_side_cus: as g_early_cus, for D's forward beside G's forward and head)
+        with torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
             D.finish_update()
             if zero_grads:
                 D.zero_grads()
-            ctx = D.trunk.forward(images, for_backward) if for_backward is False else D.trunk.forward(images)
-            D.head.precompute(ctx)
-            return ctx
-        main = torch.cuda.current_stream()
-        self.side.wait_stream(main)
-        cap = int(getattr(self.K, "d_side_cus", 0))      # (option d_side_cus: as g_early_cus, for D's forward beside G's forward and head)
-        kw = {"cu_cap": cap} if cap else {}
-        with torch.cuda.stream(self.side):
-            D.finish_update()
-            if zero_grads:
-                D.zero_grads()
-            ctx = D.trunk.forward(images, for_backward, **kw) if for_backward is False else D.trunk.forward(images, **kw)
-            D.head.precompute(ctx)
-        return ctx
+            return self._encode(D, images, for_backward, cu_cap=cap)
 
     def _join_side(self):
         if self.side is not None:
@@ -240,7 +236,7 @@ class GanStep:
             self.G.finish_update()
             gst, _ = self.generator_forward(images, noise, for_backward=False)
             ctx = self._d_encoder_on_side_stream(images, zero_grads=True)
-        if self.side is not None and getattr(K, "g_early", 0):
+        if self.side is not None and option(K, "g_early"):
             # G's encoder buffers are free from here on, and this critic update does not touch G's weights (_g_early_stream)
             self._ev_g_free = torch.cuda.Event()
             self._ev_g_free.record()
@@ -290,8 +286,7 @@ class GanStep:
             out = self.val_losses
         fake_rows, real_rows, hat_rows = self.TRI[:B], self.TRI[B:2 * B], self.TRI[2 * B:]
         self.flush()
-        ctx = D.trunk.forward(images, False)
-        D.head.precompute(ctx)
+        ctx = self._encode(D, images, False)
         gst, _ = self.generator_forward(images, noise, for_backward=False)
         fake_rows.copy_(gst.OUT[0])
         K.onehot(labels, real_rows)

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import torch
 
+from .lib import option
 from .params import CONV_SPECS, FEAT_C, conv_name, ln_name, same_pads
 
 
@@ -81,6 +82,13 @@ def pc_ln_fusion_pays(out_shape, cin_next, cout_next):
     return 0.35 * mb > flops * (1.0 / 340e12 - 1.0 / 425e12) * 1e6
 
 
+def _on(**operands):
+    """The optional operands of a kernel call that are switched on (not None / False / 0), as keywords.  Every op has one call site
+    for every kernel set: a set with narrower signatures (the CPU reference kernels) serves as long as nothing it lacks is asked of
+    it, and being asked for it is an error (TypeError), never a silent fall-back."""
+    return {name: v for name, v in operands.items() if not (v is None or v is False or (type(v) is int and v == 0))}
+
+
 class Trunk:
     def __init__(self, K, arena, grad_views, B, S):
         self.K, self.B, self.S = K, B, S
@@ -88,7 +96,7 @@ class Trunk:
         dev, dt = arena.flat.device, arena.flat.dtype
         p, g = arena.views, grad_views
         self.layers = []
-        plan = plan_canvas(S) if getattr(K, "canvas", True) else None
+        plan = plan_canvas(S)
         S_in = plan[0][0] if plan else S
         # the image inside its zero canvas (odd sizes): filled by forward(), zero elsewhere for good
         self.img_canvas = torch.zeros((B, S_in, S_in, 3), device=dev, dtype=dt) if plan else None
@@ -117,28 +125,27 @@ class Trunk:
                 "y": torch.empty((B, ho, wo, cout), device=dev, dtype=dt),
             }
             lay["w_fwd"] = lay["w"] if cin == 3 else torch.empty((k, k, cout, cin), device=dev, dtype=dt)
-            # split modes: both weight layouts pre-split into 16-bit planes once per optimiser step (HIP backend only)
-            lay["ws_fwd"] = lay["ws_bwd"] = None
-            # 3x3 stride-1 layers on 8-divisible grids: halo-resident kernel, weights pre-arranged as MFMA fragments
-            # (re-derived in refresh_weights: the layout depends on the conv precision in force)
             lay["hin"], lay["win"] = h, w
             lay["prev"] = self.layers[-1] if self.layers else None
-            # forward and dgrad are asked separately: the kernels' channel conditions are not symmetric in (cin, cout)
-            lay["ws_layout"] = lay["ws_layout_bwd"] = 0
-            self._query_layouts(lay)
-            if cin != 3 and getattr(K, "conv_precision", 0) and hasattr(K, "split_weights"):
+            # split modes: both weight layouts pre-split into 16-bit planes once per optimiser step (kernel sets that convert weights)
+            lay["ws_fwd"] = lay["ws_bwd"] = None
+            if cin != 3 and option(K, "conv_precision") and hasattr(K, "prepare_weights"):
                 lay["ws_fwd"] = torch.empty((3, lay["w"].numel()), device=dev, dtype=torch.int16)
                 lay["ws_bwd"] = torch.empty((3, lay["w"].numel()), device=dev, dtype=torch.int16)
-            if 3 in (lay["ws_layout"], lay["ws_layout_bwd"]):
-                # conv1_3 as a 3x3 convolution over the space-to-depth view of its input: the 9-tap kernel and its HWOI transpose
-                lay["w3"] = torch.empty((3, 3, 4 * cin, cout), device=dev, dtype=dt)
-                lay["w3_fwd"] = torch.empty((3, 3, cout, 4 * cin), device=dev, dtype=dt)
+            # 3x3 stride-1 layers on 8-divisible grids: halo-resident kernel, weights pre-arranged as MFMA fragments.  Forward and
+            # dgrad are asked separately: the kernels' channel conditions are not symmetric in (cin, cout).  (_plan asks again: the
+            # layout depends on the conv precision in force; here it sizes the tile-statistics buffer.)
+            lay["ws_layout"] = lay["ws_layout_bwd"] = 0
+            self._query_layouts(lay)
             lay["tstats"] = None
             if has_ln and hasattr(K, "conv_tile_stats_count") and region is None:
                 nts = K.conv_tile_stats_count((B, ho, wo, cout), cin, k, s, lay["ws_layout"])
                 if nts > 0:     # the conv epilogue emits the LayerNorm partial statistics for this shape
                     lay["tstats"] = torch.zeros((B, nts, 4), device=dev, dtype=dt)
-                    lay["tstats_mode"] = (K.conv_precision, lay["ws_layout"])
+                    lay["tstats_mode"] = (option(K, "conv_precision"), lay["ws_layout"])
+            # what the last forward() did with this layer's LayerNorm: left to the consumer's prologue / written pre-split
+            lay["fused_now"] = lay["a_s16_now"] = False
+            lay["ln_ws"] = None
             if has_ln:
                 lay["gamma"], lay["beta"] = p[ln_name(i) + "/gamma"], p[ln_name(i) + "/beta"]
                 lay["ggamma"], lay["gbeta"] = g[ln_name(i) + "/gamma"], g[ln_name(i) + "/beta"]
@@ -167,6 +174,7 @@ class Trunk:
                     todo.append({"ws": lay["ln_ws"], "gamma": lay["gamma"], "stats": lay["stats"], "dgamma": lay["ggamma"], "dbeta": lay["gbeta"],
                                  "dbias": lay["gb"], "shape": lay["out_shape"], "region": lay["region"]})
             self._ln_fin = K.ln_finalize_descs(todo)
+        self._plan_key = None
         self.refresh_weights()
 
     def _query_layouts(self, lay):
@@ -180,7 +188,6 @@ class Trunk:
                 # MFMA wave per SIMD).  A layer whose forward mostly runs with the prologue keeps the four-wave kernel's fragments for
                 # the forward; its dgrad (never a prologue) still takes layout 4 below.  
                 lay["ws_layout"] = 1
-            ho, wo = lay["out_shape"][1], lay["out_shape"][2]
             # (both directions are asked with the full-resolution grid: forward input = dgrad output)
             lay["ws_layout_bwd"] = K.conv_wsplit_layout(k, s, lay["hin"], lay["win"], lay["cout"], lay["cin"])
             if lay["ws_layout_bwd"] == 1 and self._dy_presplit_static(lay) and hasattr(K, "conv_wsplit_layout_presplit"):
@@ -189,24 +196,23 @@ class Trunk:
                 lay["ws_layout_bwd"] = K.conv_wsplit_layout_presplit(k, s, lay["hin"], lay["win"], lay["cout"], lay["cin"])
 
     def _dy_presplit_static(self, lay):
-        """Will _plan_s16 / backward() hand this layer's dgrad a PRE-SPLIT dy in every backward?  (The static conditions of
-        lay["dy_s16"] and of backward()'s nxt_s16: LayerNorm layer, fp16 two-piece mode with pre-split weights, the deferred LayerNorm
-        finalize, a resident filter gradient.)"""
+        """Will _plan hand this layer's dgrad a PRE-SPLIT dy in every backward?  (The static conditions of lay["dy_s16"]: LayerNorm
+        layer, fp16 two-piece mode with pre-split weights, the deferred LayerNorm finalize, a resident filter gradient.)"""
         K = self.K
-        if not (lay["has_ln"] and lay["cin"] != 3 and bool(getattr(K, "presplit", False)) and getattr(K, "conv_precision", 0) == 2
-                and hasattr(K, "wgrad_resident") and hasattr(K, "ln_bwd_finalize") and hasattr(K, "split_weights")):
+        if not (lay["has_ln"] and lay["cin"] != 3 and option(K, "presplit") and option(K, "conv_precision") == 2
+                and hasattr(K, "wgrad_resident") and hasattr(K, "ln_bwd_finalize") and hasattr(K, "prepare_weights")):
             return False
         Bn, ho, wo, cout = lay["out_shape"]
         return bool(K.wgrad_resident(Bn, ho, wo, lay["cin"], lay["cout"], lay["k"], lay["s"]))
 
     def _ln_prologue_expected(self, lay):
-        """Will _plan_ln_fusion let this layer's forward apply the previous layer's LayerNorm + ELU in its patch staging, in either
-        kind of pass?  (The static part of that plan: the statistics conditions it adds can only remove a fusion.)"""
+        """Will _plan let this layer's forward apply the previous layer's LayerNorm + ELU in its patch staging, in either kind of
+        pass?  (The static part of that plan: the statistics conditions it adds can only remove a fusion.)"""
         K, prev = self.K, lay.get("prev")
-        mode = getattr(K, "ln_fusion", 0)
+        mode = option(K, "ln_fusion")
         if not mode or prev is None or not prev["has_ln"] or prev["region"] or not hasattr(K, "ln_prologue_ok"):
             return False
-        if prev["i"] in getattr(K, "ln_fusion_skip", ()):
+        if prev["i"] in option(K, "ln_fusion_skip"):
             return False
         if mode == 1 and self._pc_presplit(lay):
             return False
@@ -220,33 +226,75 @@ class Trunk:
         matrix peak against 0.43): those LayerNorms keep their apply pass - in passes with a backward always; in forward-only passes
         except where pc_ln_fusion_pays says the saved pass is worth the slower variant (round 5: LN4, LN5)."""
         K = self.K
-        return (bool(getattr(K, "presplit", False)) and getattr(K, "conv_precision", 0) == 2 and hasattr(K, "conv_wsplit_layout") and
+        return (bool(option(K, "presplit")) and option(K, "conv_precision") == 2 and hasattr(K, "conv_wsplit_layout") and
                 K.conv_wsplit_layout(lay["k"], lay["s"], lay["hin"], lay["win"], lay["cin"], lay["cout"]) == 4)
 
     def _f16(self):
-        return getattr(self.K, "conv_precision", 0) in (1, 2)      # fp16 pieces: per-tensor scaling from the amax words
+        return option(self.K, "conv_precision") in (1, 2)      # fp16 pieces: per-tensor scaling from the amax words
 
     def _am(self, row, j):
         return self.amax[row, j:j + 1] if self._f16() else None
 
-    def _plan_ln_fusion(self):
-        """lay["fuse_ln"] / lay["fuse_ln_bwd"]: this layer's LayerNorm + ELU is applied by its consumer (the next convolution's patch
-        staging) instead of a pass of its own, in encoder passes that no backward follows / that a backward follows (then the
-        activation a_j is never written and the consumer's wgrad applies the prologue as well).  Needs the statistics partials from
-        this layer's conv epilogue and a consumer on the halo-resident kernels in the conv precision in force.
+    # the options of K that _plan reads (lib.DEFAULT_OPTIONS; oracle/kernels_ref.py: RefKernels declares their off-values)
+    PLAN_OPTIONS = ("conv_precision", "conv_halo", "halo_pc", "halo_pc64", "presplit", "presplit_head_grad", "ln_fusion",
+                    "ln_fusion_skip", "ln_fusion_force", "ln_fusion_force_bwd", "ln_fusion_skip_bwd")
 
-        K.ln_fusion: 0 off; 2 wherever the kernels allow (slower: DESIGN.md); 1 (default) where the measured cost model
-        (ln_fusion_pays) says it pays, per kind of pass."""
+    def _key(self):
+        """What the plan in force must have been made for: the parameters' version and every option _plan reads."""
         K = self.K
-        mode = getattr(K, "ln_fusion", 0)
+        return (self.arena.version,) + tuple(option(K, name) for name in self.PLAN_OPTIONS)
+
+    def plan_current(self):
+        """False: the next forward() / backward() will re-derive the operand formats first (refresh_weights, on ITS stream)."""
+        return self._plan_key == self._key()
+
+    def _alloc_w3(self, lay):
+        """conv1_3 as a 3x3 convolution over the space-to-depth view of its input (layout 3): the 9-tap kernel and its HWOI
+        transpose, allocated the first time either direction asks for that layout."""
+        if 3 in (lay["ws_layout"], lay["ws_layout_bwd"]) and "w3" not in lay:
+            cin, cout, w = lay["cin"], lay["cout"], lay["w"]
+            lay["w3"] = torch.empty((3, 3, 4 * cin, cout), device=w.device, dtype=w.dtype)
+            lay["w3_fwd"] = torch.empty((3, 3, cout, 4 * cin), device=w.device, dtype=w.dtype)
+
+    def _plan(self):
+        """Everything forward() and backward() decide per layer, resolved for the options of K in force (PLAN_OPTIONS):
+
+        lay["ws_layout"] / ["ws_layout_bwd"]   fragment layout of the pre-split weights per direction (_query_layouts)
+        lay["use_ws_fwd"] / ["use_ws_bwd"]     the pre-split weights (lay["ws_fwd"] / ["ws_bwd"]) where refresh_weights converts them
+                                               in the precision in force, else None: f32 weights, layout 0
+        lay["use_tstats"]                      the tile-statistics buffer where the forward's epilogue fills it in this precision and
+                                               layout (it was sized for those of the construction), else None
+        lay["fuse_ln"] / ["fuse_ln_bwd"], lay["a_s16"] / ["dy_s16"]: below.
+        self._wdesc: the weight table of refresh_weights (None: a kernel set that converts no weights)."""
+        K = self.K
+        n = len(self.layers)
+        todo = []
+        for j, lay in enumerate(self.layers):
+            self._query_layouts(lay)
+            self._alloc_w3(lay)
+            split = lay["ws_fwd"] is not None and bool(option(K, "conv_precision"))
+            lay["use_ws_fwd"], lay["use_ws_bwd"] = (lay["ws_fwd"], lay["ws_bwd"]) if split else (None, None)
+            stats = lay["tstats"] is not None and (lay["cin"] == 3 or (split and lay["tstats_mode"] == (option(K, "conv_precision"), lay["ws_layout"])))
+            lay["use_tstats"] = lay["tstats"] if stats else None
+            if lay["cin"] != 3:
+                todo.append({"w": lay["w"], "w_fwd": lay["w_fwd"], "w3": lay.get("w3"), "w3_fwd": lay.get("w3_fwd"),
+                             "ws_fwd": lay["use_ws_fwd"], "ws_bwd": lay["use_ws_bwd"], "amax": self._am(2, j),
+                             "ws_layout": lay["ws_layout"] if split else 0, "ws_layout_bwd": lay["ws_layout_bwd"] if split else 0})
+        self._wdesc = K.weight_descs(todo) if hasattr(K, "prepare_weights") else None
+
+        # lay["fuse_ln"] / lay["fuse_ln_bwd"]: this layer's LayerNorm + ELU is applied by its consumer (the next convolution's patch
+        # staging) instead of a pass of its own, in encoder passes that no backward follows / that a backward follows (then the
+        # activation a_j is never written and the consumer's wgrad applies the prologue as well).  Needs the statistics partials from
+        # this layer's conv epilogue and a consumer on the halo-resident kernels in the conv precision in force.
+        # K.ln_fusion: 0 off; 2 wherever the kernels allow (slower: DESIGN.md); 1 (default) where the measured cost model
+        # (ln_fusion_pays) says it pays, per kind of pass.
+        mode = option(K, "ln_fusion")
         for j, lay in enumerate(self.layers):
             lay["fuse_ln"] = lay["fuse_ln_bwd"] = False
-            if not (lay["has_ln"] and hasattr(K, "ln_prologue_ok") and mode) or j + 1 >= len(self.layers) or lay["region"]:
+            if not (lay["has_ln"] and hasattr(K, "ln_prologue_ok") and mode) or j + 1 >= n or lay["region"]:
                 continue
             nxt = self.layers[j + 1]
-            stats_ok = lay["tstats"] is not None and (lay["cin"] == 3 or (lay["ws_fwd"] is not None and lay.get("ws_mode") == K.conv_precision
-                                                                          and lay.get("tstats_mode") == (K.conv_precision, lay["ws_layout"])))
-            if not (stats_ok and nxt["ws_fwd"] is not None):
+            if lay["use_tstats"] is None or nxt["use_ws_fwd"] is None:
                 continue
             args = (nxt["k"], nxt["s"], nxt["hin"], nxt["win"], nxt["cin"], nxt["cout"])
             both_ok = bool(K.ln_prologue_ok(*args))
@@ -259,94 +307,57 @@ class Trunk:
                 # consumer on the producer / consumer kernel: with a backward never (its filter gradient wants the pre-split a_j);
                 # forward-only where the apply pass it saves outweighs the consumer's slower prologue variant (pc_ln_fusion_pays)
                 pays_fwd, pays_bwd = pc_ln_fusion_pays(lay["out_shape"], nxt["cin"], nxt["cout"]), False
-            if lay["i"] in getattr(K, "ln_fusion_skip", ()):      # (A/B option ln_fusion_skip of sgg_amd/lib.py)
+            if lay["i"] in option(K, "ln_fusion_skip"):          # (A/B option ln_fusion_skip of sgg_amd/lib.py)
                 pays_fwd = pays_bwd = False
-            if lay["i"] in getattr(K, "ln_fusion_force", ()):     # (A/B option ln_fusion_force)
+            if lay["i"] in option(K, "ln_fusion_force"):         # (A/B option ln_fusion_force)
                 pays_fwd = True
-            if lay["i"] in getattr(K, "ln_fusion_force_bwd", ()):
+            if lay["i"] in option(K, "ln_fusion_force_bwd"):
                 pays_bwd = True
-            if lay["i"] in getattr(K, "ln_fusion_skip_bwd", ()):  # (A/B option: keep the apply pass in passes a backward follows)
+            if lay["i"] in option(K, "ln_fusion_skip_bwd"):      # (A/B option: keep the apply pass in passes a backward follows)
                 pays_bwd = False
             lay["fuse_ln"] = fwd_ok and pays_fwd
             lay["fuse_ln_bwd"] = both_ok and pays_bwd
 
-    def _plan_s16(self):
-        """lay["a_s16"] / lay["dy_s16"]: this layer's activation a_j = ELU(LN(y_j)) / the gradient dy_j its LayerNorm backward produces
-        is written PRE-SPLIT (two fp16 pieces per value in the f32 tensor's bytes: csrc/split16.h) by the LayerNorm kernel, so that the
-        convolutions that consume it stage it without splitting it again.  Needs the fp16 modes (per-tensor scale) and every consumer on
-        a resident kernel: a_j feeds conv_{j+1}'s forward and filter gradient, dy_j feeds conv_j's dgrad and filter gradient."""
-        K = self.K
-        on = bool(getattr(K, "presplit", False)) and getattr(K, "conv_precision", 0) in (1, 2) and hasattr(K, "wgrad_resident")
-        n = len(self.layers)
+        # lay["a_s16"] / lay["dy_s16"]: this layer's activation a_j = ELU(LN(y_j)) / the gradient dy_j its LayerNorm backward produces
+        # is written PRE-SPLIT (two fp16 pieces per value in the f32 tensor's bytes: csrc/split16.h) by the LayerNorm kernel, so that the
+        # convolutions that consume it stage it without splitting it again.  Needs the fp16 modes (per-tensor scale) and every consumer on
+        # a resident kernel: a_j feeds conv_{j+1}'s forward and filter gradient, dy_j feeds conv_j's dgrad and filter gradient (and is
+        # written so only by the LayerNorm backward with the deferred finalize).
+        on = bool(option(K, "presplit")) and self._f16() and hasattr(K, "wgrad_resident")
+        resident = (1, 2, 3, 4)
+        wg_ok = lambda l: K.wgrad_resident(l["out_shape"][0], l["out_shape"][1], l["out_shape"][2], l["cin"], l["cout"], l["k"], l["s"])
         for j, lay in enumerate(self.layers):
             lay["a_s16"] = lay["dy_s16"] = False
             if not on:
                 continue
+            dy_ok = lay["use_ws_bwd"] is not None and lay["ws_layout_bwd"] in resident and bool(wg_ok(lay))
             if not lay["has_ln"]:
                 # the last convolution: its dy is the head's f32 gradient, converted once per backward (sgg_presplit16) where both of
                 # its consumers take pre-split operands and its input activation arrives pre-split as well
-                wg = K.wgrad_resident(lay["out_shape"][0], lay["out_shape"][1], lay["out_shape"][2], lay["cin"], lay["cout"], lay["k"], lay["s"])
-                lay["dy_s16"] = (j == n - 1 and j > 0 and hasattr(K, "presplit16") and bool(getattr(K, "presplit_head_grad", True)) and
-                                 lay["ws_bwd"] is not None and
-                                 lay["ws_layout_bwd"] in (1, 2, 3, 4) and wg and lay["cout"] % 32 == 0)
+                lay["dy_s16"] = (j == n - 1 and j > 0 and hasattr(K, "presplit16") and bool(option(K, "presplit_head_grad")) and dy_ok
+                                 and lay["cout"] % 32 == 0)
                 continue
-            B, ho, wo, cout = lay["out_shape"]
-            wg_ok = lambda l: K.wgrad_resident(B, l["out_shape"][1], l["out_shape"][2], l["cin"], l["cout"], l["k"], l["s"])
             if j + 1 < n:
                 nxt = self.layers[j + 1]
-                lay["a_s16"] = nxt["ws_fwd"] is not None and nxt["ws_layout"] in (1, 2, 3, 4) and wg_ok(nxt)
-            lay["dy_s16"] = lay["cin"] != 3 and lay["ws_bwd"] is not None and lay["ws_layout_bwd"] in (1, 2, 3, 4) and wg_ok(lay)
+                lay["a_s16"] = nxt["use_ws_fwd"] is not None and nxt["ws_layout"] in resident and bool(wg_ok(nxt))
+            lay["dy_s16"] = lay["cin"] != 3 and dy_ok and self._ln_fin is not None
 
     def refresh_weights(self):
         """Re-derive the operand formats of the convolution kernels after the parameters changed (Adam step / state-dict load):
-        HWOI transposes, max|w| words, the space-to-depth kernel of conv1_3, both pre-split 16-bit copies.  One multi-tensor call
-        (three launches for the whole encoder) where the kernel set has it; per layer otherwise (the CPU reference kernels)."""
+        HWOI transposes, max|w| words, the space-to-depth kernel of conv1_3, both pre-split 16-bit copies - one multi-tensor call
+        (three launches for the whole encoder); the CPU reference kernels take the HWOI transposes only.  Re-plans first when an
+        option the plan reads has changed (layouts and formats depend on the precision in force)."""
         K = self.K
-        self._wver = getattr(self.arena, "version", 0)
-        if hasattr(K, "prepare_weights"):
-            key = (K.conv_precision, getattr(K, "conv_halo", True), bool(getattr(K, "presplit", False)), bool(getattr(K, "halo_pc64", True)))
-            if getattr(self, "_wdesc_key", None) != key:       # layouts depend on the precision in force: rebuild the table
-                todo = []
-                for j, lay in enumerate(self.layers):
-                    if lay["cin"] == 3:
-                        continue
-                    self._query_layouts(lay)
-                    if 3 in (lay["ws_layout"], lay["ws_layout_bwd"]) and "w3" not in lay:
-                        lay["w3"] = torch.empty((3, 3, 4 * lay["cin"], lay["cout"]), device=lay["w"].device, dtype=lay["w"].dtype)
-                        lay["w3_fwd"] = torch.empty((3, 3, lay["cout"], 4 * lay["cin"]), device=lay["w"].device, dtype=lay["w"].dtype)
-                    split = lay["ws_fwd"] is not None and K.conv_precision
-                    todo.append({"w": lay["w"], "w_fwd": lay["w_fwd"], "w3": lay.get("w3"), "w3_fwd": lay.get("w3_fwd"),
-                                 "ws_fwd": lay["ws_fwd"] if split else None, "ws_bwd": lay["ws_bwd"] if split else None,
-                                 "amax": self._am(2, j), "ws_layout": lay["ws_layout"] if split else 0,
-                                 "ws_layout_bwd": lay["ws_layout_bwd"] if split else 0})
-                self._wdesc, self._wdesc_key = K.weight_descs(todo), key
+        key = self._key()
+        if self._plan_key is None or key[1:] != self._plan_key[1:]:
+            self._plan()
+        self._plan_key = key
+        if self._wdesc is not None:
             K.prepare_weights(self._wdesc)
-            for lay in self.layers:
-                if lay["cin"] != 3 and lay["ws_fwd"] is not None and K.conv_precision:
-                    lay["ws_mode"] = K.conv_precision
-            self._plan_ln_fusion()
-            self._plan_s16()
             return
-        if self._f16():
-            self.K.fill(self.amax[2], 0.0)
-        for j, lay in enumerate(self.layers):
+        for lay in self.layers:
             if lay["cin"] != 3:
-                self.K.hwio_to_hwoi(lay["w"], lay["w_fwd"])
-                if self._f16():
-                    self.K.absmax(lay["w"], self._am(2, j))
-                if lay["ws_fwd"] is not None and self.K.conv_precision:
-                    self._query_layouts(lay)
-                    if 3 in (lay["ws_layout"], lay["ws_layout_bwd"]):
-                        if "w3" not in lay:
-                            lay["w3"] = torch.empty((3, 3, 4 * lay["cin"], lay["cout"]), device=lay["w"].device, dtype=lay["w"].dtype)
-                            lay["w3_fwd"] = torch.empty((3, 3, lay["cout"], 4 * lay["cin"]), device=lay["w"].device, dtype=lay["w"].dtype)
-                        self.K.s2d_weights(lay["w"], lay["w3"])
-                        self.K.hwio_to_hwoi(lay["w3"], lay["w3_fwd"])
-                    self.K.split_weights(lay["w3_fwd"] if lay["ws_layout"] == 3 else lay["w_fwd"], lay["ws_fwd"], self._am(2, j), lay["ws_layout"])
-                    self.K.split_weights(lay["w3"] if lay["ws_layout_bwd"] == 3 else lay["w"], lay["ws_bwd"], self._am(2, j), lay["ws_layout_bwd"])
-                    lay["ws_mode"] = self.K.conv_precision
-        self._plan_ln_fusion()
-        self._plan_s16()
+                K.hwio_to_hwoi(lay["w"], lay["w_fwd"])
 
     def forward(self, images, for_backward=True, cu_cap=0):
         """images [B,S,S,3] NHWC fp32, already standardised (train.py:172) -> downsampled as ctx [B, L, 512].
@@ -354,12 +365,12 @@ class Trunk:
         layer may be applied by the consuming convolution's patch staging instead of a pass of its own (K.ln_fusion = 1).
         cu_cap (1 .. 31): launch hint - the persistent convolution kernels of this pass occupy at most that many of an XCD's 32 CUs
         (a forward that runs beside another stream's latency-critical chain: step.GanStep, option g_early_cus)."""
-        cu_cap = cu_cap or int(getattr(self.K, "fwd_cus", 0))      # (option fwd_cus: the same hint for every encoder forward)
-        cap = {"cu_cap": int(cu_cap)} if cu_cap else {}
         assert tuple(images.shape) == (self.B, self.S, self.S, 3), images.shape
         K = self.K
-        if self._wver != getattr(self.arena, "version", 0):
-            self.refresh_weights()          # the parameters changed through another encoder on this arena (another batch size)
+        if not self.plan_current():
+            # the parameters changed through another encoder on this arena (another batch size), or an option of K was changed
+            self.refresh_weights()
+        cu_cap = int(cu_cap or option(K, "fwd_cus"))           # (option fwd_cus: the same hint for every encoder forward)
         fuse_key = "fuse_ln_bwd" if for_backward else "fuse_ln"
         self._fwd_for_backward = for_backward
         if self.img_canvas is not None:
@@ -373,25 +384,15 @@ class Trunk:
         if self._f16():
             K.fill(self.amax[0], 0.0)
         for j, lay in enumerate(self.layers):
-            ws = lay["ws_fwd"] if (lay["ws_fwd"] is not None and lay.get("ws_mode") == getattr(K, "conv_precision", 0)) else None
-            ts = lay["tstats"] if (lay["tstats"] is not None and (ws is not None or lay["cin"] == 3)
-                                   and (lay["cin"] == 3 or lay.get("tstats_mode") == (K.conv_precision, lay["ws_layout"]))) else None
-            if ln_in is not None:
-                K.conv_fwd(x, lay["w"], lay["w_fwd"], lay["b"], lay["y"], lay["s"], ws, self._am(0, j - 1), self._am(2, j), ts,
-                           lay["ws_layout"], ln=ln_in, **cap)
-            elif x_s16:
-                assert ws is not None
-                K.conv_fwd(x, lay["w"], lay["w_fwd"], lay["b"], lay["y"], lay["s"], ws, self._am(0, j - 1), self._am(2, j), ts, lay["ws_layout"],
-                           x_s16=True, **cap)
-            elif ws is not None or self._f16() or ts is not None:
-                K.conv_fwd(x, lay["w"], lay["w_fwd"], lay["b"], lay["y"], lay["s"], ws, self._am(0, j - 1) if j else None, self._am(2, j), ts,
-                           lay["ws_layout"] if ws is not None else 0, **cap)
-            else:
-                K.conv_fwd(x, lay["w"], lay["w_fwd"], lay["b"], lay["y"], lay["s"])
+            ws, ts = lay["use_ws_fwd"], lay["use_tstats"]
+            assert ws is not None or not (x_s16 or ln_in is not None), "pre-split or LN-prologue operands need pre-split weights"
+            K.conv_fwd(x, lay["w"], lay["w_fwd"], lay["b"], lay["y"], lay["s"],
+                       **_on(w_split=ws, amax_x=self._am(0, j - 1) if j else None, amax_w=self._am(2, j), tile_stats=ts,
+                             w_split_layout=lay["ws_layout"] if ws is not None else 0, ln=ln_in, x_s16=x_s16, cu_cap=cu_cap))
             ln_in = None
             x_s16 = False
             if lay["has_ln"]:
-                if lay.get(fuse_key) and ts is not None:
+                if lay[fuse_key]:
                     # statistics only; the consumer normalises y while it stages its patches (forward and wgrad)
                     K.ln_finalize(ts, lay["gamma"], lay["beta"], lay["stats"], self._am(0, j), lay["out_shape"][1] * lay["out_shape"][2])
                     ln_in = (lay["stats"], lay["gamma"], lay["beta"])
@@ -399,20 +400,10 @@ class Trunk:
                     lay["fused_now"] = True
                     continue
                 lay["fused_now"] = False
-                # (the consumer must exist in the precision in force: its pre-split weights are what x_s16 above asserts)
-                s16 = bool(lay.get("a_s16")) and j + 1 < len(self.layers) and self.layers[j + 1].get("ws_mode") == getattr(K, "conv_precision", 0)
-                lay["a_s16_now"] = s16
-                if s16:
-                    K.ln_elu_fwd(lay["y"], lay["gamma"], lay["beta"], lay["a"], lay["stats"], self._am(0, j), ts, region=lay["region"], out_s16=True)
-                elif lay["region"] is not None:
-                    K.ln_elu_fwd(lay["y"], lay["gamma"], lay["beta"], lay["a"], lay["stats"], *([self._am(0, j), None] if self._f16() else []),
-                                 region=lay["region"])
-                elif self._f16() or ts is not None:
-                    K.ln_elu_fwd(lay["y"], lay["gamma"], lay["beta"], lay["a"], lay["stats"], self._am(0, j), ts)
-                else:
-                    K.ln_elu_fwd(lay["y"], lay["gamma"], lay["beta"], lay["a"], lay["stats"])
+                x_s16 = lay["a_s16_now"] = lay["a_s16"]
+                K.ln_elu_fwd(lay["y"], lay["gamma"], lay["beta"], lay["a"], lay["stats"],
+                             **_on(amax_out=self._am(0, j), tile_stats=ts, region=lay["region"], out_s16=x_s16))
                 x = lay["a"]
-                x_s16 = s16
             else:
                 x = lay["y"]
         return x.view(self.B, self.L, FEAT_C)
@@ -443,6 +434,8 @@ class Trunk:
         assert getattr(self, "_fwd_for_backward", True), "the last forward was run with for_backward=False"
         if not param_grads and dimages is None:
             return                                 # (nothing to compute)
+        if not self.plan_current():
+            self.refresh_weights()                 # (as forward(): the weights' formats must be those of the options in force)
         dy = dctx.view(B, self.Hf, self.Wf, FEAT_C)
         n = len(self.layers)
         f16 = self._f16()
@@ -455,9 +448,9 @@ class Trunk:
         if f16:
             K.fill(self.amax[1], 0.0)
             K.absmax(dy, self._am(1, n - 1))
-            if any(l.get("dy_s16") for l in self.layers):
+            if any(l["dy_s16"] for l in self.layers):
                 K.fill(self.pq, 0.0)
-            if self.layers[-1].get("dy_s16") and self.layers[-1].get("ws_mode") == getattr(K, "conv_precision", 0):
+            if self.layers[-1]["dy_s16"]:
                 # no LayerNorm kernel writes the head's gradient: one conversion pass, and the last layer's dgrad and filter gradient
                 # stage it by DMA like every other layer's
                 if getattr(self, "_dctx16", None) is None:
@@ -475,19 +468,14 @@ class Trunk:
                     # conv1_1: dy was never written - the filter gradient computes it from the LayerNorm backward's operands
                     K.conv_c3_wgrad_ln(self.images, lay["y"], c3_fused, lay["gamma"], lay["beta"], lay["stats"], self._ln0_means, lay["gw"])
                     return
-                if prv is not None and prv.get("fused_now"):
-                    # the input activation was never written: the wgrad kernel applies LayerNorm + ELU to the producing layer's y
-                    K.conv_wgrad(prv["y"], dy, lay["gw"], lay["s"], self._am(0, j - 1), self._am(1, j), ln=(prv["stats"], prv["gamma"], prv["beta"]),
-                                 **({"dy_s16": True} if dy_s16 else {}))
-                else:
-                    x_in = self.images if j == 0 else prv["a"]
-                    x_s16 = bool(j and prv.get("a_s16_now"))
-                    if x_s16 or dy_s16:
-                        K.conv_wgrad(x_in, dy, lay["gw"], lay["s"], self._am(0, j - 1) if j else None, self._am(1, j), x_s16=x_s16, dy_s16=dy_s16)
-                    elif f16:
-                        K.conv_wgrad(x_in, dy, lay["gw"], lay["s"], self._am(0, j - 1) if j else None, self._am(1, j))
-                    else:
-                        K.conv_wgrad(x_in, dy, lay["gw"], lay["s"])
+                # a fused input activation was never written: the wgrad kernel applies LayerNorm + ELU to the producing layer's y
+                fused = j > 0 and prv["fused_now"]
+                x_in = self.images if j == 0 else (prv["y"] if fused else prv["a"])
+                K.conv_wgrad(x_in, dy, lay["gw"], lay["s"],
+                             **_on(amax_x=self._am(0, j - 1) if j else None, amax_dy=self._am(1, j),
+                                   ln=(prv["stats"], prv["gamma"], prv["beta"]) if fused else None,
+                                   x_s16=j > 0 and not fused and prv["a_s16_now"], dy_s16=dy_s16))
+
             def wgrad_on_side(cur=cur, lay=lay):
                 with torch.cuda.stream(side):
                     wgrad()
@@ -498,7 +486,7 @@ class Trunk:
                     if cur >= 0:
                         reader_done[cur] = torch.cuda.Event()
                         reader_done[cur].record(side)
-            late = side is not None and j > 0 and bool(getattr(K, "wgrad_late", False))
+            late = side is not None and j > 0 and bool(option(K, "wgrad_late"))
             if param_grads and side is None:
                 wgrad()
             elif param_grads and not late:
@@ -517,15 +505,13 @@ class Trunk:
                 main.wait_event(reader_done[nxt])
                 reader_done[nxt] = None
             dYp = dybufs[nxt][:numel].view(prev["out_shape"])
-            ws = lay["ws_bwd"] if (lay["ws_bwd"] is not None and lay.get("ws_mode") == getattr(K, "conv_precision", 0)) else None
-            if dy_s16:
-                assert ws is not None
-                K.conv_dgrad(dy, lay["w"], dA, lay["s"], ws, self._am(1, j), self._am(2, j), lay["ws_layout_bwd"], dy_s16=True)
-            elif ws is not None or f16:
-                assert not (ws is not None and lay["ws_layout_bwd"] == 4 and lay["cin"] % 128), "four-block producer / consumer tiles need a pre-split dy"
-                K.conv_dgrad(dy, lay["w"], dA, lay["s"], ws, self._am(1, j), self._am(2, j), lay["ws_layout_bwd"] if ws is not None else 0)
-            else:
-                K.conv_dgrad(dy, lay["w"], dA, lay["s"])
+            ws = lay["use_ws_bwd"]
+            assert ws is not None or not dy_s16, "a pre-split dy needs pre-split weights"
+            assert dy_s16 or not (ws is not None and lay["ws_layout_bwd"] == 4 and lay["cin"] % 128), \
+                "four-block producer / consumer tiles need a pre-split dy"
+            K.conv_dgrad(dy, lay["w"], dA, lay["s"],
+                         **_on(w_split=ws, amax_dy=self._am(1, j), amax_w=self._am(2, j),
+                               w_split_layout=lay["ws_layout_bwd"] if ws is not None else 0, dy_s16=dy_s16))
             if late:
                 # option wgrad_late: the filter gradient starts when dgrad_j has FINISHED, i.e. beside the HBM-bound LayerNorm backward
                 # of layer j - 1 instead of beside dgrad_j (both MFMA-bound)
@@ -533,9 +519,8 @@ class Trunk:
                 ev.record(main)
                 side.wait_event(ev)
                 wgrad_on_side()
-            nxt_s16 = bool(prev.get("dy_s16")) and prev.get("ws_mode") == getattr(K, "conv_precision", 0) and self._ln_fin is not None
             if (j == 1 and prev["cin"] == 3 and prev["region"] is None and self._ln_fin is not None and hasattr(K, "conv_c3_wgrad_ln")
-                    and getattr(K, "c3_ln_bwd_fused", False) and prev["out_shape"][3] == 32
+                    and option(K, "c3_ln_bwd_fused") and prev["out_shape"][3] == 32
                     and (dimages is None or hasattr(K, "conv_c3_dgrad_ln"))):
                 # conv1_1's LayerNorm: the reductions only.  Its dy has ONE consumer, conv1_1's filter gradient, which computes it
                 # from (y, dA) itself (sgg_conv2d_nhwc_wgrad_c3_ln): no apply pass, no dy tensor.  dA stays untouched until then
@@ -546,21 +531,14 @@ class Trunk:
                 c3_fused = dA
                 dy, cur, dy_s16 = None, nxt, False
                 continue
-            if nxt_s16:
-                K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, None, None, None, self._am(1, j - 1),
-                             region=prev["region"], ws=prev["ln_ws"], out_s16=True, pq=self.pq[j - 1])
-            elif self._ln_fin is not None:
-                K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, None, None, None, self._am(1, j - 1) if f16 else None,
-                             region=prev["region"], ws=prev["ln_ws"])
+            if self._ln_fin is not None:
+                pg = (None, None, None)           # deferred: the reductions stay in the layer's workspace until ln_bwd_finalize below
             else:
                 pg = (prev["ggamma"], prev["gbeta"], prev["gb"]) if param_grads else self._pg_scratch(prev)
-                if prev["region"] is not None:
-                    K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, *pg, *([self._am(1, j - 1)] if f16 else []),
-                                 region=prev["region"])
-                elif f16:
-                    K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, *pg, self._am(1, j - 1))
-                else:
-                    K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, *pg)
+            nxt_s16 = prev["dy_s16"]
+            K.ln_elu_bwd(prev["y"], dA, prev["gamma"], prev["beta"], prev["stats"], dYp, *pg,
+                         **_on(amax_out=self._am(1, j - 1), region=prev["region"], ws=prev["ln_ws"], out_s16=nxt_s16,
+                               pq=self.pq[j - 1] if nxt_s16 else None))
             dy, cur, dy_s16 = dYp, nxt, nxt_s16
         if dimages is not None:
             self._image_grad(dy, c3_fused, dimages)

@@ -9,6 +9,7 @@ class _K:
     conv_precision = 2
     ln_fusion = 1
     ln_fusion_skip = ()
+    presplit = False
 
     def conv_wsplit_layout(self, k, s, H, W, cin, cout):      # what csrc/conv_gather.hip: sgg_conv_wsplit_layout answers in mode 2
         if k == 3 and s == 1 and cout % 128 == 0 and cin % 64 == 0:
