@@ -308,6 +308,22 @@ int sgg_adam_tf_multi(float* params, const float* grads, float* m, float* v, lon
 /* ---- tf.argmax(x, axis=-1): train.py:270-271 ---------------------------------------------------------------- */
 int sgg_argmax_rows(const float* x, long long* out, int rows, int V, int ld, void* stream);
 
+/* ---- scene-graph prediction: score_accumulator.argsort() and the top-k selection, train.py:314-327 -----------
+ * The host side of the reference's evaluation (accumulate the N sampled triples of an image and their critic scores, argsort,
+ * take the first k) as one workgroup per image, extended to what a prediction needs: the DISTINCT triples in ranked order.
+ *   tokens int64 [N][nb][3] (sample k of image j at [k][j]; every token in [0, V)), d fp32 [N][nb][3] (the critic's three outputs).
+ *   score[k] = ((d0 + d1) + d2) / 3 in fp32 with a correctly rounded division (= numpy's float32 mean over the three steps).
+ *   Order: ascending score (descending = 1: descending), ties by the smaller sample index, NaN scores last in sample order in
+ *   both directions (ascending: np.argsort(score, kind="stable")).  A sample whose three tokens equal those of an earlier one in
+ *   that order is a duplicate of it.  For image j and u < min(n_distinct[j], K), slot [j][u] holds the u-th distinct triple:
+ *   triples int64 [nb][K][3], scores fp32 [nb][K] (of its first = best-ranked occurrence), first_rank int32 [nb][K] (position of
+ *   that occurrence among the N ordered samples), first_sample int32 [nb][K] (its sample index k), counts int32 [nb][K] (how many
+ *   of the N samples are this triple).  Slots u >= n_distinct[j] hold -1, NaN, -1, -1, 0.  sample_scores (optional, may be NULL):
+ *   fp32 [nb][N], the per-sample scores.  1 <= K <= N <= 4096, 1 <= V <= 2^21. */
+int sgg_rank_triples(const long long* tokens, const float* d, int N, int nb, int V, int K, int descending, long long* triples,
+                     float* scores, int* first_rank, int* first_sample, int* counts, int* n_distinct, float* sample_scores,
+                     void* stream);
+
 int sgg_fill(float* p, long long n, float value, void* stream);
 
 #ifdef __cplusplus

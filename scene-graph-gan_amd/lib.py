@@ -77,6 +77,7 @@ SIGNATURES = {
     "sgg_wgan_losses": (_i, [_vp, _vp, _f, _i, _i, _i, _vp, _vp]),
     "sgg_adam_tf_multi": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _vp]),
     "sgg_argmax_rows": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "sgg_rank_triples": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgg_fill": (_i, [_vp, _ll, _f, _vp]),
 }
 
@@ -896,6 +897,34 @@ class HipKernels:
         V = x.shape[-1]
         x2 = x.reshape(-1, V)
         self._check(self.lib.sgg_argmax_rows(_p(x2), _p(out), x2.shape[0], V, _ld(x2), self._stream()), "sgg_argmax_rows")
+
+    def rank_triples(self, tokens, d, K, descending=False, want_sample_scores=False, vocab=None, out=None):
+        """The ranked DISTINCT triples of every image (csrc/rank.hip): tokens int64 [N, nb, 3] (sample k of image j at [k, j]), d
+        [N, nb, 3] or [N, nb, 3, 1] critic outputs -> dict of new device tensors: triples int64 [nb, K, 3], scores [nb, K],
+        first_rank / first_sample / counts int32 [nb, K], n_distinct int32 [nb] and, on request, sample_scores [nb, N].  Score =
+        fp32 mean of the three outputs; ascending (descending=True: descending), ties by sample index, NaN last; slots behind
+        n_distinct hold -1 / NaN / -1 / -1 / 0.  vocab: the vocabulary size (every token in [0, vocab); default: the library's
+        limit, 2^21).  out: optional dict of preallocated contiguous tensors under those names."""
+        self._dev(tokens, d)
+        assert tokens.dtype == torch.int64 and tokens.dim() == 3 and tokens.shape[2] == 3 and tokens.is_contiguous()
+        N, nb = int(tokens.shape[0]), int(tokens.shape[1])
+        assert d.dtype == torch.float32 and d.numel() == N * nb * 3 and d.is_contiguous(), "d must be contiguous [N, nb, 3]"
+        K, V = max(int(K), 0), (1 << 21) if vocab is None else int(vocab)
+        spec = {"triples": ((nb, K, 3), torch.int64), "scores": ((nb, K), torch.float32), "first_rank": ((nb, K), torch.int32),
+                "first_sample": ((nb, K), torch.int32), "counts": ((nb, K), torch.int32), "n_distinct": ((nb,), torch.int32)}
+        if want_sample_scores:
+            spec["sample_scores"] = ((nb, N), torch.float32)
+        res = {}
+        for name, (shape, dtype) in spec.items():
+            t = out[name] if out is not None else torch.empty(shape, dtype=dtype, device=tokens.device)
+            self._dev(t)
+            assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous(), name
+            res[name] = t
+        self._check(self.lib.sgg_rank_triples(_p(tokens), _p(d), N, nb, V, K, int(bool(descending)),
+                                              _p(res["triples"]), _p(res["scores"]), _p(res["first_rank"]), _p(res["first_sample"]),
+                                              _p(res["counts"]), _p(res["n_distinct"]), _p(res.get("sample_scores")),
+                                              self._stream()), "sgg_rank_triples")
+        return res
 
     def fill(self, t, value):
         self._dev(t)

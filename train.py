@@ -2,6 +2,7 @@
 
     python train.py --synthetic 64,224,1000 --max_iterations 20           # no Visual Genome files needed
     python train.py --checkpoints_dir ckpt --saliency_dir maps             # per-word saliency maps of the test split
+    python train.py --checkpoints_dir ckpt --predict_dir graphs            # ranked scene graph of every test image
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -31,6 +32,7 @@ from sgg_amd import dp as dpmod
 from sgg_amd.api import kernels_for
 from sgg_amd.data import PrefetchLoader, ShuffledStream, parse_image
 from sgg_amd.params import EMBED_DIM
+from sgg_amd.predict import DEFAULT_LOGITS_BUDGET_BYTES, images_per_pass, scene_graph
 from sgg_amd.step import GanStep
 
 
@@ -503,6 +505,133 @@ class SceneGraphGAN(object):
             print({"saliency_dir": out_dir, "images": len(items)})
         return index
 
+    ############################################################
+    ## Prediction: the ranked distinct triples of an image (csrc/rank.hip, sgg_amd/predict.py)
+    ############################################################
+    def _predict_items(self, items=None, max_images=None):
+        """[(key, image tensor or path)]: items may hold standardised [S,S,3] tensors, image paths or (image, anything) pairs; the
+        default is the test split, or with --synthetic the synthetic images of test() (same seed, same sequence).  key = the path,
+        or the index for a tensor."""
+        if items is None:
+            return self._saliency_items(max_images)
+        out = []
+        for i, it in enumerate(list(items)[:max_images]):
+            x = it[0] if isinstance(it, (tuple, list)) else it
+            out.append((x if isinstance(x, str) else str(i), x))
+        return out
+
+    def _predict_iter(self, items=None, max_images=None, n_samples=None, top_k=None, descending=False, with_attention=False,
+                      logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
+        """predict(), one image at a time (write_predictions streams it to disk)."""
+        if self.step is None:
+            images, _ = self._next_batch(0)
+            self._constructOps(images)
+        self.step.flush()
+        K = kernels_for(self.device)
+        V, TB = len(self.vocab), max(1, self.TEST_BATCH_SIZE)
+        N = int(n_samples) if n_samples is not None else self.TEST_BATCH_MULTIPLIER * TB
+        top_k = int(top_k) if top_k is not None else N
+        if not 1 <= top_k <= N <= 4096:
+            raise ValueError("predict: 1 <= top_k <= n_samples <= 4096 (got top_k = %d, n_samples = %d)" % (top_k, N))
+        passes = -(-N // TB)
+        items = self._predict_items(items, max_images)
+        if not items:
+            return
+        nb = images_per_pass(N, V, TB, len(items), logits_budget_bytes)
+        ordering = "%s mean critic score" % ("descending" if descending else "ascending")
+        load = lambda x: self._parseFunction(x) if isinstance(x, str) else x
+        pool = ThreadPoolExecutor(max_workers=min(16, nb)) if any(isinstance(x, str) for _, x in items) else None
+        fetch = lambda i0: [pool.submit(load, x) if pool is not None else x for _, x in items[i0:i0 + nb]]
+        # the ranked outputs of a batch live in ONE device buffer (carved into the kernel's output tensors): one copy to the host
+        parts = [("triples", np.int64, (nb, top_k, 3)), ("scores", np.float32, (nb, top_k)), ("first_rank", np.int32, (nb, top_k)),
+                 ("first_sample", np.int32, (nb, top_k)), ("counts", np.int32, (nb, top_k)), ("n_distinct", np.int32, (nb,))]
+        offs, total = {}, 0
+        for name, dt, shape in parts:
+            offs[name] = total
+            total += -(-int(np.prod(shape)) * np.dtype(dt).itemsize // 8) * 8
+        packed = torch.empty((total,), dtype=torch.uint8, device=self.device)
+        tdt = {np.int64: torch.int64, np.float32: torch.float32, np.int32: torch.int32}
+        out = {name: packed[offs[name]:offs[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(tdt[dt]).view(shape)
+               for name, dt, shape in parts}
+        toks = torch.empty((N, nb, 3), dtype=torch.int64, device=self.device)
+        col = torch.arange(nb, device=self.device).view(nb, 1)
+        gen = torch.Generator().manual_seed(self.seed + 123)
+        try:
+            pending = fetch(0)
+            for i0 in range(0, len(items), nb):
+                imgs = [f.result() for f in pending] if pool is not None else pending
+                pending = fetch(i0 + nb) if i0 + nb < len(items) else None
+                n = len(imgs)
+                images = torch.stack(imgs + [imgs[-1]] * (nb - n)).to(self.device)      # (the last batch padded with its last image)
+                noise = torch.zeros((passes * TB, nb, 512))
+                for j in range(n):
+                    for p in range(passes):
+                        noise[p * TB:(p + 1) * TB, j] = torch.randn((TB, 512), generator=gen)
+                logits = self.g.sample(images, N, noise[:N].to(self.device))
+                K.argmax_rows(logits, toks.view(-1))
+                d = self.d.score_samples(logits, images)
+                K.rank_triples(toks, d.view(N, nb, 3), top_k, descending=descending, vocab=V, out=out)
+                if with_attention:      # the attention of every triple's first-occurrence sample: head row first_sample * nb + j
+                    rows = out["first_sample"].long().clamp_(min=0) * nb + col
+                    al = self.g.alphas
+                    side = int(round(al.shape[-1] ** 0.5))
+                    att_h = al[rows.view(-1)].view(nb, top_k, 3, side, side).cpu().numpy()
+                host = packed.cpu().numpy()
+                h = {name: host[offs[name]:offs[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape)
+                     for name, dt, shape in parts}
+                for j in range(n):
+                    nd = int(h["n_distinct"][j])
+                    U = min(nd, top_k)
+                    r = {"image": items[i0 + j][0], "n_distinct": nd, "ordering": ordering}
+                    for name in ("triples", "scores", "first_rank", "first_sample", "counts"):
+                        r[name] = h[name][j, :U].copy()
+                    r["words"] = [[self.reverse_vocab.get(int(i), "UNK") for i in row] for row in r["triples"]]
+                    r["graph"] = scene_graph(r["triples"], r["scores"], r["counts"], self.reverse_vocab)
+                    if with_attention:
+                        r["attention"] = att_h[j, :U].copy()
+                    yield r
+        finally:
+            if pool is not None:
+                pool.shutdown(wait=True, cancel_futures=True)
+
+    def predict(self, items=None, max_images=None, n_samples=None, top_k=None, descending=False, with_attention=False,
+                logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
+        """The scene graph of every image: its n_samples generator samples (default TEST_BATCH_MULTIPLIER x TEST_BATCH_SIZE) scored by
+        the critic as in test(), reduced on the device to the DISTINCT triples in ranked order (K.rank_triples: ascending mean
+        critic score - the order of test() - or descending=True for the highest score first; ties by sample index), the first top_k
+        of them kept (default: all).
+
+        items: list of standardised [S,S,3] tensors, image paths or (image, anything) pairs; default: the test split, or with
+        --synthetic the synthetic images of test().  Returns one dict per image: triples [U,3] int64, words, scores [U] (of each
+        triple's best-ranked sample), first_rank [U] (position of that sample among the n_samples ordered ones), first_sample [U],
+        counts [U] (samples that were this triple), n_distinct (before top_k), graph (sgg_amd.predict.scene_graph), ordering, image
+        (path or index) and, with with_attention, attention [U,3,Hf,Wf]: the generator's attention of each triple's first_sample.
+
+        Schedule: sgg_amd.predict.images_per_pass images per encoder pass (TEST_BATCH_SIZE unless the [n_samples, nb, 3, V] logits
+        exceed logits_budget_bytes; the last batch padded with its last image), Generator.sample -> argmax_rows ->
+        Discriminator.score_samples -> rank_triples, one copy of the ranked outputs to the host per batch (tokens and scores of the
+        samples stay on the device).  Noise: per image ceil(n_samples / TEST_BATCH_SIZE) draws of [TEST_BATCH_SIZE, 512] from seed
+        + 123, image after image, the first n_samples rows used - with the defaults the stream of test(), sample for sample.
+        Touches no weights and no optimiser state; usable on an untrained model, as test() is."""
+        return list(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention, logits_budget_bytes))
+
+    def write_predictions(self, out_dir, max_images=None, n_samples=None, top_k=None, descending=False, items=None):
+        """predict(with_attention=True) of the test images to disk: one <index>.npz per image (triples, words, scores, first_rank,
+        first_sample, counts, n_distinct, attention) and index.json (image path or index -> npz file, n_distinct and the graph)."""
+        os.makedirs(out_dir, exist_ok=True)
+        index = {}
+        for i, r in enumerate(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention=True)):
+            name = "%06d.npz" % i
+            np.savez(os.path.join(out_dir, name), triples=r["triples"], words=np.array(r["words"], dtype=str).reshape(-1, 3),
+                     scores=r["scores"], first_rank=r["first_rank"], first_sample=r["first_sample"], counts=r["counts"],
+                     n_distinct=np.int32(r["n_distinct"]), attention=r["attention"])
+            index[r["image"]] = {"file": name, "n_distinct": r["n_distinct"], "graph": r["graph"]}
+        with open(os.path.join(out_dir, "index.json"), "w") as f:
+            json.dump(index, f, indent=1)
+        if self.rank == 0:
+            print({"predict_dir": out_dir, "images": len(index)})
+        return index
+
 
 def _str2bool(v):
     """--resume of the reference is `type=bool` (train.py:410), which makes every non-empty string - "False" included - true."""
@@ -545,6 +674,14 @@ if __name__ == "__main__":
     parser.add_argument("--saliency_dir", default=None,
                         help="load the checkpoint in --checkpoints_dir, write per-word saliency maps of the test images (one .npz per "
                              "image + index.json) to this directory and exit; no training")
+    parser.add_argument("--predict_dir", default=None,
+                        help="load the checkpoint in --checkpoints_dir, write the ranked scene graph of the test images (one .npz per "
+                             "image + index.json) to this directory and exit; no training")
+    parser.add_argument("--predict_samples", default=None, type=int,
+                        help="generator samples per image for --predict_dir (default: 8 x the test batch size, as the evaluation)")
+    parser.add_argument("--top_k", default=None, type=int, help="keep the first K distinct triples per image (default: all)")
+    parser.add_argument("--predict_descending", action="store_true",
+                        help="highest critic score first (default: ascending, the order of the evaluation)")
     args = parser.parse_args()
     params = vars(args)
 
@@ -564,6 +701,13 @@ if __name__ == "__main__":
                   file=sys.stderr)
             sys.exit(2)
         gan.write_saliency(params["saliency_dir"], max_images=params["max_test_images"])
+    elif params["predict_dir"]:
+        if not gan.load_checkpoint():
+            print("--predict_dir: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
+                  file=sys.stderr)
+            sys.exit(2)
+        gan.write_predictions(params["predict_dir"], max_images=params["max_test_images"], n_samples=params["predict_samples"],
+                              top_k=params["top_k"], descending=params["predict_descending"])
     elif params["test_only"]:
         if not gan.load_checkpoint():
             print("--test_only: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
