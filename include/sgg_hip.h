@@ -324,6 +324,23 @@ int sgg_rank_triples(const long long* tokens, const float* d, int N, int nb, int
                      float* scores, int* first_rank, int* first_sample, int* counts, int* n_distinct, float* sample_scores,
                      void* stream);
 
+/* ---- scene-graph metrics: the ground truth matched against the ranked distinct list --------------------------------------
+ * Where each ground-truth triple of an image stands in that image's ranked list of distinct predictions (sgg_rank_triples), one
+ * workgroup per image.
+ *   ranked int64 [nb][K][3], n_distinct int32 [nb]: outputs of sgg_rank_triples; image j's list is its first
+ *   U_j = min(n_distinct[j], K) rows, the rows behind U_j are never read.  gt int64 [nb][M][3], gt_count int32 [nb]: image j has
+ *   gt_count[j] ground-truth rows, the rows m >= gt_count[j] are padding with arbitrary content.
+ *   pos int32 [nb][M]:  u >= 0  row m equals ranked[j][u] (at most one u: the list is distinct);
+ *                       -1      valid row, absent from the list;
+ *                       -2      valid row equal to an earlier row m' < m of the image (the smallest row carries the result);
+ *                       -3      padding row;
+ *                       -4      valid row with a token outside [0, V): never matches, never merges with another row, not counted.
+ *   n_gt int32 [nb]: rows with pos >= -1, the distinct valid ground-truth triples of the image.
+ *   1 <= K <= 4096, 1 <= M <= 4096, 1 <= V <= 2^21.  gt_count and n_distinct are device arrays and are NOT checked on the host:
+ *   the kernel clamps them to [0, M] and [0, K].  All results are integers: two launches give the same bits. */
+int sgg_match_triples(const long long* ranked, const int* n_distinct, int nb, int K, const long long* gt, const int* gt_count, int M,
+                      int V, int* pos, int* n_gt, void* stream);
+
 int sgg_fill(float* p, long long n, float value, void* stream);
 
 #ifdef __cplusplus

@@ -7,36 +7,16 @@
 //                       the run length (binary search for its end) is the triple's count;
 //                    4. prefix sum of the run heads in rank order = the slot of every distinct triple.
 // Not on the training path.
-#include "sgg_common.h"
+#include "bitonic.h"
 
-#define RANK_MAX_N 4096
-#define RANK_MAX_V (1 << 21)            // three tokens pack into 63 bits
-#define RANK_PAD 0xffffffffffffffffull  // sorts behind every sample in both sorts
+#define RANK_MAX_N SGG_SORT_MAX_P
+#define RANK_MAX_V SGG_SORT_MAX_V       // three tokens pack into 63 bits
+#define RANK_PAD SGG_SORT_PAD           // sorts behind every sample in both sorts
 
 // float -> unsigned whose order is the float order (-inf lowest, +inf = 0xff800000 highest); +-0 are one value
 __device__ __forceinline__ unsigned rank_orderable(float s) {
   const unsigned b = (s == 0.f) ? 0u : __float_as_uint(s);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// ascending bitonic sort of the P (a power of two) pairs (key[i], pay[i]), compared as (key, pay); blockDim.x threads
-__device__ __forceinline__ void rank_bitonic(unsigned long long* key, unsigned short* pay, int P) {
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      __syncthreads();
-      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-        const int i = 2 * t - (t & (j - 1)), l = i + j;      // bit j of i is clear
-        const unsigned long long a = key[i], b = key[l];
-        const unsigned short pa = pay[i], pb = pay[l];
-        const bool gt = a > b || (a == b && pa > pb);
-        if (gt == ((i & k) == 0)) {
-          key[i] = b; key[l] = a;
-          pay[i] = pb; pay[l] = pa;
-        }
-      }
-    }
-  }
-  __syncthreads();
 }
 
 __device__ __forceinline__ float rank_score(const float* __restrict__ d, int k, int nb, int j) {
@@ -73,19 +53,18 @@ __global__ __launch_bounds__(1024) void rank_triples_kernel(const long long* __r
     cnt[k] = 0;
   }
   // 2. the stable order: order[r] = sample at rank r
-  rank_bitonic(key, order, P);
+  sgg_bitonic_pairs(key, order, P);
   // 3. (packed triple, rank)
   for (int r = tid; r < P; r += T) {
     unsigned long long c = RANK_PAD;
     if (r < N) {
       const long long* t = tokens + ((size_t)order[r] * nb + j) * 3;
-      c = ((unsigned long long)(t[0] & (RANK_MAX_V - 1)) << 42) | ((unsigned long long)(t[1] & (RANK_MAX_V - 1)) << 21) |
-          (unsigned long long)(t[2] & (RANK_MAX_V - 1));
+      c = sgg_pack_triple(t[0], t[1], t[2]);
     }
     key[r] = c;
     pay[r] = (unsigned short)r;
   }
-  rank_bitonic(key, pay, P);
+  sgg_bitonic_pairs(key, pay, P);
   for (int q = tid; q < N; q += T) {             // (the first N sorted entries are the samples: the padding sorts last)
     const unsigned long long c = key[q];
     if (q > 0 && key[q - 1] == c) continue;

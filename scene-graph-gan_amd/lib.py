@@ -78,6 +78,7 @@ SIGNATURES = {
     "sgg_adam_tf_multi": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _vp]),
     "sgg_argmax_rows": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sgg_rank_triples": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgg_match_triples": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "sgg_fill": (_i, [_vp, _ll, _f, _vp]),
 }
 
@@ -924,6 +925,29 @@ class HipKernels:
                                               _p(res["triples"]), _p(res["scores"]), _p(res["first_rank"]), _p(res["first_sample"]),
                                               _p(res["counts"]), _p(res["n_distinct"]), _p(res.get("sample_scores")),
                                               self._stream()), "sgg_rank_triples")
+        return res
+
+    def match_triples(self, ranked, n_distinct, gt, gt_count, vocab=None, out=None):
+        """Where every ground-truth triple stands in its image's ranked distinct list (csrc/match.hip): ranked int64 [nb, K, 3] and
+        n_distinct int32 [nb] (rank_triples' outputs), gt int64 [nb, M, 3], gt_count int32 [nb] (rows m >= gt_count[j] are padding)
+        -> {"pos": int32 [nb, M], "n_gt": int32 [nb]}.  pos: the slot u >= 0 of the list that equals the row, -1 absent, -2
+        duplicate of an earlier row of the image, -3 padding, -4 a token outside [0, vocab); n_gt: rows with pos >= -1.  vocab:
+        default the library's limit, 2^21.  out: optional dict of preallocated contiguous tensors under those names."""
+        self._dev(ranked, n_distinct, gt, gt_count)
+        assert ranked.dtype == torch.int64 and ranked.dim() == 3 and ranked.shape[2] == 3 and ranked.is_contiguous()
+        nb, K = int(ranked.shape[0]), int(ranked.shape[1])
+        assert gt.dtype == torch.int64 and gt.dim() == 3 and gt.shape[0] == nb and gt.shape[2] == 3 and gt.is_contiguous()
+        M, V = int(gt.shape[1]), (1 << 21) if vocab is None else int(vocab)
+        for t in (n_distinct, gt_count):
+            assert t.dtype == torch.int32 and tuple(t.shape) == (nb,) and t.is_contiguous()
+        res = {}
+        for name, shape in (("pos", (nb, M)), ("n_gt", (nb,))):
+            t = out[name] if out is not None else torch.empty(shape, dtype=torch.int32, device=ranked.device)
+            self._dev(t)
+            assert tuple(t.shape) == shape and t.dtype == torch.int32 and t.is_contiguous(), name
+            res[name] = t
+        self._check(self.lib.sgg_match_triples(_p(ranked), _p(n_distinct), nb, K, _p(gt), _p(gt_count), M, V, _p(res["pos"]),
+                                               _p(res["n_gt"]), self._stream()), "sgg_match_triples")
         return res
 
     def fill(self, t, value):

@@ -3,6 +3,7 @@
     python train.py --synthetic 64,224,1000 --max_iterations 20           # no Visual Genome files needed
     python train.py --checkpoints_dir ckpt --saliency_dir maps             # per-word saliency maps of the test split
     python train.py --checkpoints_dir ckpt --predict_dir graphs            # ranked scene graph of every test image
+    python train.py --checkpoints_dir ckpt --metrics_out metrics.json      # R@K, mR@K, zsR@K of the test split
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -32,6 +33,7 @@ from sgg_amd import dp as dpmod
 from sgg_amd.api import kernels_for
 from sgg_amd.data import PrefetchLoader, ShuffledStream, parse_image
 from sgg_amd.params import EMBED_DIM
+from sgg_amd.metrics import MAX_GT, RecallAccumulator, zero_shot_mask
 from sgg_amd.predict import DEFAULT_LOGITS_BUDGET_BYTES, images_per_pass, scene_graph
 from sgg_amd.step import GanStep
 
@@ -520,41 +522,44 @@ class SceneGraphGAN(object):
             out.append((x if isinstance(x, str) else str(i), x))
         return out
 
-    def _predict_iter(self, items=None, max_images=None, n_samples=None, top_k=None, descending=False, with_attention=False,
-                      logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
-        """predict(), one image at a time (write_predictions streams it to disk)."""
+    def _sampling_setup(self, who, n_samples, top_k):
+        """(kernels, V, TEST_BATCH_SIZE, samples per image, list slots) of predict() / evaluate(); builds the networks if needed."""
         if self.step is None:
             images, _ = self._next_batch(0)
             self._constructOps(images)
         self.step.flush()
-        K = kernels_for(self.device)
-        V, TB = len(self.vocab), max(1, self.TEST_BATCH_SIZE)
+        TB = max(1, self.TEST_BATCH_SIZE)
         N = int(n_samples) if n_samples is not None else self.TEST_BATCH_MULTIPLIER * TB
         top_k = int(top_k) if top_k is not None else N
         if not 1 <= top_k <= N <= 4096:
-            raise ValueError("predict: 1 <= top_k <= n_samples <= 4096 (got top_k = %d, n_samples = %d)" % (top_k, N))
-        passes = -(-N // TB)
-        items = self._predict_items(items, max_images)
-        if not items:
-            return
-        nb = images_per_pass(N, V, TB, len(items), logits_budget_bytes)
-        ordering = "%s mean critic score" % ("descending" if descending else "ascending")
-        load = lambda x: self._parseFunction(x) if isinstance(x, str) else x
-        pool = ThreadPoolExecutor(max_workers=min(16, nb)) if any(isinstance(x, str) for _, x in items) else None
-        fetch = lambda i0: [pool.submit(load, x) if pool is not None else x for _, x in items[i0:i0 + nb]]
-        # the ranked outputs of a batch live in ONE device buffer (carved into the kernel's output tensors): one copy to the host
-        parts = [("triples", np.int64, (nb, top_k, 3)), ("scores", np.float32, (nb, top_k)), ("first_rank", np.int32, (nb, top_k)),
-                 ("first_sample", np.int32, (nb, top_k)), ("counts", np.int32, (nb, top_k)), ("n_distinct", np.int32, (nb,))]
+            raise ValueError("%s: 1 <= top_k <= n_samples <= 4096 (got top_k = %d, n_samples = %d)" % (who, top_k, N))
+        return kernels_for(self.device), len(self.vocab), TB, N, top_k
+
+    def _device_pack(self, parts, device):
+        """ONE uint8 buffer on `device` carved into the tensors `parts` = [(name, numpy dtype, shape)] (8-byte aligned), so that they
+        cross the bus as one copy: (buffer, {name: tensor view}, views(buffer on the other side as numpy) -> {name: array})."""
         offs, total = {}, 0
         for name, dt, shape in parts:
             offs[name] = total
             total += -(-int(np.prod(shape)) * np.dtype(dt).itemsize // 8) * 8
-        packed = torch.empty((total,), dtype=torch.uint8, device=self.device)
+        packed = torch.empty((total,), dtype=torch.uint8, device=device)
         tdt = {np.int64: torch.int64, np.float32: torch.float32, np.int32: torch.int32}
-        out = {name: packed[offs[name]:offs[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(tdt[dt]).view(shape)
-               for name, dt, shape in parts}
+        size = lambda dt, shape: int(np.prod(shape)) * np.dtype(dt).itemsize
+        out = {name: packed[offs[name]:offs[name] + size(dt, shape)].view(tdt[dt]).view(shape) for name, dt, shape in parts}
+        views = lambda host: {name: host[offs[name]:offs[name] + size(dt, shape)].view(dt).reshape(shape) for name, dt, shape in parts}
+        return packed, out, views
+
+    def _ranked_batches(self, K, items, N, nb, top_k, descending, out):
+        """The sampling passes predict() and evaluate() share.  items: [(key, image tensor or path)]; per batch of nb images (the
+        last one padded with its last image): Generator.sample -> argmax_rows -> Discriminator.score_samples -> rank_triples into
+        `out`; yields (i0, n) = first item and number of real images of the batch, with `out` (and self.g.alphas) holding its
+        results.  Noise: per image ceil(N / TEST_BATCH_SIZE) draws of [TEST_BATCH_SIZE, 512] from seed + 123, image after image."""
+        V, TB = len(self.vocab), max(1, self.TEST_BATCH_SIZE)
+        passes = -(-N // TB)
+        load = lambda x: self._parseFunction(x) if isinstance(x, str) else x
+        pool = ThreadPoolExecutor(max_workers=min(16, nb)) if any(isinstance(x, str) for _, x in items) else None
+        fetch = lambda i0: [pool.submit(load, x) if pool is not None else x for _, x in items[i0:i0 + nb]]
         toks = torch.empty((N, nb, 3), dtype=torch.int64, device=self.device)
-        col = torch.arange(nb, device=self.device).view(nb, 1)
         gen = torch.Generator().manual_seed(self.seed + 123)
         try:
             pending = fetch(0)
@@ -571,28 +576,43 @@ class SceneGraphGAN(object):
                 K.argmax_rows(logits, toks.view(-1))
                 d = self.d.score_samples(logits, images)
                 K.rank_triples(toks, d.view(N, nb, 3), top_k, descending=descending, vocab=V, out=out)
-                if with_attention:      # the attention of every triple's first-occurrence sample: head row first_sample * nb + j
-                    rows = out["first_sample"].long().clamp_(min=0) * nb + col
-                    al = self.g.alphas
-                    side = int(round(al.shape[-1] ** 0.5))
-                    att_h = al[rows.view(-1)].view(nb, top_k, 3, side, side).cpu().numpy()
-                host = packed.cpu().numpy()
-                h = {name: host[offs[name]:offs[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape)
-                     for name, dt, shape in parts}
-                for j in range(n):
-                    nd = int(h["n_distinct"][j])
-                    U = min(nd, top_k)
-                    r = {"image": items[i0 + j][0], "n_distinct": nd, "ordering": ordering}
-                    for name in ("triples", "scores", "first_rank", "first_sample", "counts"):
-                        r[name] = h[name][j, :U].copy()
-                    r["words"] = [[self.reverse_vocab.get(int(i), "UNK") for i in row] for row in r["triples"]]
-                    r["graph"] = scene_graph(r["triples"], r["scores"], r["counts"], self.reverse_vocab)
-                    if with_attention:
-                        r["attention"] = att_h[j, :U].copy()
-                    yield r
+                yield i0, n
         finally:
             if pool is not None:
                 pool.shutdown(wait=True, cancel_futures=True)
+
+    def _predict_iter(self, items=None, max_images=None, n_samples=None, top_k=None, descending=False, with_attention=False,
+                      logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
+        """predict(), one image at a time (write_predictions streams it to disk)."""
+        K, V, TB, N, top_k = self._sampling_setup("predict", n_samples, top_k)
+        items = self._predict_items(items, max_images)
+        if not items:
+            return
+        nb = images_per_pass(N, V, TB, len(items), logits_budget_bytes)
+        ordering = "%s mean critic score" % ("descending" if descending else "ascending")
+        # the ranked outputs of a batch live in ONE device buffer (carved into the kernel's output tensors): one copy to the host
+        packed, out, views = self._device_pack(
+            [("triples", np.int64, (nb, top_k, 3)), ("scores", np.float32, (nb, top_k)), ("first_rank", np.int32, (nb, top_k)),
+             ("first_sample", np.int32, (nb, top_k)), ("counts", np.int32, (nb, top_k)), ("n_distinct", np.int32, (nb,))], self.device)
+        col = torch.arange(nb, device=self.device).view(nb, 1)
+        for i0, n in self._ranked_batches(K, items, N, nb, top_k, descending, out):
+            if with_attention:      # the attention of every triple's first-occurrence sample: head row first_sample * nb + j
+                rows = out["first_sample"].long().clamp_(min=0) * nb + col
+                al = self.g.alphas
+                side = int(round(al.shape[-1] ** 0.5))
+                att_h = al[rows.view(-1)].view(nb, top_k, 3, side, side).cpu().numpy()
+            h = views(packed.cpu().numpy())
+            for j in range(n):
+                nd = int(h["n_distinct"][j])
+                U = min(nd, top_k)
+                r = {"image": items[i0 + j][0], "n_distinct": nd, "ordering": ordering}
+                for name in ("triples", "scores", "first_rank", "first_sample", "counts"):
+                    r[name] = h[name][j, :U].copy()
+                r["words"] = [[self.reverse_vocab.get(int(i), "UNK") for i in row] for row in r["triples"]]
+                r["graph"] = scene_graph(r["triples"], r["scores"], r["counts"], self.reverse_vocab)
+                if with_attention:
+                    r["attention"] = att_h[j, :U].copy()
+                yield r
 
     def predict(self, items=None, max_images=None, n_samples=None, top_k=None, descending=False, with_attention=False,
                 logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
@@ -631,6 +651,101 @@ class SceneGraphGAN(object):
         if self.rank == 0:
             print({"predict_dir": out_dir, "images": len(index)})
         return index
+
+
+    ############################################################
+    ## Metrics: R@K, mR@K, zsR@K over distinct predictions (csrc/match.hip, sgg_amd/metrics.py)
+    ############################################################
+    def _evaluate_items(self, items=None, max_images=None):
+        """[(key, image tensor or path, [[s, p, o], ...])]: the given (image, triples) pairs, else the test split with its true
+        triples, or with --synthetic the synthetic images and triples of test() (same seed)."""
+        if items is not None:
+            return [(x if isinstance(x, str) else str(i), x, [list(map(int, t)) for t in real])
+                    for i, (x, real) in enumerate(list(items)[:max_images])]
+        if self.dataset is None:
+            g = torch.Generator().manual_seed(self.seed + 99)
+            return [(str(i), torch.randn((self.image_size, self.image_size, 3), generator=g),
+                     torch.randint(0, len(self.vocab), (5, 3), generator=g).tolist()) for i in range(max_images or 2)]
+        return [(k, k, real) for k, real in self.test_items[:max_images]]
+
+    def evaluate(self, items=None, max_images=None, ks=(20, 50, 100), n_samples=None, descending=False, train_triples=None,
+                 return_details=False, out_path=None, logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
+        """R@K, mR@K and zsR@K of the model (sgg_amd.metrics.RecallAccumulator has the definitions): per image the ranked list of
+        DISTINCT triples of predict() - same passes, same noise stream, same order - cut at max(ks), and the image's true triples
+        matched against it on the device (K.match_triples).  Distinct predictions, denominators |GT|: not the protocol of test(),
+        whose top 50 / 100 are samples (duplicates use up the budget) and whose denominators are the constants 50 and 100.
+
+        items: list of (standardised [S,S,3] tensor or image path, [[s, p, o], ...]); default: the test split, or with --synthetic
+        the synthetic images and triples of test().  train_triples: set of (s, p, o) tuples that zsR@K counts as seen; default:
+        every triple of the training images (the train and val label arrays, both from the 90 % image split), or None with
+        --synthetic (zsR@K is then None).  Returns RecallAccumulator.result() plus ks, samples_per_image, ordering, mean_n_distinct,
+        definition and, with return_details, details: per image {"image", "pos", "n_gt", "n_distinct"}; rank 0 writes the dict as
+        JSON to out_path.  A ground-truth list of more than 4096 triples or a token outside the vocabulary raises ValueError
+        before anything is launched.
+
+        Schedule: the batches of predict(); per batch one copy to the device (the padded ground truth and its counts) and one
+        copy back (pos, n_gt, n_distinct).  Ranked triples, tokens and scores stay on the device.  Touches no weights and no
+        optimiser state; usable on an untrained model, as test() and predict() are."""
+        ks = tuple(sorted(set(int(k) for k in ks)))
+        if not ks or ks[0] < 1:
+            raise ValueError("evaluate: ks must be positive integers (got %r)" % (ks,))
+        items = self._evaluate_items(items, max_images)
+        V = len(self.vocab)
+        for key, _, real in items:
+            if len(real) > MAX_GT:
+                raise ValueError("evaluate: image %s has %d ground-truth triples (at most %d per image)" % (key, len(real), MAX_GT))
+            for t in real:
+                if len(t) != 3 or not all(0 <= x < V for x in t):
+                    raise ValueError("evaluate: image %s: ground-truth triple %r is not three tokens in [0, %d)" % (key, list(t), V))
+        if train_triples is None and self.dataset is not None:
+            train_triples = set(map(tuple, np.concatenate([self.dataset["train"][1], self.dataset["val"][1]]).tolist()))
+        K, V, TB, N, _ = self._sampling_setup("evaluate", n_samples, None)
+        top_k = min(max(ks), N)
+        acc = RecallAccumulator(ks, V)
+        details, nd_all = [], []
+        if items:
+            nb = images_per_pass(N, V, TB, len(items), logits_budget_bytes)
+            M = max(1, max(len(real) for _, _, real in items))
+            ranked = {name: torch.empty(shape, dtype=dt, device=self.device) for name, shape, dt in
+                      [("triples", (nb, top_k, 3), torch.int64), ("scores", (nb, top_k), torch.float32),
+                       ("first_rank", (nb, top_k), torch.int32), ("first_sample", (nb, top_k), torch.int32),
+                       ("counts", (nb, top_k), torch.int32)]}
+            packed, back, views = self._device_pack([("pos", np.int32, (nb, M)), ("n_gt", np.int32, (nb,)),
+                                                     ("n_distinct", np.int32, (nb,))], self.device)
+            ranked["n_distinct"] = back["n_distinct"]
+            gt_parts = [("gt", np.int64, (nb, M, 3)), ("gt_count", np.int32, (nb,))]
+            gt_host, _, gt_views = self._device_pack(gt_parts, "cpu")
+            gt_h = gt_views(gt_host.numpy())                    # (numpy views of the host buffer: filled in place)
+            gt_packed, gt_d, _ = self._device_pack(gt_parts, self.device)
+            for i0, n in self._ranked_batches(K, [(key, x) for key, x, _ in items], N, nb, top_k, descending, ranked):
+                gt_h["gt"][:] = 0
+                gt_h["gt_count"][:] = 0                  # (the padded images of the last batch: no ground truth)
+                for j in range(n):
+                    real = items[i0 + j][2]
+                    gt_h["gt"][j, :len(real)] = np.asarray(real, dtype=np.int64).reshape(-1, 3)
+                    gt_h["gt_count"][j] = len(real)
+                gt_packed.copy_(gt_host)
+                K.match_triples(ranked["triples"], ranked["n_distinct"], gt_d["gt"], gt_d["gt_count"], vocab=V, out=back)
+                h = views(packed.cpu().numpy())
+                for j in range(n):
+                    key, _, real = items[i0 + j]
+                    pos = h["pos"][j, :len(real)].copy()
+                    acc.add(pos, real, None if train_triples is None else zero_shot_mask(real, train_triples))
+                    nd_all.append(int(h["n_distinct"][j]))
+                    if return_details:
+                        details.append({"image": key, "pos": pos.tolist(), "n_gt": int(h["n_gt"][j]), "n_distinct": nd_all[-1]})
+        res = acc.result(self.reverse_vocab)
+        res.update({"ks": list(ks), "samples_per_image": N, "ordering": "%s mean critic score" % ("descending" if descending else "ascending"),
+                    "mean_n_distinct": float(np.mean(nd_all)) if nd_all else None,
+                    "definition": "distinct predictions, denominators |GT|: R@K = mean over images of hits in the first K distinct "
+                                  "triples / |GT|; mR@K = mean over predicates of the per-predicate mean over images; zsR@K = R@K on "
+                                  "the triples absent from the training set"})
+        if return_details:
+            res["details"] = details
+        if self.rank == 0 and out_path:
+            with open(out_path, "w") as f:
+                json.dump(res, f, indent=1)
+        return res
 
 
 def _str2bool(v):
@@ -678,10 +793,14 @@ if __name__ == "__main__":
                         help="load the checkpoint in --checkpoints_dir, write the ranked scene graph of the test images (one .npz per "
                              "image + index.json) to this directory and exit; no training")
     parser.add_argument("--predict_samples", default=None, type=int,
-                        help="generator samples per image for --predict_dir (default: 8 x the test batch size, as the evaluation)")
+                        help="generator samples per image for --predict_dir / --metrics_out (default: 8 x the test batch size, as the evaluation)")
     parser.add_argument("--top_k", default=None, type=int, help="keep the first K distinct triples per image (default: all)")
     parser.add_argument("--predict_descending", action="store_true",
                         help="highest critic score first (default: ascending, the order of the evaluation)")
+    parser.add_argument("--metrics_out", default=None,
+                        help="load the checkpoint in --checkpoints_dir, write R@K, mR@K and zsR@K of the test images (distinct "
+                             "predictions, denominators |GT|) as JSON to this file and exit; no training")
+    parser.add_argument("--metrics_k", default="20,50,100", help="the K values of --metrics_out, comma-separated")
     args = parser.parse_args()
     params = vars(args)
 
@@ -708,6 +827,15 @@ if __name__ == "__main__":
             sys.exit(2)
         gan.write_predictions(params["predict_dir"], max_images=params["max_test_images"], n_samples=params["predict_samples"],
                               top_k=params["top_k"], descending=params["predict_descending"])
+    elif params["metrics_out"]:
+        if not gan.load_checkpoint():
+            print("--metrics_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
+                  file=sys.stderr)
+            sys.exit(2)
+        m = gan.evaluate(max_images=params["max_test_images"], ks=tuple(int(k) for k in params["metrics_k"].split(",") if k.strip()),
+                         n_samples=params["predict_samples"], descending=params["predict_descending"], out_path=params["metrics_out"])
+        if gan.rank == 0:
+            print({k: v for k, v in m.items() if k != "predicates" and k != "definition"})
     elif params["test_only"]:
         if not gan.load_checkpoint():
             print("--test_only: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
