@@ -102,7 +102,8 @@ int sgg_conv2d_nhwc_fwd(const float* x, const float* w, const void* w_split, con
 /* operand_format of sgg_conv2d_nhwc_fwd, bits 8 .. 13 (launch hint, 0 = none): the persistent resident kernels (w_split_layout
  * 1 .. 4) occupy at most that many of an XCD's 32 CUs instead of all of them - for a forward pass that runs on its own HIP stream
  * beside another stream's chain of short, latency-critical launches (the recurrent heads), which then find free CUs at once.  The
- * work decomposition (tiles, products, summation orders) does not depend on it: results are bit-identical.
+ * work decomposition (tiles, products, summation orders) does not depend on it: results are bit-identical
+ * (tests/test_persistent_tiles_gpu.py: every resident kernel form under caps that give a workgroup several tiles, against no cap).
  * operand_format bit 0 (sgg_conv2d_nhwc_fwd / _dgrad: 0 or 1; _wgrad: bit 0 = x, bit 1 = dy): 1 = the operand is a PRE-SPLIT tensor as
  * sgg_layernorm_hwc_elu_fwd / _bwd write it with out_format 1 - same shape and bytes as the f32 tensor, every aligned group of 32
  * channels (128 B) holding the 32 leading fp16 pieces (64 B) then the 32 residual pieces of x * 2^e, e from the tensor's amax word

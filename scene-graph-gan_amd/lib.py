@@ -179,7 +179,7 @@ DEFAULT_OPTIONS = {
     # workgroup of G's forward to finish its tile.  The convolutions lose nothing on 28 of 32 CUs (every persistent kernel capped at
     # 28: +0.25 ms per step only, profiles/r05_persistent_cu_cap_ab.log); 28 here: 42.75 / 42.80 against 43.04 / 42.97 ms per step, on
     # another box 44.02 / 44.07 against 44.32 / 44.18; 30, 26, 24, 20: equal to none (profiles/r05_early_forward_cu_cap_ab*.log).
-    # Tiles, products and summation orders are unchanged: bit-identical results (tests/test_concurrency_gpu.py)
+    # Tiles, products and summation orders are unchanged: bit-identical results (tests/test_concurrency_gpu.py, tests/test_persistent_tiles_gpu.py)
     "g_early_cus": 28,
     # True: the LayerNorm backward of conv1_1's output runs without its apply pass - conv1_1's filter gradient, the only consumer of
     # that dy, computes it itself (sgg_conv2d_nhwc_wgrad_c3_ln): one read of y and da instead of the apply pass (2 reads + 1 write of

@@ -408,7 +408,8 @@ HALO_CASES = [
     (3, 8, 8, 128, 128),        # odd number of blocks
     (1, 16, 16, 128, 256),
     (2, 8, 8, 256, 256),
-    (5, 40, 24, 32, 32),        # 75 blocks: several stages per workgroup, ragged last stage
+    (5, 40, 24, 32, 32),        # 75 blocks = 38 tiles, the last one with a dead block; XCD ranges of 4 or 5 tiles, ONE tile per workgroup
+                                # (as in every case here; several tiles per workgroup: tests/test_persistent_tiles_gpu.py)
     (3, 24, 40, 64, 64),
     (1, 8, 8, 512, 512),        # 16 channel chunks, 4 n-tiles, one block: most XCD ranges are empty
     (9, 8, 16, 64, 32),         # 18 blocks over 8 XCD ranges of 0..1 tiles (N = 32 tile: 4 blocks per workgroup)
@@ -578,8 +579,10 @@ S2_CASES = [
     (5, 28, 256, 512),      # 980 positions, ragged last band, four n-tiles, 16 chunks
     (70, 4, 32, 128),       # 2x2 grid: a band spans up to 56 images (224 patch rows of two slots)
     (20, 8, 32, 128),       # 4x4 grid: a band of 128 positions spans 8 images (each with its own zero rows in the padded row space)
-    (24, 112, 32, 128),     # 336 bands of 224 positions: more work items than CUs -> the 7-tile variant (the small cases above run
-                            # the 4-tile variant unless LayerNorm partials are requested)
+    (24, 112, 32, 128),     # 336 bands of 224 positions: more than 256 work items -> the channel chunks are not split over two
+                            # workgroups (in the small cases above they are, unless LayerNorm partials or the LN prologue are
+                            # requested); 42 bands per XCD on 64 workgroup slots: still ONE band per workgroup (several:
+                            # tests/test_persistent_tiles_gpu.py)
     # round 4: more shapes whose bands cross image boundaries mid-row (added with the balanced-band experiment)
     (12, 28, 64, 128),      # 14x14 grid: 10.5 bands, every band crosses an image boundary mid-row
     (9, 56, 64, 256),       # 28x28 grid: 31.5 bands (ragged last band and row tile), two n-tiles
