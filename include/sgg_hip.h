@@ -123,6 +123,17 @@ int sgg_conv2d_nhwc_fwd_tile_stats(int Ho, int Wo, int Cin, int Cout, int KH, in
 int sgg_conv2d_nhwc_dgrad(const float* dy, const float* w_hwio, const void* w_split, float* dx, int B, int Hi, int Wi, int Cin, int Ho,
                           int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int precision, int w_split_layout,
                           const float* amax_dy, const float* amax_w, int operand_format, void* stream);
+/* Which kernel the launch with these arguments runs: its symbol as rocprofv3 prints it with the spaces removed, every defaulted
+ * template argument written out (e.g. conv_halo3_pc_kernel<true,false,true,2>), into buf (buf_len >= 96).  Same scalar arguments as
+ * sgg_conv2d_nhwc_fwd / _dgrad; the optional operands only as flags (has_w_split, has_tile_stats, has_ln: that pointer would not be
+ * NULL; the required ones and the amax words count as given).  Both run the launch's own validation and read the symbol off the very
+ * route the launch switches on, so an argument set the launch refuses is refused here in the same way (sgg_last_error), and what
+ * they report is what runs.  Pure host functions: no GPU needed, nothing launched. */
+int sgg_conv2d_nhwc_fwd_symbol(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l,
+                               int precision, int w_split_layout, int has_w_split, int has_tile_stats, int has_ln, int operand_format,
+                               char* buf, int buf_len);
+int sgg_conv2d_nhwc_dgrad_symbol(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l,
+                                 int precision, int w_split_layout, int has_w_split, int operand_format, char* buf, int buf_len);
 /* Conv2DBackpropFilter: dw (HWIO) from x and dy.  algo: 0 = automatic (halo-resident kernel where it applies), 1 = per-tap
  * kernels only (A/B measurements). */
 size_t sgg_conv2d_nhwc_wgrad_workspace_bytes(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW);

@@ -16,6 +16,7 @@
 #include "split16.h"
 #include "mma_f32.h"
 #include "conv_halo.h"
+#include <stdio.h>
 #include <stdlib.h>
 
 struct GatherClass {
@@ -726,82 +727,85 @@ __global__ void hwio_to_hwoi_kernel(const float* __restrict__ w, float* __restri
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-template <int BM, int BN, int WGM, int WGN>
-static void launch_gather(const GatherParams& p, hipStream_t st) {
-  int maxwg = 0;
-  GatherParams q = p;
-  for (int i = 0; i < q.ncls; ++i) {
-    q.cls[i].mtiles = sgg_cdiv(q.cls[i].M, BM);
-    const int nwg = q.cls[i].mtiles * (q.N / BN);
-    if (nwg > maxwg) maxwg = nwg;
-  }
-  dim3 grid(maxwg, q.ncls, 1);
-  hipLaunchKernelGGL((conv_gather_kernel<BM, BN, WGM, WGN>), grid, dim3(256), 0, st, q);
-}
-
-template <int BM, int BN, int WGM, int WGN, int BK>
-static void launch_gather3(const GatherParams& p, hipStream_t st) {
-  int maxwg = 0;
-  GatherParams q = p;
-  for (int i = 0; i < q.ncls; ++i) {
-    q.cls[i].mtiles = sgg_cdiv(q.cls[i].M, BM);
-    const int nwg = q.cls[i].mtiles * (q.N / BN);
-    if (nwg > maxwg) maxwg = nwg;
-  }
-  const unsigned src_bytes = (unsigned)((size_t)q.B * q.Hs * q.Ws * q.C * sizeof(float));
-  dim3 grid(maxwg, q.ncls, 1);
-  hipLaunchKernelGGL((conv_gather3_kernel<BM, BN, WGM, WGN, BK>), grid, dim3(256), 0, st, q, src_bytes);
-}
-
-template <int BM, int BN, int WGM, int WGN, int P, bool HALF, int BK = 32>
-static void launch_gather_bf16s(const GatherParams& p, hipStream_t st) {
-  int maxwg = 0;
-  GatherParams q = p;
-  for (int i = 0; i < q.ncls; ++i) {
-    q.cls[i].mtiles = sgg_cdiv(q.cls[i].M, BM);
-    const int nwg = q.cls[i].mtiles * (q.N / BN);
-    if (nwg > maxwg) maxwg = nwg;
-  }
-  const unsigned src_bytes = (unsigned)((size_t)q.B * q.Hs * q.Ws * q.C * sizeof(float));
-  dim3 grid(maxwg, q.ncls, 1);
-  if (q.w_split && (size_t)(q.w_bytes / 2) * P < 0x80000000ull)
-    hipLaunchKernelGGL((conv_gather_bf16s_kernel<BM, BN, WGM, WGN, P, true, HALF, BK>), grid, dim3(256), 0, st, q, src_bytes);
-  else
-    hipLaunchKernelGGL((conv_gather_bf16s_kernel<BM, BN, WGM, WGN, P, false, HALF, BK>), grid, dim3(256), 0, st, q, src_bytes);
-}
+// The route of a gather launch (conv_halo.h "routes"): which of the three kernels, its tile, and - split modes - P pieces, weights
+// from pre-split planes (WS), fp16 (HALF) or bf16 pieces, slab depth BK.
+enum { GATHER_V1, GATHER_V3, GATHER_BF16S };
+struct GatherRoute {
+  int kind;
+  int BM, BN, WGM, WGN;
+  int P;
+  bool WS, HALF;
+  int BK;
+};
 
 // precision: 0 = native f32 MFMA; 2 = scaled f16 pieces, 3 products; 3 / 6 = bf16 pieces, 3 / 6 products
-static int dispatch_gather(const GatherParams& p, hipStream_t st, int precision) {
+static GatherRoute gather_route(const GatherParams& p, int precision) {
   precision = sgg_prec_general(precision);      // (no single-piece variant of the gather kernel: modes 1 / 4 run as 2 / 3 here)
-  const bool small_ = (size_t)p.B * p.Hs * p.Ws * p.C * sizeof(float) < 0x80000000ull && p.w_bytes < 0x80000000u;
-  if (precision != 0 && small_) {
-#define SGG_GB(BM, BN, WGM, WGN)                                                        \
-  do {                                                                                  \
-    if (precision == 2) launch_gather_bf16s<BM, BN, WGM, WGN, 2, true>(p, st);          \
-    else if (precision == 3) launch_gather_bf16s<BM, BN, WGM, WGN, 2, false>(p, st);    \
-    else launch_gather_bf16s<BM, BN, WGM, WGN, 3, false>(p, st);                        \
-  } while (0)
-    // (64-deep slabs, BK = 64: 2 instead of 3 waves per SIMD, measured 3 % slower in every mode)
-    // (a 128 x 256 tile for N >= 256: 242 VGPRs, 2 waves per SIMD, measured +-3 % - not dispatched)
-    if (p.N % 128 == 0) SGG_GB(128, 128, 2, 2);
-    else if (p.N % 64 == 0) SGG_GB(256, 64, 4, 1);
-    else SGG_GB(256, 32, 4, 1);
-#undef SGG_GB
-    return SGG_OK;
-  }
-  // buffer-load path: byte offsets must stay below the out-of-range marker 2^31
+  // buffer-load paths: byte offsets must stay below the out-of-range marker 2^31
   const bool small = (size_t)p.B * p.Hs * p.Ws * p.C * sizeof(float) < 0x80000000ull && p.w_bytes < 0x80000000u;
-  if (p.N % 128 == 0 && small)
-    launch_gather3<128, 128, 2, 2, 32>(p, st);   // 64-deep slabs measured 3 % slower (2 instead of 3 waves per SIMD)
-  else if (p.N % 64 != 0 && small)
-    launch_gather3<256, 32, 4, 1, 32>(p, st);     // (N = 64: the v1 kernel measured 95 vs 89 TFLOP/s, kept below)
-  else if (p.N % 128 == 0)
-    launch_gather<128, 128, 2, 2>(p, st);
-  else if (p.N % 64 == 0)
-    launch_gather<256, 64, 4, 1>(p, st);
+  GatherRoute r;
+  r.kind = (precision != 0 && small) ? GATHER_BF16S : ((small && (p.N % 128 == 0 || p.N % 64 != 0)) ? GATHER_V3 : GATHER_V1);
+  // (64-deep slabs, BK = 64: 2 instead of 3 waves per SIMD, measured 3 % slower in every mode)
+  // (a 128 x 256 tile for N >= 256: 242 VGPRs, 2 waves per SIMD, measured +-3 % - not dispatched)
+  // (N = 64 in the f32 mode: the v1 kernel measured 95 vs 89 TFLOP/s of the v3 one)
+  r.BM = p.N % 128 == 0 ? 128 : 256;
+  r.BN = p.N % 128 == 0 ? 128 : (p.N % 64 == 0 ? 64 : 32);
+  r.WGM = r.BM == 128 ? 2 : 4;
+  r.WGN = r.BM == 128 ? 2 : 1;
+  r.P = precision == 6 ? 3 : 2;
+  r.HALF = precision == 2;
+  r.WS = p.w_split && (size_t)(p.w_bytes / 2) * r.P < 0x80000000ull;
+  r.BK = 32;
+  return r;
+}
+
+static void gather_symbol(const GatherRoute& r, char* buf, size_t len) {
+  if (r.kind == GATHER_BF16S)
+    snprintf(buf, len, "conv_gather_bf16s_kernel<%d,%d,%d,%d,%d,%s,%s,%d>", r.BM, r.BN, r.WGM, r.WGN, r.P, sgg_tf(r.WS), sgg_tf(r.HALF), r.BK);
+  else if (r.kind == GATHER_V3)
+    snprintf(buf, len, "conv_gather3_kernel<%d,%d,%d,%d,%d>", r.BM, r.BN, r.WGM, r.WGN, r.BK);
   else
-    launch_gather<256, 32, 4, 1>(p, st);
-  return SGG_OK;
+    snprintf(buf, len, "conv_gather_kernel<%d,%d,%d,%d>", r.BM, r.BN, r.WGM, r.WGN);
+}
+
+static int launch_gather(const GatherRoute& r, const GatherParams& p, hipStream_t st) {
+  int maxwg = 0;
+  GatherParams q = p;
+  for (int i = 0; i < q.ncls; ++i) {
+    q.cls[i].mtiles = sgg_cdiv(q.cls[i].M, r.BM);
+    const int nwg = q.cls[i].mtiles * (q.N / r.BN);
+    if (nwg > maxwg) maxwg = nwg;
+  }
+  const unsigned src_bytes = (unsigned)((size_t)q.B * q.Hs * q.Ws * q.C * sizeof(float));
+  const dim3 grid(maxwg, q.ncls, 1), blk(256);
+#define SGG_TILE(BM_, BN_, WGM_, WGN_) (r.BM == BM_ && r.BN == BN_ && r.WGM == WGM_ && r.WGN == WGN_)
+#define SGG_G1(BM, BN, WGM, WGN) \
+  SGG_LAUNCH_ARM(r.kind == GATHER_V1 && SGG_TILE(BM, BN, WGM, WGN), (conv_gather_kernel<BM, BN, WGM, WGN>), grid, blk, 0, st, q)
+#define SGG_G3(BM, BN, WGM, WGN)                                                                                                     \
+  SGG_LAUNCH_ARM(r.kind == GATHER_V3 && SGG_TILE(BM, BN, WGM, WGN) && r.BK == 32, (conv_gather3_kernel<BM, BN, WGM, WGN, 32>), grid, blk, 0, \
+                 st, q, src_bytes)
+#define SGG_GB(BM, BN, WGM, WGN, P_, WS_, HALF_)                                                                                     \
+  SGG_LAUNCH_ARM(r.kind == GATHER_BF16S && SGG_TILE(BM, BN, WGM, WGN) && r.P == P_ && r.WS == WS_ && r.HALF == HALF_ && r.BK == 32, \
+                 (conv_gather_bf16s_kernel<BM, BN, WGM, WGN, P_, WS_, HALF_, 32>), grid, blk, 0, st, q, src_bytes)
+#define SGG_GB_TILE(BM, BN, WGM, WGN)                                                \
+  SGG_GB(BM, BN, WGM, WGN, 2, true, true) SGG_GB(BM, BN, WGM, WGN, 2, false, true)   \
+  SGG_GB(BM, BN, WGM, WGN, 2, true, false) SGG_GB(BM, BN, WGM, WGN, 2, false, false) \
+  SGG_GB(BM, BN, WGM, WGN, 3, true, false) SGG_GB(BM, BN, WGM, WGN, 3, false, false)
+  SGG_GB_TILE(128, 128, 2, 2)
+  SGG_GB_TILE(256, 64, 4, 1)
+  SGG_GB_TILE(256, 32, 4, 1)
+  SGG_G3(128, 128, 2, 2)
+  SGG_G3(256, 32, 4, 1)
+  SGG_G1(128, 128, 2, 2)
+  SGG_G1(256, 64, 4, 1)
+  SGG_G1(256, 32, 4, 1)
+#undef SGG_GB_TILE
+#undef SGG_GB
+#undef SGG_G3
+#undef SGG_G1
+#undef SGG_TILE
+  sgg_set_error("launch_gather: no instantiation for this route");
+  return SGG_ERR_ARG;
 }
 
 // f32 [n] -> P planes of 16-bit pieces [P][n]: the operand format of conv_gather_bf16s_kernel<.., WS = true>
@@ -867,217 +871,304 @@ extern "C" int sgg_conv2d_nhwc_fwd_tile_stats(int Ho, int Wo, int Cin, int Cout,
   return (Ho * Wo / bm) * (Cout / bn);
 }
 
-// Forward. `w` is the HWIO kernel for Cin == 3 and the HWOI transpose (sgg_hwio_to_hwoi) otherwise.
-extern "C" int sgg_conv2d_nhwc_fwd(const float* x, const float* w, const void* w_split, const float* bias, float* y, int B, int Hi, int Wi,
-                                   int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l,
-                                   int precision, int w_split_layout, const float* amax_x, const float* amax_w, float* tile_stats,
-                                   const float* ln_stats, const float* ln_gamma, const float* ln_beta, int operand_format, void* stream) {
-  SGG_CHECK_ARG(x && w && bias && y, "sgg_conv2d_nhwc_fwd: null pointer");
+// ---- forward and dgrad entry points ---------------------------------------------------------------------------------------------
+// What a launch is made of: its operands (the query entry points pass `sgg_present` for those they were told are there: nothing on
+// this path reads through them) and, once validated, the family that serves it with its params and route.  sgg_conv2d_nhwc_fwd /
+// _dgrad launch the plan, sgg_conv2d_nhwc_fwd_symbol / _dgrad_symbol print its route: one decision, read twice.
+struct ConvOperands {
+  const float* src;       // forward: x; dgrad: dy
+  const float* w;
+  const void* w_split;
+  const float* bias;      // forward
+  float* out;
+  const float* amax_src;
+  const float* amax_w;
+  float* tile_stats;      // forward
+  const float* ln_stats;  // forward: LN prologue
+  const float* ln_gamma;
+  const float* ln_beta;
+};
+enum { CONV_C3, CONV_HALO, CONV_HALO_PC, CONV_S2, CONV_GATHER };
+struct ConvPlan {
+  int family;
+  const char* name;       // of the launch, for its error message
+  HaloParams h;
+  S2Params q;
+  GatherParams g;
+  HaloRoute halo;
+  HaloPcRoute pc;
+  S2Route s2;
+  GatherRoute gather;
+};
+static float sgg_present[1];
+
+// Halo family: a 3x3 stride-1 convolution over the H x W grid, C contraction channels, N output columns.  view 1 / 2: the source /
+// the output is a full-resolution tensor [B, 2H, 2W, C / 4 resp. N / 4] read / written through its space-to-depth view (conv1_3).
+static int plan_halo(ConvPlan& pl, const char* name, const ConvOperands& o, int B, int H, int W, int C, int N, int flip, int frag16, int view,
+                     int src_s16, int cu_cap, int precision) {
+  HaloParams& h = pl.h;
+  h.src = o.src; h.wfrag = o.w_split; h.bias = o.bias; h.out = o.out; h.amax_src = o.amax_src; h.amax_w = o.amax_w; h.tile_stats = o.tile_stats;
+  h.ln_stats = o.ln_stats; h.ln_gamma = o.ln_gamma; h.ln_beta = o.ln_beta;
+  h.B = B; h.H = H; h.W = W; h.C = C; h.N = N; h.bh = H / 8; h.bw = W / 8; h.nblk = B * h.bh * h.bw; h.flip = flip;
+  h.src_bytes = (unsigned)((size_t)B * H * W * C * sizeof(float));
+  h.w_bytes = (unsigned)((size_t)9 * C * N * sizeof(float));
+  h.gx = 0;
+  sgg_halo_dense_strides(h);
+  if (view == 1) {        // chunk (qy, qx): x[2a + qy][2c + qx][0..c)
+    const int c = C / 4;
+    h.in_rs = 2 * 2 * W * c; h.in_ps = 2 * c; h.in_cA = 2 * W * c; h.in_cB = c;
+    h.ln_nc = c;
+  } else if (view == 2) { // group (qy, qx) -> dx[2a + qy][2c + qx][0..c)
+    const int c = N / 4;
+    h.out_rs = 2 * 2 * W * c; h.out_ps = 2 * c; h.out_nA = 2 * W * c; h.out_nB = c;
+  }
+  h.frag16 = frag16;
+  h.src_s16 = src_s16;
+  h.cu_cap = cu_cap;
+  if (frag16) {           // w_split_layout 4: producer / consumer workgroups, K = 32 MFMA shape
+    pl.family = CONV_HALO_PC;
+    pl.pc = sgg_halo_pc_route(h, precision);
+  } else {
+    pl.family = CONV_HALO;
+    pl.halo = sgg_halo_route(h, precision);
+  }
+  pl.name = name;
+  return SGG_OK;
+}
+
+// Band family (5x5 stride 2): Ho x Wo = the half-resolution grid, C contraction channels, N output columns.
+static int plan_s2(ConvPlan& pl, const char* name, const ConvOperands& o, int dgrad, int B, int Ho, int Wo, int C, int N, int src_s16, int cu_cap,
+                   int precision) {
+  S2Params& q = pl.q;
+  q.src = o.src; q.wfrag = o.w_split; q.bias = o.bias; q.out = o.out; q.amax_src = o.amax_src; q.amax_w = o.amax_w; q.tile_stats = o.tile_stats;
+  q.ln_stats = o.ln_stats; q.ln_gamma = o.ln_gamma; q.ln_beta = o.ln_beta;
+  q.B = B; q.Ho = Ho; q.Wo = Wo; q.C = C; q.N = N; q.M = B * Ho * Wo; q.nbands = sgg_cdiv(q.M, 224); q.pitch = Wo;
+  q.src_bytes = (unsigned)((size_t)(dgrad ? 1 : 4) * q.M * C * sizeof(float));      // (forward: the full-resolution x)
+  q.w_bytes = (unsigned)((size_t)25 * C * N * sizeof(float));
+  q.gx = 0; q.ksplit = 1;
+  q.src_s16 = src_s16;
+  q.cu_cap = cu_cap;
+  pl.family = CONV_S2;
+  pl.s2 = sgg_s2_route(q, dgrad, precision);
+  pl.name = name;
+  return SGG_OK;
+}
+
+// Gather family: forward = one class over the output grid; dgrad = stride^2 parity classes of dx, each a stride-1 correlation of dy
+// with a sub-sampled kernel.  (Hi, Wi, Cin) / (Ho, Wo, Cout): the convolution's input / output side in either direction.
+static int plan_gather(ConvPlan& pl, const char* name, const ConvOperands& o, int dgrad, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout,
+                       int KH, int KW, int stride, int pad_t, int pad_l, int precision) {
+  GatherParams& p = pl.g;
+  p.src = o.src; p.wm = o.w; p.bias = o.bias; p.out = o.out; p.w_split = (precision != 0) ? o.w_split : nullptr;
+  p.amax_src = o.amax_src; p.amax_w = o.amax_w;
+  p.tile_stats = o.tile_stats;
+  p.KW = KW;
+  p.w_bytes = (unsigned)((size_t)KH * KW * Cin * Cout * sizeof(float));
+  if (!dgrad) {
+    p.hw = Ho * Wo;
+    p.B = B; p.Hs = Hi; p.Ws = Wi; p.C = Cin; p.N = Cout; p.Ho = Ho; p.Wo = Wo;
+    p.sy = stride; p.sx = stride; p.dy = 1; p.dx = 1; p.osy = 1; p.osx = 1;
+    p.ncls = 1;
+    GatherClass& c = p.cls[0];
+    c.Hm = Ho; c.Wm = Wo; c.M = B * Ho * Wo; c.nth = KH; c.ntw = KW; c.oy = -pad_t; c.ox = -pad_l;
+    c.kh0 = 0; c.kw0 = 0; c.kstep = 1; c.ooy = 0; c.oox = 0; c.mtiles = 0;
+  } else {
+    p.hw = Hi * Wi;
+    p.B = B; p.Hs = Ho; p.Ws = Wo; p.C = Cout; p.N = Cin; p.Ho = Hi; p.Wo = Wi;
+    p.sy = 1; p.sx = 1; p.dy = -1; p.dx = -1; p.osy = stride; p.osx = stride;
+    p.ncls = stride * stride;
+    for (int ph = 0; ph < stride; ++ph)
+      for (int pw = 0; pw < stride; ++pw) {
+        GatherClass& c = p.cls[ph * stride + pw];
+        const int kh0 = (ph + pad_t) % stride, kw0 = (pw + pad_l) % stride;
+        c.Hm = (Hi - ph + stride - 1) / stride;
+        c.Wm = (Wi - pw + stride - 1) / stride;
+        c.M = B * c.Hm * c.Wm;
+        c.nth = (KH - kh0 + stride - 1) / stride;
+        c.ntw = (KW - kw0 + stride - 1) / stride;
+        c.oy = (ph + pad_t - kh0) / stride;
+        c.ox = (pw + pad_l - kw0) / stride;
+        c.kh0 = kh0; c.kw0 = kw0; c.kstep = stride; c.ooy = ph; c.oox = pw; c.mtiles = 0;
+      }
+  }
+  pl.family = CONV_GATHER;
+  pl.gather = gather_route(p, precision);
+  pl.name = name;
+  return SGG_OK;
+}
+
+static int plan_launch(const ConvPlan& pl, hipStream_t st) {
+  int rc = SGG_ERR_ARG;
+  if (pl.family == CONV_HALO) rc = sgg_halo_launch(pl.halo, pl.h, st);
+  else if (pl.family == CONV_HALO_PC) rc = sgg_halo_pc_launch(pl.pc, pl.h, st);
+  else if (pl.family == CONV_S2) rc = sgg_s2_launch(pl.s2, pl.q, st);
+  else if (pl.family == CONV_GATHER) rc = launch_gather(pl.gather, pl.g, st);
+  if (rc != SGG_OK) return rc;
+  SGG_LAUNCH_CHECK(pl.name);
+  return SGG_OK;
+}
+
+static int plan_symbol(const ConvPlan& pl, char* buf, int buf_len) {
+  SGG_CHECK_ARG(buf && buf_len >= 96, "sgg_conv2d_nhwc_*_symbol: the buffer must hold at least 96 bytes");
+  if (pl.family == CONV_C3) snprintf(buf, (size_t)buf_len, "conv_c3_fwd_kernel");
+  else if (pl.family == CONV_HALO) sgg_halo_symbol(pl.halo, buf, (size_t)buf_len);
+  else if (pl.family == CONV_HALO_PC) sgg_halo_pc_symbol(pl.pc, buf, (size_t)buf_len);
+  else if (pl.family == CONV_S2) sgg_s2_symbol(pl.s2, buf, (size_t)buf_len);
+  else gather_symbol(pl.gather, buf, (size_t)buf_len);
+  return SGG_OK;
+}
+
+// Validates a forward launch and plans it.  `o.w` is the HWIO kernel for Cin == 3 and the HWOI transpose (sgg_hwio_to_hwoi) otherwise.
+static int plan_fwd(ConvPlan& pl, const ConvOperands& o, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
+                    int pad_t, int pad_l, int precision, int w_split_layout, int operand_format) {
+  SGG_CHECK_ARG(o.src && o.w && o.bias && o.out, "sgg_conv2d_nhwc_fwd: null pointer");
   // bits 8 .. 13: launch hint for the persistent kernels - occupy at most this many of an XCD's 32 CUs (0 = all; include/sgg_hip.h)
   const int cu_cap = (operand_format >> 8) & 63;
   SGG_CHECK_ARG((operand_format & ~0x3f01) == 0 && cu_cap <= 32, "sgg_conv2d_nhwc_fwd: operand_format: bit 0 = pre-split x, bits 8 .. 13 = CUs per XCD (<= 32)");
   operand_format &= 1;
   SGG_CHECK_ARG(operand_format == 0 || (operand_format == 1 && sgg_prec_half(precision) && w_split_layout >= 1 && w_split_layout <= 4 &&
-                                        !ln_stats && Cin != 3),
+                                        !o.ln_stats && Cin != 3),
                 "sgg_conv2d_nhwc_fwd: a pre-split (S16) x needs precision 1 / 2, a resident kernel (w_split_layout 1 .. 4) and no LN prologue");
-  SGG_CHECK_ARG(!ln_stats || (w_split_layout >= 1 && w_split_layout <= 4 && ln_gamma && ln_beta && Cin <= 512),
+  SGG_CHECK_ARG(!o.ln_stats || (w_split_layout >= 1 && w_split_layout <= 4 && o.ln_gamma && o.ln_beta && Cin <= 512),
                 "sgg_conv2d_nhwc_fwd: the LN prologue needs w_split_layout 1 .. 4 (resident kernels), gamma, beta and Cin <= 512");
   SGG_CHECK_ARG(precision == 0 || (precision >= 1 && precision <= 4) || precision == 6, "sgg_conv2d_nhwc_fwd: precision must be 0, 1, 2, 3, 4 or 6");
-  SGG_CHECK_ARG(!sgg_prec_half(precision) || Cin == 3 || (amax_x && amax_w), "sgg_conv2d_nhwc_fwd: precision 1 / 2 need the amax words");
-  SGG_CHECK_ARG(!ln_stats || !sgg_prec_one(precision), "sgg_conv2d_nhwc_fwd: the LN prologue exists in the two-piece modes (2, 3) only");
+  SGG_CHECK_ARG(!sgg_prec_half(precision) || Cin == 3 || (o.amax_src && o.amax_w), "sgg_conv2d_nhwc_fwd: precision 1 / 2 need the amax words");
+  SGG_CHECK_ARG(!o.ln_stats || !sgg_prec_one(precision), "sgg_conv2d_nhwc_fwd: the LN prologue exists in the two-piece modes (2, 3) only");
   SGG_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && stride >= 1 && stride <= 2, "sgg_conv2d_nhwc_fwd: bad dims");
   SGG_CHECK_ARG(Ho == (Hi + stride - 1) / stride && Wo == (Wi + stride - 1) / stride,
                 "sgg_conv2d_nhwc_fwd: Ho/Wo must be ceil(in/stride) (SAME padding)");
   SGG_CHECK_ARG((long long)B * Hi * Wi * Cin < (1LL << 31) && (long long)B * Ho * Wo * Cout < (1LL << 31),
                 "sgg_conv2d_nhwc_fwd: tensor exceeds 2^31 elements");
-  hipStream_t st = (hipStream_t)stream;
   if (Cin == 3) {
     SGG_CHECK_ARG(KH == 3 && KW == 3 && stride == 1 && Cout == 32, "sgg_conv2d_nhwc_fwd: Cin=3 path needs 3x3 s1 Cout=32");
-    const int tiles_x = sgg_cdiv(Wo, 32), tiles_y = sgg_cdiv(Ho, 8);
-    const int ntiles = B * tiles_x * tiles_y;
-    hipLaunchKernelGGL(conv_c3_fwd_kernel, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(256), 0, st, x, w, bias, y, tile_stats,
-                       Hi, Wi, pad_t, pad_l, tiles_x, tiles_y, ntiles);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_fwd(c3)");
+    pl.family = CONV_C3;
+    pl.name = "sgg_conv2d_nhwc_fwd(c3)";
     return SGG_OK;
   }
   SGG_CHECK_ARG(Cin % 32 == 0 && Cout % 32 == 0, "sgg_conv2d_nhwc_fwd: Cin and Cout must be multiples of 32 (or Cin == 3)");
   if (w_split_layout == 1 || w_split_layout == 4) {        // halo-resident 3x3 stride-1 kernels, weights in MFMA fragment order
-    SGG_CHECK_ARG(w_split && sgg_halo_applicable(KH, KW, stride, Hi, Wi, Cin, Cout, precision) && pad_t == 1 && pad_l == 1,
+    SGG_CHECK_ARG(o.w_split && sgg_halo_applicable(KH, KW, stride, Hi, Wi, Cin, Cout, precision) && pad_t == 1 && pad_l == 1,
                   "sgg_conv2d_nhwc_fwd: w_split_layout 1 / 4 needs 3x3 stride 1, H %% 8 == W %% 8 == 0, precision 2 or 3 (sgg_conv_wsplit_layout)");
     SGG_CHECK_ARG(w_split_layout != 4 || sgg_halo_pc_applicable(Cin, Cout, precision) ||
-                      (sgg_halo_pc64_applicable(Cin, Cout, precision) && (operand_format & 1) && !ln_stats),
+                      (sgg_halo_pc64_applicable(Cin, Cout, precision) && (operand_format & 1) && !o.ln_stats),
                   "sgg_conv2d_nhwc_fwd: w_split_layout 4 needs Cout %% 128 == 0, Cin %% 64 == 0, precision 2 or 3 (sgg_conv_wsplit_layout) - or "
                   "Cout %% 64 == 0 with a pre-split x in precision 2 (sgg_conv_wsplit_layout_presplit)");
-    HaloParams h;
-    h.src = x; h.wfrag = w_split; h.bias = bias; h.out = y; h.amax_src = amax_x; h.amax_w = amax_w; h.tile_stats = tile_stats;
-    h.ln_stats = ln_stats; h.ln_gamma = ln_gamma; h.ln_beta = ln_beta;
-    h.B = B; h.H = Hi; h.W = Wi; h.C = Cin; h.N = Cout; h.bh = Hi / 8; h.bw = Wi / 8; h.nblk = B * h.bh * h.bw; h.flip = 0;
-    h.src_bytes = (unsigned)((size_t)B * Hi * Wi * Cin * sizeof(float));
-    h.w_bytes = (unsigned)((size_t)9 * Cin * Cout * sizeof(float));
-    sgg_halo_dense_strides(h);
-    h.frag16 = w_split_layout == 4;
-    h.src_s16 = operand_format & 1;
-    h.cu_cap = cu_cap;
     SGG_CHECK_ARG((size_t)B * Hi * Wi * Cin * sizeof(float) < 0x80000000ull, "sgg_conv2d_nhwc_fwd: input exceeds 2 GiB");
-    sgg_halo_launch(h, precision, st);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_fwd(halo)");
-    return SGG_OK;
+    return plan_halo(pl, "sgg_conv2d_nhwc_fwd(halo)", o, B, Hi, Wi, Cin, Cout, 0, w_split_layout == 4, 0, operand_format & 1, cu_cap, precision);
   }
   if (w_split_layout == 3) {        // 5x5 stride 2 over 32 channels = 3x3 stride 1 over the space-to-depth view of x (halo-resident kernel)
-    SGG_CHECK_ARG(w_split && sgg_s2d_applicable(KH, KW, stride, Hi, Wi, Cin, Cout, precision) && pad_t == 1 && pad_l == 1,
+    SGG_CHECK_ARG(o.w_split && sgg_s2d_applicable(KH, KW, stride, Hi, Wi, Cin, Cout, precision) && pad_t == 1 && pad_l == 1,
                   "sgg_conv2d_nhwc_fwd: w_split_layout 3 needs 5x5 stride 2, 32 -> 32 channels, H %% 16 == W %% 16 == 0, precision 2 or 3 "
                   "(sgg_conv_wsplit_layout)");
     SGG_CHECK_ARG((size_t)B * Hi * Wi * Cin * sizeof(float) < 0x80000000ull, "sgg_conv2d_nhwc_fwd: input exceeds 2 GiB");
-    HaloParams h;
-    h.src = x; h.wfrag = w_split; h.bias = bias; h.out = y; h.amax_src = amax_x; h.amax_w = amax_w; h.tile_stats = tile_stats;
-    h.ln_stats = ln_stats; h.ln_gamma = ln_gamma; h.ln_beta = ln_beta;
-    h.B = B; h.H = Ho; h.W = Wo; h.C = 4 * Cin; h.N = Cout; h.bh = Ho / 8; h.bw = Wo / 8; h.nblk = B * h.bh * h.bw; h.flip = 0;
-    h.src_bytes = (unsigned)((size_t)B * Hi * Wi * Cin * sizeof(float));
-    h.w_bytes = (unsigned)((size_t)9 * 4 * Cin * Cout * sizeof(float));
-    sgg_halo_dense_strides(h);
-    h.in_rs = 2 * Wi * Cin; h.in_ps = 2 * Cin; h.in_cA = Wi * Cin; h.in_cB = Cin;     // chunk (qy, qx): x[2a + qy][2c + qx][0..32)
-    h.ln_nc = Cin;
-    h.src_s16 = operand_format & 1;
-    h.cu_cap = cu_cap;
-    sgg_halo_launch(h, precision, st);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_fwd(s2d)");
-    return SGG_OK;
+    return plan_halo(pl, "sgg_conv2d_nhwc_fwd(s2d)", o, B, Ho, Wo, 4 * Cin, Cout, 0, 0, 1, operand_format & 1, cu_cap, precision);
   }
   if (w_split_layout == 2) {        // band-resident 5x5 stride-2 kernel (conv_s2.hip), weights in MFMA fragment order (25 taps)
-    SGG_CHECK_ARG(w_split && sgg_s2_applicable(KH, KW, stride, B, Hi, Wi, Cin, Cout, precision) && pad_t == 1 && pad_l == 1,
+    SGG_CHECK_ARG(o.w_split && sgg_s2_applicable(KH, KW, stride, B, Hi, Wi, Cin, Cout, precision) && pad_t == 1 && pad_l == 1,
                   "sgg_conv2d_nhwc_fwd: w_split_layout 2 needs 5x5 stride 2 on an even grid, Cout %% 128 == 0, precision 2 or 3 "
                   "(sgg_conv_wsplit_layout)");
     SGG_CHECK_ARG((size_t)B * Hi * Wi * Cin * sizeof(float) < 0x80000000ull && (size_t)B * Ho * Wo * Cout * sizeof(float) < 0x80000000ull,
                   "sgg_conv2d_nhwc_fwd: tensor exceeds 2 GiB");
-    SGG_CHECK_ARG(!tile_stats || sgg_s2_stats_per_sample(Ho, Wo, Cout) > 0, "sgg_conv2d_nhwc_fwd: tile_stats need Ho*Wo %% 224 == 0 here");
-    S2Params q;
-    q.src = x; q.wfrag = w_split; q.bias = bias; q.out = y; q.amax_src = amax_x; q.amax_w = amax_w; q.tile_stats = tile_stats;
-    q.ln_stats = ln_stats; q.ln_gamma = ln_gamma; q.ln_beta = ln_beta;
-    q.B = B; q.Ho = Ho; q.Wo = Wo; q.C = Cin; q.N = Cout; q.M = B * Ho * Wo; q.nbands = sgg_cdiv(q.M, 224); q.pitch = Wo;
-    q.src_bytes = (unsigned)((size_t)B * Hi * Wi * Cin * sizeof(float));
-    q.w_bytes = (unsigned)((size_t)25 * Cin * Cout * sizeof(float));
-    q.src_s16 = operand_format & 1;
-    q.cu_cap = cu_cap;
-    sgg_s2_launch(q, 0, precision, st);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_fwd(s2)");
-    return SGG_OK;
+    SGG_CHECK_ARG(!o.tile_stats || sgg_s2_stats_per_sample(Ho, Wo, Cout) > 0, "sgg_conv2d_nhwc_fwd: tile_stats need Ho*Wo %% 224 == 0 here");
+    return plan_s2(pl, "sgg_conv2d_nhwc_fwd(s2)", o, 0, B, Ho, Wo, Cin, Cout, operand_format & 1, cu_cap, precision);
   }
-  GatherParams p;
-  p.src = x; p.wm = w; p.bias = bias; p.out = y; p.w_split = (precision != 0) ? w_split : nullptr;
-  p.amax_src = amax_x; p.amax_w = amax_w;
-  p.hw = Ho * Wo;
-  p.tile_stats = nullptr;
-  if (tile_stats && precision != 0) {
+  ConvOperands og = o;
+  if (precision == 0) og.tile_stats = nullptr;
+  if (og.tile_stats) {
     const int bm = (Cout % 128 == 0) ? 128 : 256;
     SGG_CHECK_ARG((Ho * Wo) % bm == 0, "sgg_conv2d_nhwc_fwd: tile_stats needs Ho*Wo %% %d == 0 (see sgg_conv2d_nhwc_fwd_tile_stats)", bm);
-    p.tile_stats = tile_stats;
   }
-  p.B = B; p.Hs = Hi; p.Ws = Wi; p.C = Cin; p.N = Cout; p.Ho = Ho; p.Wo = Wo;
-  p.sy = stride; p.sx = stride; p.dy = 1; p.dx = 1; p.osy = 1; p.osx = 1; p.KW = KW;
-  p.ncls = 1;
-  p.w_bytes = (unsigned)((size_t)KH * KW * Cin * Cout * sizeof(float));
-  GatherClass& c = p.cls[0];
-  c.Hm = Ho; c.Wm = Wo; c.M = B * Ho * Wo; c.nth = KH; c.ntw = KW; c.oy = -pad_t; c.ox = -pad_l;
-  c.kh0 = 0; c.kw0 = 0; c.kstep = 1; c.ooy = 0; c.oox = 0; c.mtiles = 0;
-  dispatch_gather(p, st, precision);
-  SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_fwd");
-  return SGG_OK;
+  return plan_gather(pl, "sgg_conv2d_nhwc_fwd", og, 0, B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l, precision);
 }
 
 // dgrad: dx[B,Hi,Wi,Cin] = conv-transpose of dy[B,Ho,Wo,Cout] with the HWIO kernel w (no bias).
-extern "C" int sgg_conv2d_nhwc_dgrad(const float* dy, const float* w, const void* w_split, float* dx, int B, int Hi, int Wi, int Cin, int Ho,
-                                     int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int precision,
-                                     int w_split_layout, const float* amax_dy, const float* amax_w, int operand_format, void* stream) {
-  SGG_CHECK_ARG(dy && w && dx, "sgg_conv2d_nhwc_dgrad: null pointer");
+static int plan_dgrad(ConvPlan& pl, const ConvOperands& o, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
+                      int pad_t, int pad_l, int precision, int w_split_layout, int operand_format) {
+  SGG_CHECK_ARG(o.src && o.w && o.out, "sgg_conv2d_nhwc_dgrad: null pointer");
   SGG_CHECK_ARG(operand_format == 0 || (operand_format == 1 && sgg_prec_half(precision) && w_split_layout >= 1 && w_split_layout <= 4),
                 "sgg_conv2d_nhwc_dgrad: a pre-split (S16) dy needs precision 1 / 2 and a resident kernel (w_split_layout 1 .. 4)");
   SGG_CHECK_ARG(precision == 0 || (precision >= 1 && precision <= 4) || precision == 6, "sgg_conv2d_nhwc_dgrad: precision must be 0, 1, 2, 3, 4 or 6");
-  SGG_CHECK_ARG(!sgg_prec_half(precision) || (amax_dy && amax_w), "sgg_conv2d_nhwc_dgrad: precision 1 / 2 need the amax words");
+  SGG_CHECK_ARG(!sgg_prec_half(precision) || (o.amax_src && o.amax_w), "sgg_conv2d_nhwc_dgrad: precision 1 / 2 need the amax words");
   SGG_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && stride >= 1 && stride <= 2, "sgg_conv2d_nhwc_dgrad: bad dims");
   SGG_CHECK_ARG(Cin % 32 == 0 && Cout % 32 == 0, "sgg_conv2d_nhwc_dgrad: Cin and Cout must be multiples of 32");
   SGG_CHECK_ARG((long long)B * Hi * Wi * Cin < (1LL << 31) && (long long)B * Ho * Wo * Cout < (1LL << 31),
                 "sgg_conv2d_nhwc_dgrad: tensor exceeds 2^31 elements");
   if (w_split_layout == 1 || w_split_layout == 4) {        // halo-resident 3x3 stride-1 kernels: dx = correlation of dy with the mirrored taps
-    SGG_CHECK_ARG(w_split && sgg_halo_applicable(KH, KW, stride, Hi, Wi, Cout, Cin, precision) && pad_t == 1 && pad_l == 1 &&
+    SGG_CHECK_ARG(o.w_split && sgg_halo_applicable(KH, KW, stride, Hi, Wi, Cout, Cin, precision) && pad_t == 1 && pad_l == 1 &&
                       Ho == Hi && Wo == Wi,
                   "sgg_conv2d_nhwc_dgrad: w_split_layout 1 / 4 needs 3x3 stride 1, H %% 8 == W %% 8 == 0, precision 2 or 3 (sgg_conv_wsplit_layout)");
     SGG_CHECK_ARG(w_split_layout != 4 || sgg_halo_pc_applicable(Cout, Cin, precision) ||
                       (sgg_halo_pc64_applicable(Cout, Cin, precision) && (operand_format & 1)),
                   "sgg_conv2d_nhwc_dgrad: w_split_layout 4 needs Cin %% 128 == 0, Cout %% 64 == 0, precision 2 or 3 (sgg_conv_wsplit_layout)");
     SGG_CHECK_ARG((size_t)B * Ho * Wo * Cout * sizeof(float) < 0x80000000ull, "sgg_conv2d_nhwc_dgrad: dy exceeds 2 GiB");
-    HaloParams h;
-    h.src = dy; h.wfrag = w_split; h.bias = nullptr; h.out = dx; h.amax_src = amax_dy; h.amax_w = amax_w; h.tile_stats = nullptr;
-    h.ln_stats = nullptr; h.ln_gamma = nullptr; h.ln_beta = nullptr;
-    h.B = B; h.H = Hi; h.W = Wi; h.C = Cout; h.N = Cin; h.bh = Hi / 8; h.bw = Wi / 8; h.nblk = B * h.bh * h.bw; h.flip = 1;
-    h.src_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * sizeof(float));
-    h.w_bytes = (unsigned)((size_t)9 * Cin * Cout * sizeof(float));
-    sgg_halo_dense_strides(h);
-    h.frag16 = w_split_layout == 4;
-    h.src_s16 = operand_format & 1;
-    sgg_halo_launch(h, precision, (hipStream_t)stream);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_dgrad(halo)");
-    return SGG_OK;
+    return plan_halo(pl, "sgg_conv2d_nhwc_dgrad(halo)", o, B, Hi, Wi, Cout, Cin, 1, w_split_layout == 4, 0, operand_format & 1, 0, precision);
   }
   if (w_split_layout == 3) {        // dx through the space-to-depth view: 3x3 correlation of dy with the mirrored 9-tap kernel, 4*Cin outputs
-    SGG_CHECK_ARG(w_split && sgg_s2d_applicable(KH, KW, stride, Hi, Wi, Cin, Cout, precision) && pad_t == 1 && pad_l == 1 &&
+    SGG_CHECK_ARG(o.w_split && sgg_s2d_applicable(KH, KW, stride, Hi, Wi, Cin, Cout, precision) && pad_t == 1 && pad_l == 1 &&
                       Hi == 2 * Ho && Wi == 2 * Wo,
                   "sgg_conv2d_nhwc_dgrad: w_split_layout 3 needs 5x5 stride 2, 32 -> 32 channels, H %% 16 == W %% 16 == 0, precision 2 or 3 "
                   "(sgg_conv_wsplit_layout)");
-    HaloParams h;
-    h.src = dy; h.wfrag = w_split; h.bias = nullptr; h.out = dx; h.amax_src = amax_dy; h.amax_w = amax_w; h.tile_stats = nullptr;
-    h.ln_stats = nullptr; h.ln_gamma = nullptr; h.ln_beta = nullptr;
-    h.B = B; h.H = Ho; h.W = Wo; h.C = Cout; h.N = 4 * Cin; h.bh = Ho / 8; h.bw = Wo / 8; h.nblk = B * h.bh * h.bw; h.flip = 1;
-    h.src_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * sizeof(float));
-    h.w_bytes = (unsigned)((size_t)9 * 4 * Cin * Cout * sizeof(float));
-    sgg_halo_dense_strides(h);
-    h.out_rs = 2 * Wi * Cin; h.out_ps = 2 * Cin; h.out_nA = Wi * Cin; h.out_nB = Cin;  // group (qy, qx) -> dx[2a + qy][2c + qx][0..32)
-    h.src_s16 = operand_format & 1;
-    sgg_halo_launch(h, precision, (hipStream_t)stream);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_dgrad(s2d)");
-    return SGG_OK;
+    return plan_halo(pl, "sgg_conv2d_nhwc_dgrad(s2d)", o, B, Ho, Wo, Cout, 4 * Cin, 1, 0, 2, operand_format & 1, 0, precision);
   }
   if (w_split_layout == 2) {        // band-resident 5x5 stride-2 kernel: the four pixel parities of dx from resident dy patches
-    SGG_CHECK_ARG(w_split && sgg_s2_applicable(KH, KW, stride, B, Hi, Wi, Cout, Cin, precision) && pad_t == 1 && pad_l == 1 &&
+    SGG_CHECK_ARG(o.w_split && sgg_s2_applicable(KH, KW, stride, B, Hi, Wi, Cout, Cin, precision) && pad_t == 1 && pad_l == 1 &&
                       Hi == 2 * Ho && Wi == 2 * Wo,
                   "sgg_conv2d_nhwc_dgrad: w_split_layout 2 needs 5x5 stride 2 on an even grid, Cin %% 128 == 0, precision 2 or 3 "
                   "(sgg_conv_wsplit_layout)");
     SGG_CHECK_ARG((size_t)B * Hi * Wi * Cin * sizeof(float) < 0x80000000ull && (size_t)B * Ho * Wo * Cout * sizeof(float) < 0x80000000ull,
                   "sgg_conv2d_nhwc_dgrad: tensor exceeds 2 GiB");
-    S2Params q;
-    q.src = dy; q.wfrag = w_split; q.bias = nullptr; q.out = dx; q.amax_src = amax_dy; q.amax_w = amax_w; q.tile_stats = nullptr;
-    q.ln_stats = nullptr; q.ln_gamma = nullptr; q.ln_beta = nullptr;
-    q.B = B; q.Ho = Ho; q.Wo = Wo; q.C = Cout; q.N = Cin; q.M = B * Ho * Wo; q.nbands = sgg_cdiv(q.M, 224); q.pitch = Wo;
-    q.src_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * sizeof(float));
-    q.w_bytes = (unsigned)((size_t)25 * Cin * Cout * sizeof(float));
-    q.src_s16 = operand_format & 1;
-    q.cu_cap = 0;
-    sgg_s2_launch(q, 1, precision, (hipStream_t)stream);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_dgrad(s2)");
+    return plan_s2(pl, "sgg_conv2d_nhwc_dgrad(s2)", o, 1, B, Ho, Wo, Cout, Cin, operand_format & 1, 0, precision);
+  }
+  return plan_gather(pl, "sgg_conv2d_nhwc_dgrad", o, 1, B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l, precision);
+}
+
+extern "C" int sgg_conv2d_nhwc_fwd(const float* x, const float* w, const void* w_split, const float* bias, float* y, int B, int Hi, int Wi,
+                                   int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l,
+                                   int precision, int w_split_layout, const float* amax_x, const float* amax_w, float* tile_stats,
+                                   const float* ln_stats, const float* ln_gamma, const float* ln_beta, int operand_format, void* stream) {
+  ConvPlan pl;
+  const int rc = plan_fwd(pl, ConvOperands{x, w, w_split, bias, y, amax_x, amax_w, tile_stats, ln_stats, ln_gamma, ln_beta}, B, Hi, Wi, Cin, Ho,
+                          Wo, Cout, KH, KW, stride, pad_t, pad_l, precision, w_split_layout, operand_format);
+  if (rc != SGG_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (pl.family == CONV_C3) {
+    const int tiles_x = sgg_cdiv(Wo, 32), tiles_y = sgg_cdiv(Ho, 8);
+    const int ntiles = B * tiles_x * tiles_y;
+    hipLaunchKernelGGL(conv_c3_fwd_kernel, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(256), 0, st, x, w, bias, y, tile_stats,
+                       Hi, Wi, pad_t, pad_l, tiles_x, tiles_y, ntiles);
+    SGG_LAUNCH_CHECK(pl.name);
     return SGG_OK;
   }
-  GatherParams p;
-  p.src = dy; p.wm = w; p.bias = nullptr; p.out = dx; p.w_split = (precision != 0) ? w_split : nullptr;
-  p.amax_src = amax_dy; p.amax_w = amax_w;
-  p.hw = Hi * Wi;
-  p.tile_stats = nullptr;
-  p.B = B; p.Hs = Ho; p.Ws = Wo; p.C = Cout; p.N = Cin; p.Ho = Hi; p.Wo = Wi;
-  p.sy = 1; p.sx = 1; p.dy = -1; p.dx = -1; p.osy = stride; p.osx = stride; p.KW = KW;
-  p.ncls = stride * stride;
-  p.w_bytes = (unsigned)((size_t)KH * KW * Cin * Cout * sizeof(float));
-  for (int ph = 0; ph < stride; ++ph)
-    for (int pw = 0; pw < stride; ++pw) {
-      GatherClass& c = p.cls[ph * stride + pw];
-      const int kh0 = (ph + pad_t) % stride, kw0 = (pw + pad_l) % stride;
-      c.Hm = (Hi - ph + stride - 1) / stride;
-      c.Wm = (Wi - pw + stride - 1) / stride;
-      c.M = B * c.Hm * c.Wm;
-      c.nth = (KH - kh0 + stride - 1) / stride;
-      c.ntw = (KW - kw0 + stride - 1) / stride;
-      c.oy = (ph + pad_t - kh0) / stride;
-      c.ox = (pw + pad_l - kw0) / stride;
-      c.kh0 = kh0; c.kw0 = kw0; c.kstep = stride; c.ooy = ph; c.oox = pw; c.mtiles = 0;
-    }
-  dispatch_gather(p, (hipStream_t)stream, precision);
-  SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_dgrad");
-  return SGG_OK;
+  return plan_launch(pl, st);
+}
+
+extern "C" int sgg_conv2d_nhwc_dgrad(const float* dy, const float* w, const void* w_split, float* dx, int B, int Hi, int Wi, int Cin, int Ho,
+                                     int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int precision,
+                                     int w_split_layout, const float* amax_dy, const float* amax_w, int operand_format, void* stream) {
+  ConvPlan pl;
+  const int rc = plan_dgrad(pl, ConvOperands{dy, w, w_split, nullptr, dx, amax_dy, amax_w, nullptr, nullptr, nullptr, nullptr}, B, Hi, Wi, Cin,
+                            Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l, precision, w_split_layout, operand_format);
+  return rc != SGG_OK ? rc : plan_launch(pl, (hipStream_t)stream);
+}
+
+// The kernel symbol the launch with these arguments runs (include/sgg_hip.h): the same validation and the same routes, no GPU.
+extern "C" int sgg_conv2d_nhwc_fwd_symbol(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t,
+                                          int pad_l, int precision, int w_split_layout, int has_w_split, int has_tile_stats, int has_ln,
+                                          int operand_format, char* buf, int buf_len) {
+  float* const on = sgg_present;
+  ConvPlan pl;
+  const int rc = plan_fwd(pl, ConvOperands{on, on, has_w_split ? on : nullptr, on, on, on, on, has_tile_stats ? on : nullptr,
+                                           has_ln ? on : nullptr, has_ln ? on : nullptr, has_ln ? on : nullptr},
+                          B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l, precision, w_split_layout, operand_format);
+  return rc != SGG_OK ? rc : plan_symbol(pl, buf, buf_len);
+}
+
+extern "C" int sgg_conv2d_nhwc_dgrad_symbol(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t,
+                                            int pad_l, int precision, int w_split_layout, int has_w_split, int operand_format, char* buf,
+                                            int buf_len) {
+  float* const on = sgg_present;
+  ConvPlan pl;
+  const int rc = plan_dgrad(pl, ConvOperands{on, on, has_w_split ? on : nullptr, nullptr, on, on, on, nullptr, nullptr, nullptr, nullptr}, B, Hi,
+                            Wi, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l, precision, w_split_layout, operand_format);
+  return rc != SGG_OK ? rc : plan_symbol(pl, buf, buf_len);
 }

@@ -21,7 +21,7 @@ struct HaloParams {
   int bh, bw, nblk;       // 8x8 blocks per image (rows, cols) and in total
   int flip;               // 0: forward (correlation); 1: dgrad (taps mirrored)
   unsigned src_bytes, w_bytes;
-  int gx;                 // workgroups per XCD (set by sgg_halo_launch)
+  int gx;                 // workgroups per XCD (set by the launchers from the route)
   // Addressing in floats (sgg_halo_dense_strides fills the NHWC defaults).  Source: grid row / pixel strides and the offset of
   // 32-channel chunk cc = (cc >> 1) * in_cA + (cc & 1) * in_cB; output: the same for 32-column group g.  A 5x5 stride-2
   // convolution over 32 channels runs here as a 3x3 stride-1 convolution over the SPACE-TO-DEPTH view of x (chunk = pixel parity
@@ -44,18 +44,60 @@ inline void sgg_halo_dense_strides(HaloParams& h) {
   h.cu_cap = 0;
 }
 
+// Workgroups per XCD of a persistent launch: XCD k of the 8 owns an eighth of the `units` (M-tiles, bands), each with `ntn` (n-tile
+// [, channel half]) items; at most `slots` workgroups are resident on its CUs; a whole number of units per trip.
+inline int sgg_persist_gx(int units, int ntn, int slots) {
+  const int per_xcd = sgg_cdiv(units, 8) * ntn;
+  return sgg_cdiv(per_xcd < slots ? per_xcd : slots, ntn) * ntn;
+}
+
+// ---- routes ------------------------------------------------------------------------------------------------------------------
+// Which kernel a launch runs is decided ONCE per family, by a pure host function (no HIP call, no pointer dereferenced: it sees only
+// which optional operands are present) that fills a route: exactly the template arguments of the instantiation plus the launch
+// geometry derived with them.  The launcher switches on the route; sgg_*_symbol prints the same route as the kernel's symbol
+// (rocprofv3's spelling with spaces removed, defaulted template arguments written out) for sgg_conv2d_nhwc_fwd_symbol / _dgrad_symbol.
+// one arm of a launcher's instantiation list: the route's values that select it, then the launch
+#define SGG_LAUNCH_ARM(selected, ...)  \
+  if (selected) {                      \
+    hipLaunchKernelGGL(__VA_ARGS__);   \
+    return SGG_OK;                     \
+  }
+inline const char* sgg_tf(bool b) { return b ? "true" : "false"; }
+struct HaloRoute {      // conv_halo3_kernel<NB, BN, WGM, WGN, HALF, true, ONECH, LNP, ONE, 1>
+  int NB, BN, WGM, WGN;
+  bool HALF, ONECH, LNP, ONE;
+  int gx;
+};
+struct HaloPcRoute {    // conv_halo3_pc_kernel<HALF, LNP, DMAP, NB>
+  bool HALF, LNP, DMAP;
+  int NB;
+  int gx;
+};
+struct S2Route {        // conv_s2_kernel<DGRAD, HALF, MT, ONE, LNP, DMAP, NW>
+  bool DGRAD, HALF;
+  int MT;
+  bool ONE, LNP, DMAP;
+  int NW;
+  int ksplit, gx;
+  bool wide;
+};
+
 // 1 if the halo kernel serves a 3x3 / stride-1 convolution over an H x W grid in this precision
 int sgg_halo_applicable(int KH, int KW, int stride, int H, int W, int C, int N, int precision);
 int sgg_s2d_applicable(int KH, int KW, int stride, int Hi, int Wi, int Cin, int Cout, int precision);
 // columns covered by one (count, mean, M2) partial of the halo kernel for N output channels
 int sgg_halo_stats_cols(int N);
-void sgg_halo_launch(const HaloParams& p, int precision, hipStream_t st);
-// producer / consumer form for 128-column tiles in the two-piece modes (conv_halo_pc.hip; weights in w_split_layout 4);
-// sgg_halo_launch dispatches to it when HaloParams::frag16 is set
+HaloRoute sgg_halo_route(const HaloParams& p, int precision);
+int sgg_halo_launch(const HaloRoute& r, const HaloParams& p, hipStream_t st);     // SGG_OK, or SGG_ERR_ARG: no such instantiation
+void sgg_halo_symbol(const HaloRoute& r, char* buf, size_t len);
+// producer / consumer form for 128-column tiles in the two-piece modes (conv_halo_pc.hip; weights in w_split_layout 4: the entry
+// points take this family when HaloParams::frag16 is set)
 int sgg_halo_pc_applicable(int C, int N, int precision);
 // its four-block form for 64-column tiles (pre-split sources only)
 int sgg_halo_pc64_applicable(int C, int N, int precision);
-void sgg_halo_pc_launch(const HaloParams& p, int precision, hipStream_t st);
+HaloPcRoute sgg_halo_pc_route(const HaloParams& p, int precision);
+int sgg_halo_pc_launch(const HaloPcRoute& r, const HaloParams& p, hipStream_t st);
+void sgg_halo_pc_symbol(const HaloPcRoute& r, char* buf, size_t len);
 
 // ---- halo-resident 3x3 stride-1 wgrad (conv_wgrad_halo.hip) ---------------------------------------------------
 struct WgradHaloPlan {
@@ -115,7 +157,7 @@ struct S2Params {
   int nbands;             // ceil(M / 224)
   int pitch;              // Wo: slots per patch row (no halo columns: edge lanes read a zero slot)
   unsigned src_bytes, w_bytes;
-  int gx;                 // workgroups per XCD (set by sgg_s2_launch)
+  int gx;                 // workgroups per XCD (set by sgg_s2_launch from the route)
   int src_s16;            // 1: src is a pre-split ("S16") tensor (split16.h)
   int ksplit;             // 1, or 2: two workgroups per (band, n-tile), each contracting half of the channel chunks and ADDING its
                           // partial into the zeroed output (a + b = b + a: still deterministic); set by sgg_s2_launch
@@ -126,4 +168,6 @@ struct S2Params {
 int sgg_s2_applicable(int KH, int KW, int stride, int B, int Hi, int Wi, int C, int N, int precision);
 // (count, mean, M2) partials per sample the forward emits, 0 if bands do not align with samples
 int sgg_s2_stats_per_sample(int Ho, int Wo, int N);
-void sgg_s2_launch(const S2Params& p, int dgrad, int precision, hipStream_t st);
+S2Route sgg_s2_route(const S2Params& p, int dgrad, int precision);
+int sgg_s2_launch(const S2Route& r, const S2Params& p, hipStream_t st);
+void sgg_s2_symbol(const S2Route& r, char* buf, size_t len);

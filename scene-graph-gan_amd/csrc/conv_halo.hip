@@ -17,6 +17,7 @@
 #include "split16.h"
 #include "conv_halo.h"
 #include <type_traits>
+#include <stdio.h>
 #include <stdlib.h>
 
 constexpr int SGG_HALO_DB_MAX = 65536;   // two patch buffers when they fit in this many bytes of LDS (a gfx950 workgroup may use up to 160 KB; measured: see DESIGN.md)
@@ -492,42 +493,50 @@ int sgg_halo_applicable(int KH, int KW, int stride, int H, int W, int C, int N, 
 // slower.
 int sgg_halo_stats_cols(int N) { return N % 128 == 0 ? 64 : 32; }
 
-void sgg_halo_launch(const HaloParams& p_, int precision, hipStream_t st) {
-  if (p_.frag16) {       // w_split_layout 4 (128-column tiles, two-piece modes): producer / consumer workgroups, K = 32 MFMA shape
-    sgg_halo_pc_launch(p_, precision, st);
-    return;
-  }
-  HaloParams p = p_;
-  const bool half = sgg_prec_half(precision), one = sgg_prec_one(precision);   // (the LN prologue exists in the two-piece modes only: callers check)
-#define SGG_HALO(NB, BN, WGM, WGN)                                                                           \
-  do {                                                                                                       \
-    const int mtiles = sgg_cdiv(p.nblk, NB), ntn = p.N / BN;                                                 \
-    int per_xcd = sgg_cdiv(mtiles, 8) * ntn;       /* (tile, n-tile) pairs an XCD owns */                    \
-    const int cap = sgg_persist_cus(p.cu_cap) * 8 / (WGM * WGN);   /* eight resident waves on each of its (32) CUs */   \
-    int gx = per_xcd < cap ? per_xcd : cap;                                                                  \
-    gx = sgg_cdiv(gx, ntn) * ntn;                                                                            \
-    p.gx = gx;                                                                                               \
-    const dim3 grid((unsigned)(8 * gx));                                                                     \
-    const dim3 blk(64 * WGM * WGN);                                                                          \
-    if (one) {                                                                                                                          \
-      if (half && p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, true, false, true, 1>), grid, blk, 0, st, p);   \
-      else if (half) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, false, false, true, 1>), grid, blk, 0, st, p);      \
-      else if (p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, true, false, true, 1>), grid, blk, 0, st, p); \
-      else hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, false, false, true, 1>), grid, blk, 0, st, p);               \
-    } else if (p.ln_stats) {                                                                                                            \
-      if (half && p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, true, true, false, 1>), grid, blk, 0, st, p);   \
-      else if (half) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, false, true, false, 1>), grid, blk, 0, st, p);      \
-      else if (p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, true, true, false, 1>), grid, blk, 0, st, p); \
-      else hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, false, true, false, 1>), grid, blk, 0, st, p);               \
-    } else if (half && p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, true, false, false, 1>), grid, blk, 0, st, p); \
-    else if (half) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, true, true, false, false, false, 1>), grid, blk, 0, st, p);       \
-    else if (p.C == 32) hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, true, false, false, 1>), grid, blk, 0, st, p);  \
-    else hipLaunchKernelGGL((conv_halo3_kernel<NB, BN, WGM, WGN, false, true, false, false, false, 1>), grid, blk, 0, st, p);                \
-  } while (0)
-  if (p.N % 128 == 0) SGG_HALO(2, 128, 2, 2);
-  else if (p.N % 64 == 0) SGG_HALO(2, 64, 2, 2);
-  else SGG_HALO(2, 32, 2, 1);
+HaloRoute sgg_halo_route(const HaloParams& p, int precision) {
+  HaloRoute r;
+  r.NB = 2;
+  r.BN = p.N % 128 == 0 ? 128 : (p.N % 64 == 0 ? 64 : 32);
+  r.WGM = 2;
+  r.WGN = r.BN == 32 ? 1 : 2;
+  r.HALF = sgg_prec_half(precision);
+  r.ONECH = p.C == 32;
+  r.ONE = sgg_prec_one(precision);
+  r.LNP = !r.ONE && p.ln_stats;       // (the LN prologue exists in the two-piece modes only: the entry points check)
+  // eight resident waves on each of an XCD's (32) CUs
+  r.gx = sgg_persist_gx(sgg_cdiv(p.nblk, r.NB), p.N / r.BN, sgg_persist_cus(p.cu_cap) * 8 / (r.WGM * r.WGN));
+  return r;
+}
+
+void sgg_halo_symbol(const HaloRoute& r, char* buf, size_t len) {
+  // (sixth argument: patch prefetch, always true; last: blocks per wave, always 1)
+  snprintf(buf, len, "conv_halo3_kernel<%d,%d,%d,%d,%s,true,%s,%s,%s,1>", r.NB, r.BN, r.WGM, r.WGN, sgg_tf(r.HALF), sgg_tf(r.ONECH), sgg_tf(r.LNP),
+           sgg_tf(r.ONE));
+}
+
+// the instantiations: per tile shape HALF x ONECH, plain / with the LN prologue / single-piece
+template <int NB, int BN, int WGM, int WGN>
+static int halo_launch_tile(const HaloRoute& r, const HaloParams& p, hipStream_t st) {
+  const dim3 grid((unsigned)(8 * r.gx)), blk(64 * WGM * WGN);
+#define SGG_HALO(HALF_, ONECH_, LNP_, ONE_)                                                      \
+  SGG_LAUNCH_ARM(r.HALF == HALF_ && r.ONECH == ONECH_ && r.LNP == LNP_ && r.ONE == ONE_,        \
+                 (conv_halo3_kernel<NB, BN, WGM, WGN, HALF_, true, ONECH_, LNP_, ONE_, 1>), grid, blk, 0, st, p)
+  SGG_HALO(false, false, false, false) SGG_HALO(false, true, false, false) SGG_HALO(true, false, false, false) SGG_HALO(true, true, false, false)
+  SGG_HALO(false, false, true, false) SGG_HALO(false, true, true, false) SGG_HALO(true, false, true, false) SGG_HALO(true, true, true, false)
+  SGG_HALO(false, false, false, true) SGG_HALO(false, true, false, true) SGG_HALO(true, false, false, true) SGG_HALO(true, true, false, true)
 #undef SGG_HALO
+  return SGG_ERR_ARG;
+}
+
+int sgg_halo_launch(const HaloRoute& r, const HaloParams& p_, hipStream_t st) {
+  HaloParams p = p_;
+  p.gx = r.gx;
+  int rc = SGG_ERR_ARG;
+  if (r.NB == 2 && r.BN == 128 && r.WGM == 2 && r.WGN == 2) rc = halo_launch_tile<2, 128, 2, 2>(r, p, st);
+  else if (r.NB == 2 && r.BN == 64 && r.WGM == 2 && r.WGN == 2) rc = halo_launch_tile<2, 64, 2, 2>(r, p, st);
+  else if (r.NB == 2 && r.BN == 32 && r.WGM == 2 && r.WGN == 1) rc = halo_launch_tile<2, 32, 2, 1>(r, p, st);
+  if (rc != SGG_OK) sgg_set_error("sgg_halo_launch: no instantiation for this route");
+  return rc;
 }
 
 // Which operand format sgg_conv2d_nhwc_fwd / _dgrad want for the pre-split weights of this convolution:

@@ -22,6 +22,7 @@
 #include "split16.h"
 #include "conv_halo.h"
 #include <type_traits>
+#include <stdio.h>
 
 #define PC_PITCH 12
 #define PC_BLKB (10 * PC_PITCH * 64)      // bytes of one plane of one block's patch
@@ -612,31 +613,34 @@ int sgg_halo_pc64_applicable(int C, int N, int precision) {
   return precision == 2 && N % 64 == 0 && N % 128 != 0 && C % 64 == 0 && C <= 512;
 }
 
-void sgg_halo_pc_launch(const HaloParams& p_, int precision, hipStream_t st) {
+HaloPcRoute sgg_halo_pc_route(const HaloParams& p, int precision) {
+  HaloPcRoute r;
+  r.NB = p.N % 128 != 0 ? 4 : 2;               // (four blocks: callers checked sgg_halo_pc64_applicable and the pre-split source)
+  r.HALF = r.NB == 4 || precision == 2;
+  r.LNP = r.NB == 2 && p.ln_stats;
+  r.DMAP = r.NB == 4 || (p.src_s16 && r.HALF && !r.LNP);      // pre-split source: the patch by LDS-DMA too
+  // one workgroup on each of an XCD's (32) CUs
+  r.gx = sgg_persist_gx(sgg_cdiv(p.nblk, r.NB), p.N / (256 / r.NB), sgg_persist_cus(p.cu_cap));
+  return r;
+}
+
+void sgg_halo_pc_symbol(const HaloPcRoute& r, char* buf, size_t len) {
+  snprintf(buf, len, "conv_halo3_pc_kernel<%s,%s,%s,%d>", sgg_tf(r.HALF), sgg_tf(r.LNP), sgg_tf(r.DMAP), r.NB);
+}
+
+int sgg_halo_pc_launch(const HaloPcRoute& r, const HaloParams& p_, hipStream_t st) {
   HaloParams p = p_;
-  const bool four = p.N % 128 != 0;            // (callers checked sgg_halo_pc64_applicable and the pre-split source)
-  const int nb = four ? 4 : 2, bn = 256 / nb;
-  const int mtiles = sgg_cdiv(p.nblk, nb), ntn = p.N / bn;
-  int per_xcd = sgg_cdiv(mtiles, 8) * ntn;       // (tile, n-tile) pairs an XCD owns
-  const int cus = sgg_persist_cus(p.cu_cap);
-  int gx = per_xcd < cus ? per_xcd : cus;          // one workgroup on each of its (32) CUs
-  gx = sgg_cdiv(gx, ntn) * ntn;
-  p.gx = gx;
-  const dim3 grid((unsigned)(8 * gx)), blk(512);
-  const bool half = precision == 2;
-  if (four) {
-    hipLaunchKernelGGL((conv_halo3_pc_kernel<true, false, true, 4>), grid, blk, 0, st, p);
-    return;
-  }
-  if (p.src_s16 && half && !p.ln_stats) {      // pre-split source: the patch by LDS-DMA too
-    hipLaunchKernelGGL((conv_halo3_pc_kernel<true, false, true>), grid, blk, 0, st, p);
-    return;
-  }
-  if (p.ln_stats) {
-    if (half) hipLaunchKernelGGL((conv_halo3_pc_kernel<true, true>), grid, blk, 0, st, p);
-    else hipLaunchKernelGGL((conv_halo3_pc_kernel<false, true>), grid, blk, 0, st, p);
-  } else {
-    if (half) hipLaunchKernelGGL((conv_halo3_pc_kernel<true, false>), grid, blk, 0, st, p);
-    else hipLaunchKernelGGL((conv_halo3_pc_kernel<false, false>), grid, blk, 0, st, p);
-  }
+  p.gx = r.gx;
+  const dim3 grid((unsigned)(8 * r.gx)), blk(512);
+#define SGG_PC(HALF_, LNP_, DMAP_, NB_) \
+  SGG_LAUNCH_ARM(r.HALF == HALF_ && r.LNP == LNP_ && r.DMAP == DMAP_ && r.NB == NB_, (conv_halo3_pc_kernel<HALF_, LNP_, DMAP_, NB_>), grid, blk, 0, st, p)
+  SGG_PC(true, false, true, 4)
+  SGG_PC(true, false, true, 2)
+  SGG_PC(true, true, false, 2)
+  SGG_PC(false, true, false, 2)
+  SGG_PC(true, false, false, 2)
+  SGG_PC(false, false, false, 2)
+#undef SGG_PC
+  sgg_set_error("sgg_halo_pc_launch: no instantiation for this route");
+  return SGG_ERR_ARG;
 }

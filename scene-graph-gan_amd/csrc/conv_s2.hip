@@ -27,6 +27,7 @@
 // SQ_LDS_BANK_CONFLICT); the lanes whose tap falls off the left / right image edge read a reserved all-zero slot instead.
 #include "split16.h"
 #include "conv_halo.h"
+#include <stdio.h>
 #include <type_traits>
 
 #define S2_BAND 224                   // positions per band (what LayerNorm partials are defined on)
@@ -533,56 +534,59 @@ int sgg_s2_applicable(int KH, int KW, int stride, int B, int Hi, int Wi, int C, 
 
 int sgg_s2_stats_per_sample(int Ho, int Wo, int N) { return ((Ho * Wo) % S2_BAND == 0) ? (Ho * Wo / S2_BAND) * (N / 32) : 0; }
 
-void sgg_s2_launch(const S2Params& p_, int dgrad, int precision, hipStream_t st) {
-  S2Params p = p_;
-  const bool half = sgg_prec_half(precision), one = sgg_prec_one(precision);
-  const bool dmap = p.src_s16 && half && !one && !p.ln_stats;      // pre-split source: the patch by LDS-DMA
+S2Route sgg_s2_route(const S2Params& p, int dgrad, int precision) {
+  S2Route r;
+  r.DGRAD = dgrad;
+  r.HALF = sgg_prec_half(precision);
+  r.MT = S2_BAND / 32;
+  r.LNP = p.ln_stats;       // LN prologue: forward, two-piece modes, 224-position bands (the entry point checks)
+  r.DMAP = p.src_s16 && r.HALF && !sgg_prec_one(precision) && !r.LNP;      // pre-split source: the patch by LDS-DMA
+  r.ONE = sgg_prec_one(precision) && !r.LNP;
+  const int nbands = sgg_cdiv(p.M, S2_BAND);
   // 256-column workgroups (eight waves, one workgroup per CU) where the layer has 256+ output columns and the patch comes by DMA
   // (not where that leaves fewer work items than half the CUs - `downsampled` at batch 64: measured equal forward, 7 % slower dgrad)
-  const bool wide = dmap && p.N % 256 == 0 && sgg_cdiv(p.M, S2_BAND) * (p.N / 256) > S2_SMALL_ITEMS / 2;
-  const int bn = wide ? 256 : S2_BN;
+  r.wide = r.DMAP && p.N % 256 == 0 && nbands * (p.N / 256) > S2_SMALL_ITEMS / 2;
+  r.NW = r.wide ? 8 : 4;
+  const int bn = r.wide ? 256 : S2_BN;
   // where the bands give fewer work items than CUs (and no LayerNorm partials are asked for), the channel chunks are split over
   // two workgroups
-  const bool small_ = !wide && !p.tile_stats && !p.ln_stats && sgg_cdiv(p.M, S2_BAND) * (p.N / bn) <= S2_SMALL_ITEMS;
-  p.ksplit = (small_ && (p.C >> 4) % 4 == 0) ? 2 : 1;
-  if (p.ksplit > 1)
-    (void)hipMemsetAsync(p.out, 0, (size_t)(dgrad ? 4 : 1) * p.M * p.N * sizeof(float), st);
-  const int ntn = (p.N / bn) * p.ksplit;
+  const bool small_ = !r.wide && !p.tile_stats && !p.ln_stats && nbands * (p.N / bn) <= S2_SMALL_ITEMS;
+  r.ksplit = (small_ && (p.C >> 4) % 4 == 0) ? 2 : 1;
+  // resident workgroups per XCD (32 CUs): two of four waves, or one of eight; items = (band, n-tile, channel half)
+  r.gx = sgg_persist_gx(nbands, (p.N / bn) * r.ksplit, (r.wide ? 1 : 2) * sgg_persist_cus(p.cu_cap));
+  return r;
+}
+
+void sgg_s2_symbol(const S2Route& r, char* buf, size_t len) {
+  snprintf(buf, len, "conv_s2_kernel<%s,%s,%d,%s,%s,%s,%d>", sgg_tf(r.DGRAD), sgg_tf(r.HALF), r.MT, sgg_tf(r.ONE), sgg_tf(r.LNP), sgg_tf(r.DMAP), r.NW);
+}
+
+int sgg_s2_launch(const S2Route& r, const S2Params& p_, hipStream_t st) {
+  S2Params p = p_;
+  p.ksplit = r.ksplit;
   p.nbands = sgg_cdiv(p.M, S2_BAND);
-  const int slots = (wide ? 1 : 2) * sgg_persist_cus(p.cu_cap);      // resident workgroups per XCD (32 CUs)
-  int per_xcd = sgg_cdiv(p.nbands, 8) * ntn;       // (band, n-tile, channel half) items an XCD owns
-  int gx = per_xcd < slots ? per_xcd : slots;
-  gx = sgg_cdiv(gx, ntn) * ntn;
-  p.gx = gx;
-  const dim3 grid((unsigned)(8 * gx));
-  if (wide) {
-    if (dgrad) hipLaunchKernelGGL((conv_s2_kernel<true, true, 7, false, false, true, 8>), grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((conv_s2_kernel<false, true, 7, false, false, true, 8>), grid, dim3(512), 0, st, p);
-    return;
-  }
-  if (dmap) {
-    if (dgrad) hipLaunchKernelGGL((conv_s2_kernel<true, true, 7, false, false, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv_s2_kernel<false, true, 7, false, false, true>), grid, dim3(256), 0, st, p);
-    return;
-  }
-  if (p.ln_stats) {       // LN prologue: forward, two-piece modes, 224-position bands (host checks in sgg_conv2d_nhwc_fwd)
-    if (half) hipLaunchKernelGGL((conv_s2_kernel<false, true, 7, false, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv_s2_kernel<false, false, 7, false, true>), grid, dim3(256), 0, st, p);
-    return;
-  }
-  if (one) {
-    if (dgrad) {
-      if (half) hipLaunchKernelGGL((conv_s2_kernel<true, true, 7, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((conv_s2_kernel<true, false, 7, true>), grid, dim3(256), 0, st, p);
-    } else {
-      if (half) hipLaunchKernelGGL((conv_s2_kernel<false, true, 7, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((conv_s2_kernel<false, false, 7, true>), grid, dim3(256), 0, st, p);
-    }
-  } else if (dgrad) {
-    if (half) hipLaunchKernelGGL((conv_s2_kernel<true, true, 7>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv_s2_kernel<true, false, 7>), grid, dim3(256), 0, st, p);
-  } else {
-    if (half) hipLaunchKernelGGL((conv_s2_kernel<false, true, 7>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv_s2_kernel<false, false, 7>), grid, dim3(256), 0, st, p);
-  }
+  p.gx = r.gx;
+  if (p.ksplit > 1)
+    (void)hipMemsetAsync(p.out, 0, (size_t)(r.DGRAD ? 4 : 1) * p.M * p.N * sizeof(float), st);
+  const dim3 grid((unsigned)(8 * r.gx));
+#define SGG_S2(DGRAD_, HALF_, ONE_, LNP_, DMAP_, NW_)                                                                                        \
+  SGG_LAUNCH_ARM(r.DGRAD == DGRAD_ && r.HALF == HALF_ && r.MT == 7 && r.ONE == ONE_ && r.LNP == LNP_ && r.DMAP == DMAP_ && r.NW == NW_, \
+                 (conv_s2_kernel<DGRAD_, HALF_, 7, ONE_, LNP_, DMAP_, NW_>), grid, dim3(64 * NW_), 0, st, p)
+  SGG_S2(true, true, false, false, true, 8)     // pre-split source, 256-column workgroups
+  SGG_S2(false, true, false, false, true, 8)
+  SGG_S2(true, true, false, false, true, 4)     // pre-split source
+  SGG_S2(false, true, false, false, true, 4)
+  SGG_S2(false, true, false, true, false, 4)    // LN prologue
+  SGG_S2(false, false, false, true, false, 4)
+  SGG_S2(true, true, true, false, false, 4)     // single-piece modes
+  SGG_S2(true, false, true, false, false, 4)
+  SGG_S2(false, true, true, false, false, 4)
+  SGG_S2(false, false, true, false, false, 4)
+  SGG_S2(true, true, false, false, false, 4)    // two-piece modes
+  SGG_S2(true, false, false, false, false, 4)
+  SGG_S2(false, true, false, false, false, 4)
+  SGG_S2(false, false, false, false, false, 4)
+#undef SGG_S2
+  sgg_set_error("sgg_s2_launch: no instantiation for this route");
+  return SGG_ERR_ARG;
 }

@@ -40,6 +40,8 @@ SIGNATURES = {
     "sgg_conv2d_nhwc_fwd_tile_stats": (_i, [_i] * 9),
     "sgg_presplit16": (_i, [_vp, _vp, _ll, _vp, _vp]),
     "sgg_conv2d_nhwc_dgrad": (_i, [_vp, _vp, _vp, _vp] + [_i] * 14 + [_vp, _vp, _i, _vp]),
+    "sgg_conv2d_nhwc_fwd_symbol": (_i, [_i] * 18 + [c_char_p, _i]),
+    "sgg_conv2d_nhwc_dgrad_symbol": (_i, [_i] * 16 + [c_char_p, _i]),
     "sgg_conv2d_nhwc_wgrad_workspace_bytes": (_sz, [_i] * 9),
     "sgg_conv2d_nhwc_wgrad": (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "sgg_conv2d_nhwc_wgrad_resident": (_i, [_i] * 9),
@@ -267,17 +269,6 @@ class HipKernels:
         self.timing.append((symbol, flops, nbytes, e0, e1))
         return r
 
-    def gather_symbol(self, n_out, presplit=False):
-        """Kernel symbol (as rocprofv3 prints it, spaces removed) that csrc/conv_gather.hip: dispatch_gather picks."""
-        if self.conv_precision:
-            tile = "128,128,2,2" if n_out % 128 == 0 else ("256,64,4,1" if n_out % 64 == 0 else "256,32,4,1")
-            return "conv_gather_bf16s_kernel<%s,%d,%s,%s,32>" % (tile, 3 if self.conv_precision == 6 else 2,
-                                                                "true" if presplit else "false",
-                                                                "true" if self.conv_precision in (1, 2) else "false")
-        if n_out % 128 == 0:
-            return "conv_gather3_kernel<128,128,2,2,32>"
-        return "conv_gather_kernel<256,64,4,1>" if n_out % 64 == 0 else "conv_gather3_kernel<256,32,4,1,32>"
-
     # -- plumbing ------------------------------------------------------------------------------------
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -417,46 +408,12 @@ class HipKernels:
         return self.lib.sgg_conv2d_nhwc_fwd_tile_stats(y_shape[1], y_shape[2], cin, y_shape[3], k, k, stride, self.conv_precision,
                                                        layout)
 
-    def halo_pc_symbol(self, lnp=False, presplit=False, n_out=128):
-        """Kernel symbol of the producer / consumer 3x3 kernel (csrc/conv_halo_pc.hip; w_split_layout 4); presplit: the source is a
-        pre-split tensor, the patch is staged by LDS-DMA (third template argument); fourth: 8x8 blocks per workgroup tile (2 blocks x
-        128 columns, or 4 x 64 for the 64-column launches)."""
-        dma = presplit and not lnp and self.conv_precision == 2
-        return "conv_halo3_pc_kernel<%s,%s,%s,%d>" % ("true" if self.conv_precision == 2 else "false", "true" if lnp else "false",
-                                                      "true" if dma else "false", 2 if n_out % 128 == 0 else 4)
-
-    def halo_symbol(self, n_out, n_in, lnp=False):
-        """Kernel symbol (as rocprofv3 prints it, spaces removed) that csrc/conv_halo.hip: sgg_halo_launch picks (default build)."""
-        tile = "2,128,2,2" if n_out % 128 == 0 else ("2,64,2,2" if n_out % 64 == 0 else "2,32,2,1")
-        # (sixth argument: patch prefetch, always true; last: blocks per wave, always 1 - csrc/conv_halo.hip)
-        return "conv_halo3_kernel<%s,%s,%s,%s,%s,%s,1>" % (tile, "true" if self.conv_precision in (1, 2) else "false", "true",
-                                                           "true" if n_in == 32 else "false", "true" if lnp else "false",
-                                                           "true" if self.conv_precision in (1, 4) else "false")
-
-    def s2_symbol(self, dgrad, m_positions=1 << 30, n_out=128, stats=True, lnp=False, presplit=False):
-        """(csrc/conv_s2.hip: 224-position bands; with at most 256 work items the channel chunks are split over two workgroups);
-        presplit: the source is a pre-split tensor, the patch is staged by LDS-DMA (sixth template argument) - by eight-wave
-        workgroups that own 256 output columns where the layer has that many (seventh)"""
-        mt = 7
-        dma = presplit and not lnp and self.conv_precision == 2
-        return "conv_s2_kernel<%s,%s,%d,%s,%s,%s,%d>" % ("true" if dgrad else "false", "true" if self.conv_precision in (1, 2) else "false", mt,
-                                                         "true" if self.conv_precision in (1, 4) else "false", "true" if lnp else "false",
-                                                         "true" if dma else "false",
-                                                         8 if dma and n_out % 256 == 0 and -(-m_positions // 224) * (n_out // 256) > 128 else 4)
-
-    def conv_symbol(self, dgrad, layout, n_out, n_in, m_positions, split, stats=False, lnp=False, presplit=False):
-        """Kernel symbol of a forward (dgrad False) or dgrad launch with this w_split_layout; n_out / n_in: the channels the launch
-        produces / contracts over (dgrad: Cin / Cout of the layer); split: pre-split weights were passed; stats, lnp, presplit: the
-        launch emits tile statistics / applies the LN prologue / reads a pre-split source."""
-        if layout == 4:
-            return self.halo_pc_symbol(lnp, presplit, n_out)
-        if layout == 1:
-            return self.halo_symbol(n_out, n_in, lnp)
-        if layout == 3:         # conv1_3 through the space-to-depth view: four times the channels on its full-resolution side
-            return self.halo_symbol(4 * n_out, n_in, lnp) if dgrad else self.halo_symbol(n_out, 4 * n_in, lnp)
-        if layout == 2:
-            return self.s2_symbol(dgrad, m_positions, n_out, stats, lnp, presplit)
-        return self.gather_symbol(n_out, split)
+    def _conv_symbol(self, query, *args):
+        """The kernel symbol of a forward / dgrad launch, as the library's own routing reports it (sgg_conv2d_nhwc_fwd_symbol /
+        _dgrad_symbol: the launch's validation and route, scalars only).  Asked only while kernel timing is on."""
+        buf = ctypes.create_string_buffer(128)
+        self._check(getattr(self.lib, query)(*args, buf, len(buf)), query)
+        return buf.value.decode()
 
     def conv_fwd(self, x, w_hwio, w_fwd, bias, y, stride, w_split=None, amax_x=None, amax_w=None, tile_stats=None, w_split_layout=0,
                  ln=None, x_s16=False, cu_cap=0):
@@ -471,8 +428,9 @@ class HipKernels:
         d = self._conv_dims(x.shape, w_hwio.shape, stride)
         assert tuple(y.shape) == (d[0], d[4], d[5], d[6]) and x.is_contiguous() and y.is_contiguous()
         flops = 2.0 * d[0] * d[4] * d[5] * d[6] * d[7] * d[8] * d[3]
-        sym = "conv_c3_fwd_kernel" if d[3] == 3 else self.conv_symbol(False, w_split_layout, d[6], d[3], d[0] * d[4] * d[5], w_split is not None,
-                                                                      tile_stats is not None, ln is not None, x_s16)
+        fmt = int(bool(x_s16)) | ((int(cu_cap) & 63) << 8)
+        sym = "" if self.timing is None else self._conv_symbol("sgg_conv2d_nhwc_fwd_symbol", *d, self.conv_precision, w_split_layout,
+                                                               w_split is not None, tile_stats is not None, ln is not None, fmt)
         nb = 0.0
         if d[3] != 3:
             amax_x, amax_w = self._amax_or_compute(x, amax_x, 0), self._amax_or_compute(w_fwd, amax_w, 1)
@@ -480,7 +438,7 @@ class HipKernels:
             nb = 4.0 * (x.numel() + y.numel())      # conv1_1 (K = 27) is HBM-bound: the image read once, y written once
         self._check(self._timed(sym, flops, lambda: self.lib.sgg_conv2d_nhwc_fwd(
             _p(x), _p(w_fwd), _p(w_split), _p(bias), _p(y), *d, self.conv_precision, w_split_layout, _p(amax_x), _p(amax_w),
-            _p(tile_stats), _p(ln_s), _p(ln_g), _p(ln_b), int(bool(x_s16)) | ((int(cu_cap) & 63) << 8), self._stream()), nb),
+            _p(tile_stats), _p(ln_s), _p(ln_g), _p(ln_b), fmt, self._stream()), nb),
             "sgg_conv2d_nhwc_fwd")
 
     def conv_dgrad(self, dy, w_hwio, dx, stride, w_split=None, amax_dy=None, amax_w=None, w_split_layout=0, dy_s16=False):
@@ -490,7 +448,8 @@ class HipKernels:
         assert tuple(dy.shape) == (d[0], d[4], d[5], d[6]) and dy.is_contiguous() and dx.is_contiguous()
         flops = 2.0 * d[0] * d[4] * d[5] * d[6] * d[7] * d[8] * d[3]
         amax_dy, amax_w = self._amax_or_compute(dy, amax_dy, 0), self._amax_or_compute(w_hwio, amax_w, 1)
-        sym = self.conv_symbol(True, w_split_layout, d[3], d[6], d[0] * d[4] * d[5], w_split is not None, presplit=dy_s16)
+        sym = "" if self.timing is None else self._conv_symbol("sgg_conv2d_nhwc_dgrad_symbol", *d, self.conv_precision, w_split_layout,
+                                                               w_split is not None, int(bool(dy_s16)))
         self._check(self._timed(sym, flops, lambda: self.lib.sgg_conv2d_nhwc_dgrad(
             _p(dy), _p(w_hwio), _p(w_split), _p(dx), *d, self.conv_precision, w_split_layout, _p(amax_dy), _p(amax_w),
             int(bool(dy_s16)), self._stream())), "sgg_conv2d_nhwc_dgrad")

@@ -4,13 +4,14 @@ The 3x3 halo-resident kernel, its producer / consumer forms and the band-residen
 owns a contiguous eighth of the work units - M-tiles of NB 8x8 blocks, or bands of 224 output positions - and its `gx` workgroups
 walk that range with `for (unit = begin; unit < end; unit += tstride)`.  This module mirrors, line by line,
 
-  * csrc/conv_halo.hip     sgg_halo_launch (macro SGG_HALO: NB = 2; N % 128 / N % 64 / N % 32 tilings on 4 / 4 / 2 waves,
-                           cap = cus * 8 / (WGM * WGN)) and the range arithmetic at the head of conv_halo3_kernel;
-  * csrc/conv_halo_pc.hip  sgg_halo_pc_launch (two blocks x 128 columns, or four blocks x 64 columns where N % 128 != 0; cap = cus)
+  * csrc/conv_halo.hip     sgg_halo_route (NB = 2; N % 128 / N % 64 / N % 32 tilings on 4 / 4 / 2 waves,
+                           slots = cus * 8 / (WGM * WGN)) and the range arithmetic at the head of conv_halo3_kernel;
+  * csrc/conv_halo_pc.hip  sgg_halo_pc_route (two blocks x 128 columns, or four blocks x 64 columns where N % 128 != 0; slots = cus)
                            and the head of conv_halo3_pc_kernel;
-  * csrc/conv_s2.hip       sgg_s2_launch (`wide`, `small_` / ksplit, slots = (wide ? 1 : 2) * cus, ntn = (N / bn) * ksplit) and the
+  * csrc/conv_s2.hip       sgg_s2_route (`wide`, `small_` / ksplit, slots = (wide ? 1 : 2) * cus, ntn = (N / bn) * ksplit) and the
                            head of conv_s2_kernel;
-  * csrc/conv_halo.h       sgg_persist_cus (cu_cap 1 .. 31 caps the CUs of an XCD, anything else means all 32);
+  * csrc/conv_halo.h       sgg_persist_gx (workgroups per XCD from units, ntn and slots: _walk below), sgg_persist_cus (cu_cap
+                           1 .. 31 caps the CUs of an XCD, anything else means all 32);
   * csrc/conv_gather.hip   sgg_conv2d_nhwc_fwd / _dgrad for the unit counts (nblk = B * H/8 * W/8; M = B * Ho * Wo; the dgrad swaps
                            C and N and never passes a cap).
 
@@ -57,20 +58,20 @@ def _walk(form, units, ntn, slots, info):
 
 
 def halo_plan(nblk, N, cu_cap=0):
-    """sgg_halo_launch without frag16: conv_halo3_kernel<2, BN, WGM, WGN>."""
+    """sgg_halo_route (launches without frag16): conv_halo3_kernel<2, BN, WGM, WGN>."""
     bn, waves = (128, 4) if N % 128 == 0 else ((64, 4) if N % 64 == 0 else (32, 2))
     return _walk("halo", cdiv(nblk, 2), N // bn, persist_cus(cu_cap) * 8 // waves, {"nb": 2, "bn": bn})
 
 
 def pc_plan(nblk, N, cu_cap=0):
-    """sgg_halo_pc_launch: two-block tiles of 128 columns, four-block tiles of 64 columns where N % 128 != 0."""
+    """sgg_halo_pc_route: two-block tiles of 128 columns, four-block tiles of 64 columns where N % 128 != 0."""
     nb = 4 if N % 128 != 0 else 2
     bn = 256 // nb
     return _walk("pc%d" % nb, cdiv(nblk, nb), N // bn, persist_cus(cu_cap), {"nb": nb, "bn": bn})
 
 
 def s2_plan(M, N, C, cu_cap=0, presplit=False, stats=False, ln=False):
-    """sgg_s2_launch in the two-piece fp16 mode (precision 2; presplit only exists there): M = B * Ho * Wo output positions (dgrad:
+    """sgg_s2_route in the two-piece fp16 mode (precision 2; presplit only exists there): M = B * Ho * Wo output positions (dgrad:
     positions of dy), N output columns, C contraction channels."""
     nbands = cdiv(M, S2_BAND)
     dmap = presplit and not ln
