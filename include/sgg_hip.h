@@ -353,6 +353,30 @@ int sgg_rank_triples(const long long* tokens, const float* d, int N, int nb, int
 int sgg_match_triples(const long long* ranked, const int* n_distinct, int nb, int K, const long long* gt, const int* gt_count, int M,
                       int V, int* pos, int* n_gt, void* stream);
 
+/* ---- training diagnostics: per-tensor norms and non-finite counts of a network's arenas (csrc/stats.hip) ----------------------
+ * One read-only streaming pass over params, grads, m and v: fp32 arenas of ONE layout, every tensor 16-byte aligned and rounded up
+ * to 4 elements (the arena ends on such a boundary), as sgg_adam_tf_multi takes them.
+ *   chunk_table int64 [n_chunks][3] (device): (tensor, first arena element, count) per chunk, built by the host: a chunk lies inside
+ *   ONE tensor, `first` is a multiple of 4, 1 <= count <= sgg_arena_stats_chunk(), the rows are sorted by tensor, tensors are
+ *   numbered 0 .. n_tensors - 1.  The table is device data and is NOT checked here: the caller guarantees first + count rounded up
+ *   to 4 <= the arenas' length.  Padding elements (behind a tensor's count) enter no statistic.
+ *   Per element: g = grads * grad_scale and u = lr_t * m / (sqrtf(v) + eps), both in fp32 exactly as sgg_adam_tf_multi forms them
+ *   (called right behind it with the same lr_t and eps, u is the delta that step applied, up to its sign).
+ *   out fp64 [n_tensors][sgg_arena_stats_nstat() = 9]: (sum of squares, max |.|, non-finite count) of g, of the parameter, of u.
+ *   Sums of squares (squares formed and summed in fp64) and maxima run over the FINITE elements; Inf and NaN are counted only.
+ *   Two launches on `stream`: per-chunk rows into `workspace` (sgg_arena_stats_workspace_bytes(n_chunks), plain stores), then one
+ *   wave per tensor sums its chunk rows in a fixed order.  No atomics: bit-identical from call to call and for every `grid`
+ *   (workgroups of the first launch; 0 = the default, min(n_chunks, 4096)). */
+int sgg_arena_stats_chunk(void);
+int sgg_arena_stats_nstat(void);
+size_t sgg_arena_stats_workspace_bytes(int n_chunks);
+int sgg_arena_stats(const float* params, const float* grads, const float* m, const float* v, const long long* chunk_table,
+                    int n_chunks, int n_tensors, float lr_t, float eps, float grad_scale, int grid, void* workspace,
+                    size_t workspace_bytes, double* out, void* stream);
+/* out fp64 [5] = { min, max, sum, count of x > threshold } over the finite elements of x [n] and the non-finite count; min = +Inf,
+ * max = -Inf, sum = 0 when no element is finite.  One workgroup, fixed summation order; 1 <= n <= 2^20. */
+int sgg_vector_stats(const float* x, int n, float threshold, double* out, void* stream);
+
 int sgg_fill(float* p, long long n, float value, void* stream);
 
 #ifdef __cplusplus

@@ -9,5 +9,6 @@ Imported as `sgg_amd` (see ../sgg_amd.py).  Only what the hot path needs lives h
   head.py    attention + LN-LSTM head forward / backward (fp32 and dual-number passes)
   step.py    WGAN-GP critic step / generator step, TF-Adam
   dp.py      data-parallel gradient all-reduce over RCCL with compute overlap
+  diagnostics.py  per-tensor norms / non-finite counts of the arenas (csrc/stats.hip): chunk table, fp64 reference, summary
 """
 __version__ = "0.1.0"

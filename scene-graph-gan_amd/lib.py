@@ -81,6 +81,11 @@ SIGNATURES = {
     "sgg_argmax_rows": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sgg_rank_triples": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgg_match_triples": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "sgg_arena_stats_chunk": (_i, []),
+    "sgg_arena_stats_nstat": (_i, []),
+    "sgg_arena_stats_workspace_bytes": (_sz, [_i]),
+    "sgg_arena_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _vp, _sz, _vp, _vp]),
+    "sgg_vector_stats": (_i, [_vp, _i, _f, _vp, _vp]),
     "sgg_fill": (_i, [_vp, _ll, _f, _vp]),
 }
 
@@ -850,6 +855,49 @@ class HipKernels:
         self._check(self._timed("adam_kernel", 0.0, lambda: self.lib.sgg_adam_tf_multi(
             _p(params), _p(grads), _p(m), _p(v), params.numel(), float(lr_t), float(b1), float(b2), float(eps), float(grad_scale),
             self._stream()), 28.0 * params.numel()), "sgg_adam_tf_multi")
+
+    # -- training diagnostics (csrc/stats.hip) ---------------------------------------------------------
+    def arena_stats_chunk(self):
+        """Elements per chunk of arena_stats' chunk table (a compile-time constant of the library; sgg_amd.diagnostics.CHUNK)."""
+        return int(self.lib.sgg_arena_stats_chunk())
+
+    def arena_stats_nstat(self):
+        return int(self.lib.sgg_arena_stats_nstat())
+
+    def arena_stats_workspace_bytes(self, n_chunks):
+        return int(self.lib.sgg_arena_stats_workspace_bytes(int(n_chunks)))
+
+    def arena_stats(self, params, grads, m, v, table, n_tensors, lr_t, eps, grad_scale=1.0, out=None, ws=None, grid=0):
+        """Per-tensor statistics of the four arenas in one pass (include/sgg_hip.h): table int64 [n_chunks, 3] on the device
+        (sgg_amd.diagnostics.chunk_table; the caller has checked it against the arenas' length, diagnostics.check_table), out fp64
+        [n_tensors, 9] (default: a new tensor), ws: a uint8 buffer of arena_stats_workspace_bytes(n_chunks) (default: the stream's
+        scratch buffer).  grid: workgroups of the first launch (0 = default); the result does not depend on it.  Reads only."""
+        self._dev(params, grads, m, v, table, out, ws)
+        n = params.numel()
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (params, grads, m, v)) and n % 4 == 0
+        assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 3 and table.is_contiguous()
+        n_chunks, ns = int(table.shape[0]), self.arena_stats_nstat()
+        if out is None:
+            out = torch.empty((n_tensors, ns), dtype=torch.float64, device=params.device)
+        assert out.dtype == torch.float64 and tuple(out.shape) == (n_tensors, ns) and out.is_contiguous()
+        if ws is None:
+            ws = self.workspace(self.arena_stats_workspace_bytes(n_chunks))
+        self._check(self._timed("arena_stats(call: chunk rows + per-tensor sum)", 0.0, lambda: self.lib.sgg_arena_stats(
+            _p(params), _p(grads), _p(m), _p(v), _p(table), n_chunks, int(n_tensors), float(lr_t), float(eps), float(grad_scale),
+            int(grid), _p(ws), ws.numel() * ws.element_size(), _p(out), self._stream()), 16.0 * n), "sgg_arena_stats")
+        return out
+
+    def vector_stats(self, x, threshold, out=None):
+        """out fp64 [5] = (min, max, sum, count above `threshold`) over the finite elements of the fp32 vector x, and its non-finite
+        count (include/sgg_hip.h); one workgroup."""
+        self._dev(x, out)
+        assert x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()
+        if out is None:
+            out = torch.empty((5,), dtype=torch.float64, device=x.device)
+        assert out.dtype == torch.float64 and tuple(out.shape) == (5,) and out.is_contiguous()
+        self._check(self._timed("vector_stats_kernel", 0.0, lambda: self.lib.sgg_vector_stats(
+            _p(x), x.numel(), float(threshold), _p(out), self._stream()), 4.0 * x.numel()), "sgg_vector_stats")
+        return out
 
     def argmax_rows(self, x, out):
         self._dev(x, out)

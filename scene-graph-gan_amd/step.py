@@ -20,6 +20,7 @@ import contextlib
 
 import torch
 
+from . import diagnostics
 from .head import Head
 from .lib import option
 from .params import ADAM_B1, ADAM_B2, ADAM_EPS, ADAM_LR, EMBED_DIM, FEAT_C, NUM_UNITS, T_STEPS, ParamArena
@@ -83,10 +84,51 @@ class Network:
     def adam_step(self, grad_scale=1.0):
         self.adam_t += 1
         a = self.arena
+        lr_t = tf_adam_lr_t(self.adam_t)
         self.K.adam(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat),
-                    tf_adam_lr_t(self.adam_t), ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale)
+                    lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale)
+        if self.opt.get("armed"):            # diagnostics: one read-only pass directly behind the step, on its stream
+            self.arena_stats(lr_t, grad_scale)
         a.version += 1                       # (encoders of other batch sizes on this arena re-derive their operand formats lazily)
         self.trunk.refresh_weights()
+
+    # ---- diagnostics (sgg_amd/diagnostics.py, csrc/stats.hip) -------------------------------------------
+    def _diag_state(self):
+        """Chunk table, workspace and stats buffer of this ARENA: built once, kept in `opt` (every Network on the arena sees them)."""
+        st = self.opt.get("diag")
+        if st is None:
+            if not hasattr(self.K, "arena_stats"):
+                raise RuntimeError("diagnostics need the arena_stats kernel; the %r kernel set has none" % getattr(self.K, "name", self.K))
+            chunk = self.K.arena_stats_chunk()
+            names, offsets, numels = diagnostics.live_layout(self.arena)
+            table = diagnostics.chunk_table(offsets, numels, chunk)
+            diagnostics.check_table(table, len(names), self.arena.live_numel, chunk)
+            dev = self.arena.flat.device
+            st = self.opt["diag"] = {
+                "names": names, "offsets": offsets, "numels": numels, "table": torch.from_numpy(table).to(dev),
+                "ws": torch.empty(self.K.arena_stats_workspace_bytes(len(table)), dtype=torch.uint8, device=dev),
+                "rows": torch.full((len(names), self.K.arena_stats_nstat()), float("nan"), dtype=torch.float64, device=dev),
+                "last": None}                # (lr_t, grad_scale) of the pass the rows are from; None: no pass yet
+        return st
+
+    def arm_diagnostics(self, on=True):
+        """While armed, every optimiser step on this arena is followed by the statistics pass (its rows overwrite the buffer)."""
+        if on:
+            self._diag_state()
+        self.opt["armed"] = bool(on)
+
+    def arena_stats(self, lr_t=None, grad_scale=None):
+        """Launch the statistics pass on the current stream into the arena's buffer; default: with the lr_t and gradient scale of the
+        last pass (re-reading the arenas as they are now).  Returns the device rows [T, 9]."""
+        st = self._diag_state()
+        if lr_t is None:
+            assert st["last"] is not None, "arena_stats(): no optimiser step has been recorded yet"
+            lr_t, grad_scale = st["last"]
+        a = self.arena
+        self.K.arena_stats(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat), st["table"], len(st["names"]),
+                           lr_t, ADAM_EPS, grad_scale, out=st["rows"], ws=st["ws"])
+        st["last"] = (lr_t, grad_scale)
+        return st["rows"]
 
 
 class GanStep:
@@ -338,6 +380,39 @@ class GanStep:
         """Apply any deferred optimiser update (before reading weights / at the end of the timed region)."""
         self.D.finish_update()
         self.G.finish_update()
+
+    # ---- diagnostics ---------------------------------------------------------------------------------
+    def arm_diagnostics(self, on=True):
+        """Arm (or disarm) both networks: while armed, each of their optimiser steps is followed by the statistics pass over its
+        arenas (Network.adam_step).  Read-only: the training state is bit-identical to a run that was never armed."""
+        self.G.arm_diagnostics(on)
+        self.D.arm_diagnostics(on)
+
+    def diagnostics(self):
+        """The statistics of each network's LAST optimiser step while armed, and of the critic's per-row slopes
+        ||d sum(D(x_hat)) / d x_hat|| that the last critic update's gradient penalty left on the device:
+            {"G": summary, "D": summary,                            diagnostics.summarise
+             "gp_slope": {min, mean, max, share_above_1, nonfinite},
+             "tensors": {"G": {name: row}, "D": {name: row}}}       diagnostics.tensor_rows (short TF names)
+        Applies any deferred optimiser step first (data parallel: the step just taken is the one reported; gradients are identical
+        across ranks after the all-reduce, so every rank sees the same network rows).  One device-to-host copy."""
+        self.flush()
+        gd, dd = self.G.opt.get("diag"), self.D.opt.get("diag")
+        if gd is None or dd is None or gd["last"] is None or dd["last"] is None:
+            raise RuntimeError("diagnostics(): no optimiser step of both networks has run while armed (arm_diagnostics first)")
+        if getattr(self, "_slope_stats", None) is None:
+            self._slope_stats = torch.empty(5, dtype=torch.float64, device=self.slopes.device)
+        self.K.vector_stats(self.slopes, 1.0, out=self._slope_stats)
+        host = torch.cat([gd["rows"].view(-1), dd["rows"].view(-1), self._slope_stats]).cpu().numpy()
+        ng, nd = gd["rows"].numel(), dd["rows"].numel()
+        rows = {"G": host[:ng], "D": host[ng:ng + nd]}
+        mn, mx, total, above, bad = (float(x) for x in host[ng + nd:])
+        finite = self.B - int(bad)
+        out = {n: diagnostics.summarise(rows[n], st["names"], st["numels"]) for n, st in (("G", gd), ("D", dd))}
+        out["gp_slope"] = {"min": mn if finite else None, "mean": total / finite if finite else None, "max": mx if finite else None,
+                           "share_above_1": above / finite if finite else None, "nonfinite": int(bad)}
+        out["tensors"] = {n: diagnostics.tensor_rows(rows[n], st["names"]) for n, st in (("G", gd), ("D", dd))}
+        return out
 
     def train_iteration(self, images, labels, noises, alphas, critic_iters=1, reuse_g_encoder=False):
         """Loop body of train.py:362-368: critic_iters critic updates then one generator update on one minibatch,

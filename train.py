@@ -32,6 +32,7 @@ import sgg_amd  # noqa: F401
 from sgg_amd import dp as dpmod
 from sgg_amd.api import kernels_for
 from sgg_amd.data import PrefetchLoader, ShuffledStream, parse_image
+from sgg_amd.diagnostics import raise_if_nonfinite
 from sgg_amd.params import EMBED_DIM
 from sgg_amd.metrics import MAX_GT, RecallAccumulator, zero_shot_mask
 from sgg_amd.predict import DEFAULT_LOGITS_BUDGET_BYTES, images_per_pass, scene_graph
@@ -276,11 +277,18 @@ class SceneGraphGAN(object):
         return True
 
     def train(self, max_iterations=None, log_every=10, save_every=0, validate_every=None, test_at_end=None, patience=3,
-              test_max_images=None):
+              test_max_images=None, diagnostics_every=0, halt_on_nonfinite=False):
         """train.py:341-388.  Every `validate_every` iterations (default: the reference's len(train) / 50 on real data, off in
         synthetic mode) the critic's cost on a validation batch is compared with the previous one: `patience` (3) consecutive
         increases end the training (train.py:375-384); afterwards the model is evaluated (`print "Testing"; self.test(sess)`,
-        train.py:387-388) - by default on real data only."""
+        train.py:387-388) - by default on real data only.
+
+        diagnostics_every = N > 0: iterations N, 2N, ... run with the statistics pass armed for their whole length
+        (GanStep.arm_diagnostics: per-tensor gradient / parameter / update norms and non-finite counts behind every optimiser step,
+        read-only); their summary goes into losses.jsonl under "diag" (into that iteration's record, or one of its own) and the
+        per-tensor table into summaries_dir/diagnostics.jsonl (rank 0).  halt_on_nonfinite: such an iteration that counts an Inf or
+        NaN raises diagnostics.NonFiniteError before anything else happens - no checkpoint is written on the way out (neither
+        save_every's nor the final one), so the last good checkpoint survives."""
         images, labels = self._next_batch(0)
         self._constructOps(images)
         if self.resume and os.path.exists(self._ckpt_path()):
@@ -301,9 +309,14 @@ class SceneGraphGAN(object):
             stopper.last, stopper.count, self.val_history = rv["last"], rv["count"], [tuple(x) for x in rv["history"]]
             self._resumed_val = None
         self._stopper = stopper
+        diagnostics_every = int(diagnostics_every or 0)
+        diag_log = open(os.path.join(self.summaries_dir, "diagnostics.jsonl"), "a") if (self.rank == 0 and diagnostics_every > 0) else None
         try:
             while self.itr < n_it:
                 images, labels = next(loader) if loader is not None else self._next_batch(self.itr)
+                report = diagnostics_every > 0 and (self.itr + 1) % diagnostics_every == 0
+                if diagnostics_every > 0:
+                    self.step.arm_diagnostics(report)
                 # every update of an iteration sees the same minibatch (train.py:175-190) and G's weights change only at its end: G's
                 # encoder runs once per iteration (exact; 10 of 11 encoder forwards of G saved at CRITIC_ITERS = 10)
                 with self.step.iteration(reuse_g_encoder=self.reuse_g_encoder):
@@ -315,12 +328,24 @@ class SceneGraphGAN(object):
                     self.step.generator_step(images, noise)                             # train.py:368
                 itr = self.itr                                                          # the reference's 0-based loop variable
                 self.itr += 1
+                diag = self.step.diagnostics() if report else None
+                tensors = diag.pop("tensors") if diag is not None else None
                 if log is not None and self.itr % log_every == 0:
                     d, g = self.step.d_losses.cpu().tolist(), self.step.g_losses.cpu().tolist()
                     rate = B * self.world * (self.itr - itr0) / (time.time() - t0)      # of this run (a resumed run starts at itr0 > 0)
                     rec = {"itr": self.itr, "disc_loss": d[0], "gen_loss": -g[3], "gp": d[2], "triples_per_s": rate}
+                    if diag is not None:
+                        rec["diag"] = diag
                     log.write(json.dumps(rec) + "\n"); log.flush()
                     print(rec)
+                elif log is not None and diag is not None:
+                    log.write(json.dumps({"itr": self.itr, "diag": diag}) + "\n"); log.flush()
+                if diag_log is not None and tensors is not None:
+                    diag_log.write(json.dumps({"itr": self.itr, "tensors": tensors}) + "\n"); diag_log.flush()
+                if diag is not None and halt_on_nonfinite:
+                    # every rank sees the same network rows (the gradients are all-reduced), so every rank raises here; the exception
+                    # passes the checkpoint writes below and the final one behind the loop
+                    raise_if_nonfinite(diag, self.itr)
                 if save_every and self.itr % save_every == 0:
                     self._saveModel()
                 if validate_every and itr % validate_every == 0:                        # train.py:375-384
@@ -334,6 +359,8 @@ class SceneGraphGAN(object):
         finally:
             if loader is not None:
                 loader.close()
+            if diag_log is not None:
+                diag_log.close()
         self._saveModel()
         if test_at_end:
             print("Testing")                                                            # train.py:387-388
@@ -759,7 +786,7 @@ def _str2bool(v):
     raise argparse.ArgumentTypeError("expected a boolean, got %r" % (v,))
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--checkpoints_dir", help="Where to save the checkpoints", default="./checkpoints")
     parser.add_argument("--summaries_dir", help="Where to write the logs", default="./logs")
@@ -801,7 +828,19 @@ if __name__ == "__main__":
                         help="load the checkpoint in --checkpoints_dir, write R@K, mR@K and zsR@K of the test images (distinct "
                              "predictions, denominators |GT|) as JSON to this file and exit; no training")
     parser.add_argument("--metrics_k", default="20,50,100", help="the K values of --metrics_out, comma-separated")
-    args = parser.parse_args()
+    parser.add_argument("--diagnostics_every", default=0, type=int,
+                        help="every N iterations, report per-tensor gradient / parameter / update norms and non-finite counts of both "
+                             "networks and the critic's gradient-penalty slopes: summary under \"diag\" in losses.jsonl, per-tensor table in "
+                             "<summaries_dir>/diagnostics.jsonl (default 0: off, nothing is launched; read-only when on)")
+    parser.add_argument("--halt_on_nonfinite", action="store_true",
+                        help="with --diagnostics_every: stop with NonFiniteError (network, tensor, gradient / parameter / update) on "
+                             "the first reported iteration that counts an Inf or NaN; no checkpoint is written on the way out, so the "
+                             "last good one in --checkpoints_dir survives")
+    return parser
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
     params = vars(args)
 
     if "LOCAL_RANK" not in os.environ:
@@ -844,4 +883,5 @@ if __name__ == "__main__":
         gan.test(max_images=params["max_test_images"])
     else:
         gan.train(max_iterations=params["max_iterations"], validate_every=params["validate_every"],
-                  test_max_images=params["max_test_images"])
+                  test_max_images=params["max_test_images"], diagnostics_every=params["diagnostics_every"],
+                  halt_on_nonfinite=params["halt_on_nonfinite"])
