@@ -317,6 +317,20 @@ int sgg_resize_bilinear_tf1(const unsigned char* src, const long long* offsets, 
 int sgg_adam_tf_multi(float* params, const float* grads, float* m, float* v, long long n, float lr_t, float beta1,
                       float beta2, float eps, float grad_scale, void* stream);
 
+/* ---- tf.train.ExponentialMovingAverage of the trained variables (csrc/ema.hip) --------------------------------------------
+ * The reference never averages its weights; its framework ships the op, and evaluating a WGAN-GP generator on the average of its
+ * iterates is the usual remedy for the noise of the last one.
+ * sgg_adam_tf_multi_ema: sgg_adam_tf_multi and, in the same pass, the shadow update of the average on the new parameter value:
+ *   ema -= (ema - params_new) * one_minus_decay    in fp32 (one_minus_decay = 1 - min(decay, (1 + k) / (10 + k)) for the k-th
+ *   update, formed by the caller in double: sgg_amd/ema.py).  params, m and v come out bit-identical to sgg_adam_tf_multi on the
+ *   same inputs.  Nine streams of n words instead of seven.  All five pointers 16-byte aligned; `ema` must not overlap any other
+ *   operand (argument error); 0 <= one_minus_decay <= 1.
+ * sgg_swap_f32: exchanges a[0 .. n) and b[0 .. n) bit for bit (values are moved, never computed with: NaN payloads and -0.0
+ *   survive).  Both 16-byte aligned, the ranges must not overlap (argument error). */
+int sgg_adam_tf_multi_ema(float* params, const float* grads, float* m, float* v, float* ema, long long n, float lr_t, float beta1,
+                          float beta2, float eps, float grad_scale, float one_minus_decay, void* stream);
+int sgg_swap_f32(float* a, float* b, long long n, void* stream);
+
 /* ---- tf.argmax(x, axis=-1): train.py:270-271 ---------------------------------------------------------------- */
 int sgg_argmax_rows(const float* x, long long* out, int rows, int V, int ld, void* stream);
 

@@ -101,9 +101,18 @@ class NetworkHandle(object):
         self.alpha = al[0]
         return z[0]
 
-    def state_dict(self, full_names=True):
-        return self.net.arena.state_dict(full_names)
+    def state_dict(self, full_names=True, averaged=False):
+        """averaged=True: the weight average (Network.enable_averaging) under the same names."""
+        return self.net.state_dict(full_names, averaged)
 
     def load_state_dict(self, sd):
-        self.net.arena.load_state_dict(sd)
-        self.net.trunk.refresh_weights()
+        self.net.load_state_dict(sd)
+
+    @property
+    def has_average(self):
+        return self.net is not None and self.net.has_average
+
+    def averaged(self):
+        """Context manager: every build of this object inside it - any batch size - runs on the averaged weights
+        (step.Network.averaged)."""
+        return self.net.averaged()

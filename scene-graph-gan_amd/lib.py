@@ -78,6 +78,8 @@ SIGNATURES = {
     "sgg_wgan_gp_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "sgg_wgan_losses": (_i, [_vp, _vp, _f, _i, _i, _i, _vp, _vp]),
     "sgg_adam_tf_multi": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _vp]),
+    "sgg_adam_tf_multi_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _f, _vp]),
+    "sgg_swap_f32": (_i, [_vp, _vp, _ll, _vp]),
     "sgg_argmax_rows": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sgg_rank_triples": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgg_match_triples": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
@@ -855,6 +857,24 @@ class HipKernels:
         self._check(self._timed("adam_kernel", 0.0, lambda: self.lib.sgg_adam_tf_multi(
             _p(params), _p(grads), _p(m), _p(v), params.numel(), float(lr_t), float(b1), float(b2), float(eps), float(grad_scale),
             self._stream()), 28.0 * params.numel()), "sgg_adam_tf_multi")
+
+    def adam_ema(self, params, grads, m, v, ema, lr_t, b1, b2, eps, grad_scale=1.0, one_minus_decay=0.0):
+        """adam() and, in the same pass, ema -= (ema - params_new) * one_minus_decay (csrc/ema.hip; include/sgg_hip.h): params, m and
+        v bit-identical to adam().  ema: fp32, as long as params, overlapping none of the other operands."""
+        self._dev(params, grads, m, v, ema)
+        n = params.numel()
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (params, grads, m, v, ema))
+        self._check(self._timed("adam_ema_kernel", 0.0, lambda: self.lib.sgg_adam_tf_multi_ema(
+            _p(params), _p(grads), _p(m), _p(v), _p(ema), n, float(lr_t), float(b1), float(b2), float(eps), float(grad_scale),
+            float(one_minus_decay), self._stream()), 36.0 * n), "sgg_adam_tf_multi_ema")
+
+    def swap(self, a, b):
+        """Exchange the contents of two fp32 ranges of equal length bit for bit (csrc/ema.hip)."""
+        self._dev(a, b)
+        n = a.numel()
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (a, b))
+        self._check(self._timed("swap_kernel", 0.0, lambda: self.lib.sgg_swap_f32(_p(a), _p(b), n, self._stream()), 16.0 * n),
+                    "sgg_swap_f32")
 
     # -- training diagnostics (csrc/stats.hip) ---------------------------------------------------------
     def arena_stats_chunk(self):

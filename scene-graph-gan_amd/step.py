@@ -17,13 +17,14 @@ from __future__ import annotations
 import math
 
 import contextlib
+from collections import OrderedDict
 
 import torch
 
-from . import diagnostics
+from . import diagnostics, ema
 from .head import Head
 from .lib import option
-from .params import ADAM_B1, ADAM_B2, ADAM_EPS, ADAM_LR, EMBED_DIM, FEAT_C, NUM_UNITS, T_STEPS, ParamArena
+from .params import ADAM_B1, ADAM_B2, ADAM_EPS, ADAM_LR, EMBED_DIM, FEAT_C, NUM_UNITS, T_STEPS, ParamArena, tf_variable_name
 from .trunk import Trunk
 
 
@@ -82,14 +83,121 @@ class Network:
             self.adam_step(scale)
 
     def adam_step(self, grad_scale=1.0):
+        self._not_swapped("adam_step")
         self.adam_t += 1
         a = self.arena
         lr_t = tf_adam_lr_t(self.adam_t)
-        self.K.adam(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat),
-                    lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale)
+        avg = self.opt.get("ema")
+        if avg is None:
+            self.K.adam(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat),
+                        lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale)
+        else:                                # the same step with the shadow update of the average in the same pass (csrc/ema.hip)
+            self.K.adam_ema(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat), a.live(avg["flat"]),
+                            lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale, ema.one_minus_decay(avg["decay"], avg["updates"]))
+            avg["updates"] += 1
         if self.opt.get("armed"):            # diagnostics: one read-only pass directly behind the step, on its stream
             self.arena_stats(lr_t, grad_scale)
         a.version += 1                       # (encoders of other batch sizes on this arena re-derive their operand formats lazily)
+        self.trunk.refresh_weights()
+
+    # ---- weight averaging (sgg_amd/ema.py, csrc/ema.hip) -------------------------------------------------
+    # opt["ema"] = {"flat": buffer of the arena's layout, "decay", "updates": shadow updates applied, "swapped"}: state of the ARENA,
+    # like t / pending / diag - every Network on it sees the same average.
+    has_average = property(lambda self: self.opt.get("ema") is not None)
+
+    def _not_swapped(self, what):
+        avg = self.opt.get("ema")
+        if avg is not None and avg["swapped"]:
+            raise RuntimeError("%s inside averaged(): the arena holds the averaged weights until the context exits" % what)
+
+    def enable_averaging(self, decay):
+        """Keep tf.train.ExponentialMovingAverage(decay, num_updates) of this arena's parameters: from now on every optimiser step
+        also updates the average (one fused pass).  The first call allocates the buffer as a bit copy of the whole arena (dead tail
+        included) with update count 0; a later call changes the decay only."""
+        ema.tf_ema_decay(decay, 0)           # (ValueError unless 0 < decay < 1)
+        avg = self.opt.get("ema")
+        if avg is not None:
+            avg["decay"] = float(decay)
+            return
+        if not (hasattr(self.K, "adam_ema") and hasattr(self.K, "swap")):
+            raise RuntimeError("weight averaging needs the adam_ema and swap kernels; the %r kernel set has none"
+                               % getattr(self.K, "name", self.K))
+        self.finish_update()
+        self.opt["ema"] = {"flat": self.arena.flat.clone(), "decay": float(decay), "updates": 0, "swapped": False}
+
+    def disable_averaging(self):
+        """Stop averaging and free the buffer: the next optimiser step is the plain one again."""
+        self._not_swapped("disable_averaging")
+        self.opt.pop("ema", None)
+
+    def reset_average(self):
+        """Restart the average from the arena as it is now (after a load_state_dict): bit copy, update count 0."""
+        avg = self._average("reset_average")
+        self._not_swapped("reset_average")
+        self.finish_update()
+        avg["flat"].copy_(self.arena.flat)
+        avg["updates"] = 0
+
+    def average_state(self):
+        """What a checkpoint keeps of the average: {"flat": the whole buffer on the host, "updates", "decay"}."""
+        avg = self._average("average_state")
+        self._not_swapped("average_state")
+        self.finish_update()
+        return {"flat": avg["flat"].cpu(), "updates": int(avg["updates"]), "decay": float(avg["decay"])}
+
+    def restore_average(self, flat, updates):
+        """Put a saved buffer and update count back (average_state; the decay in force stays)."""
+        avg = self._average("restore_average")
+        self._not_swapped("restore_average")
+        flat = torch.as_tensor(flat)
+        if tuple(flat.shape) != tuple(avg["flat"].shape):
+            raise ValueError("saved average has %d elements, this network's arena %d" % (flat.numel(), avg["flat"].numel()))
+        avg["flat"].copy_(flat)
+        avg["updates"] = int(updates)
+
+    def _average(self, what):
+        avg = self.opt.get("ema")
+        if avg is None:
+            raise RuntimeError("%s: this network keeps no weight average (enable_averaging first)" % what)
+        return avg
+
+    def _exchange_average(self):
+        a = self.arena
+        self.K.swap(a.live(), a.live(self.opt["ema"]["flat"]))
+        a.version += 1                       # as adam_step after writing the parameters
+        self.trunk.refresh_weights()
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Run with the AVERAGED weights in the arena: the live ranges of the arena and of the average are exchanged on entry and
+        exchanged back on exit, bit for bit.  Addresses never change - every view, weight descriptor and pre-split copy of every
+        Network on the arena stays valid and is re-derived through arena.version, as after an optimiser step.  Applies a pending
+        update first.  Not re-entrant; adam_step, load_state_dict, reset_average and state_dict raise inside.  For use between
+        iterations (outside GanStep.iteration())."""
+        avg = self._average("averaged()")
+        self._not_swapped("a nested averaged()")
+        self.finish_update()
+        self._exchange_average()
+        avg["swapped"] = True
+        try:
+            yield self
+        finally:
+            avg["swapped"] = False
+            self._exchange_average()
+
+    def state_dict(self, full_names=False, averaged=False):
+        """The parameters (averaged=True: the average) by TF name, on the host; a pending update is applied first."""
+        self._not_swapped("state_dict")
+        self.finish_update()
+        if not averaged:
+            return self.arena.state_dict(full_names)
+        views = self.arena._make_views(self._average("state_dict(averaged=True)")["flat"])
+        return OrderedDict(((tf_variable_name(self.kind, n) if full_names else n), v.detach().clone().cpu()) for n, v in views.items())
+
+    def load_state_dict(self, sd, strict=True):
+        """arena.load_state_dict + the encoder's operand formats.  The average, if any, is left alone (reset_average restarts it)."""
+        self._not_swapped("load_state_dict")
+        self.arena.load_state_dict(sd, strict)
         self.trunk.refresh_weights()
 
     # ---- diagnostics (sgg_amd/diagnostics.py, csrc/stats.hip) -------------------------------------------

@@ -4,6 +4,7 @@
     python train.py --checkpoints_dir ckpt --saliency_dir maps             # per-word saliency maps of the test split
     python train.py --checkpoints_dir ckpt --predict_dir graphs            # ranked scene graph of every test image
     python train.py --checkpoints_dir ckpt --metrics_out metrics.json      # R@K, mR@K, zsR@K of the test split
+    python train.py --ema_decay 0.999 ...                                  # keep an average of G's weights; evaluation then uses it
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -18,6 +19,7 @@ import os, sys
 sys.path.append(os.getcwd())
 
 import argparse
+import contextlib
 import json
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -62,7 +64,8 @@ class SceneGraphGAN(object):
     ############################################################
     def __init__(self, checkpoints_dir, summaries_dir, path_to_ims_to_triples, path_to_vocab, path_to_word_embeddings,
                  path_to_image_means, path_to_image_stds, critic_iters, batch_size, lambda_, resume,
-                 synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True):
+                 synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True,
+                 ema_decay=0.0, eval_live=False):
         # Hyperparameters (train.py:26-32)
         self.CRITIC_ITERS = int(critic_iters)
         self.BATCH_SIZE = int(batch_size)
@@ -75,6 +78,15 @@ class SceneGraphGAN(object):
         # chain): same kernels, bit-identical results (tests/test_concurrency_gpu.py), +4 % triples/s
         self.two_streams = bool(two_streams)
         self.reuse_g_encoder = bool(reuse_g_encoder)
+        # ema_decay > 0: an exponential moving average of G's weights (tf.train.ExponentialMovingAverage with its warm-up schedule) is
+        # updated inside every generator step (step.Network.enable_averaging).  Training, the validation loss and sample_triples use
+        # the live weights; evaluation - test(), saliency(), predict(), evaluate() - runs G on the average whenever one exists
+        # (enabled here or restored from the checkpoint) unless eval_live.  The critic is never averaged.
+        self.ema_decay = float(ema_decay or 0.0)
+        if self.ema_decay < 0.0 or self.ema_decay >= 1.0:
+            raise ValueError("ema_decay must be 0 (off) or lie strictly between 0 and 1 (got %r)" % (ema_decay,))
+        self.eval_live = bool(eval_live)
+        self._in_eval = False
         self.shuffle_buffer = bool(shuffle_buffer)      # tf.data shuffle(buffer_size = 10 * batch) on the repeated stream (train.py:176-179)
         self.checkpoints_dir, self.summaries_dir = checkpoints_dir, summaries_dir
         self.rank, self.world, local = dpmod.init_from_env()
@@ -238,21 +250,66 @@ class SceneGraphGAN(object):
         self.step.flush()
         if self.rank == 0:
             stopper = getattr(self, "_stopper", None)
-            torch.save({"itr": self.itr, "G": self.g.state_dict(), "D": self.d.state_dict(),
-                        "G_adam": (self.step.G.m_flat.cpu(), self.step.G.v_flat.cpu(), self.step.G.adam_t),
-                        "D_adam": (self.step.D.m_flat.cpu(), self.step.D.v_flat.cpu(), self.step.D.adam_t),
-                        # the validation state of the loop (train.py:358-384): last loss, consecutive increases, batches consumed
-                        "val": {"last": stopper.last if stopper else float("inf"), "count": stopper.count if stopper else 0,
-                                "history": list(getattr(self, "val_history", []))}}, self._ckpt_path())
+            ck = {"itr": self.itr, "G": self.g.state_dict(), "D": self.d.state_dict(),
+                  "G_adam": (self.step.G.m_flat.cpu(), self.step.G.v_flat.cpu(), self.step.G.adam_t),
+                  "D_adam": (self.step.D.m_flat.cpu(), self.step.D.v_flat.cpu(), self.step.D.adam_t),
+                  # the validation state of the loop (train.py:358-384): last loss, consecutive increases, batches consumed
+                  "val": {"last": stopper.last if stopper else float("inf"), "count": stopper.count if stopper else 0,
+                          "history": list(getattr(self, "val_history", []))}}
+            if self.step.G.has_average:     # (only a run that averages writes these keys: without it the checkpoint is what it was)
+                ck["G_ema"] = self.step.G.average_state()
+                # ... and where its noise stream stands, so that a resumed run continues the stream and its average is the one of
+                # the uninterrupted run (single process: every rank draws from a stream of its own, rank 0 writes)
+                gen = getattr(self, "_noise_gen", None)
+                if gen is not None and self.world == 1:
+                    ck["noise_rng"] = gen.get_state()
+            torch.save(ck, self._ckpt_path())
 
-    def _loadModel(self):
+    def _loadModel(self, for_training=False):
         ck = torch.load(self._ckpt_path(), map_location="cpu")
         self.g.load_state_dict(ck["G"])
         self.d.load_state_dict(ck["D"])
         for net, key in ((self.step.G, "G_adam"), (self.step.D, "D_adam")):
             net.m_flat.copy_(ck[key][0]); net.v_flat.copy_(ck[key][1]); net.adam_t = ck[key][2]
+        saved, G = ck.get("G_ema"), self.step.G
+        if self.ema_decay > 0.0:            # (_constructOps enabled averaging with the decay of this run: it wins over the saved one)
+            if saved is not None:
+                G.restore_average(saved["flat"], saved["updates"])
+            else:
+                G.reset_average()           # the average starts from the loaded weights
+        elif saved is not None:
+            if for_training:
+                if self.rank == 0:
+                    print("resuming without --ema_decay: the checkpoint's average of the generator weights is dropped")
+            else:                           # evaluation-only modes use the checkpoint's average without the flag
+                G.enable_averaging(saved["decay"])
+                G.restore_average(saved["flat"], saved["updates"])
         self.itr = ck["itr"]
         self._resumed_val = ck.get("val")
+        self._resumed_rng = ck.get("noise_rng") if (for_training and self.ema_decay > 0.0 and self.world == 1) else None
+
+    @property
+    def evaluates_average(self):
+        """True if evaluation runs G on the average of its weights (one exists and eval_live is off)."""
+        return (not self.eval_live) and self.step is not None and self.step.G.has_average
+
+    @contextlib.contextmanager
+    def _eval_weights(self):
+        """The weights evaluation runs on: inside, G's arena holds the average where evaluates_average (Network.averaged: exchanged
+        on entry, exchanged back on exit), else nothing changes.  Yields "ema" or "live".  Re-entrant (write_saliency -> saliency)."""
+        if self.step is None:               # (an untrained model: the networks are built here, as the evaluation entry points do)
+            images, _ = self._next_batch(0)
+            self._constructOps(images)
+        if self._in_eval or not self.evaluates_average:
+            yield "ema" if self._in_eval else "live"
+            return
+        self.step.flush()
+        self._in_eval = True
+        try:
+            with self.g.averaged():
+                yield "ema"
+        finally:
+            self._in_eval = False
 
     ############################################################
     ## Training (train.py:341-388)
@@ -264,6 +321,8 @@ class SceneGraphGAN(object):
         reducer = dpmod.GradReducer() if self.world > 1 else None
         self.step = GanStep(kernels_for(self.device), V, S, B, lam=self.LAMBDA, G=g_net, D=d_net, reducer=reducer,
                             overlap_streams=self.two_streams)
+        if self.ema_decay > 0.0:            # G only: the critic keeps its live weights everywhere
+            self.step.G.enable_averaging(self.ema_decay)
 
     def load_checkpoint(self):
         """Build both networks and load the checkpoint in checkpoints_dir (weights, Adam state, iteration) as --resume does;
@@ -292,13 +351,16 @@ class SceneGraphGAN(object):
         images, labels = self._next_batch(0)
         self._constructOps(images)
         if self.resume and os.path.exists(self._ckpt_path()):
-            self._loadModel()
+            self._loadModel(for_training=True)
         n_it = max_iterations if max_iterations is not None else getattr(self, "max_iterations", 1000)
         if validate_every is None:
             validate_every = getattr(self, "validate_iterations", 0) if self.dataset is not None else 0
         if test_at_end is None:
             test_at_end = self.dataset is not None
-        gen = torch.Generator().manual_seed(self.seed + 7 + self.rank)
+        gen = self._noise_gen = torch.Generator().manual_seed(self.seed + 7 + self.rank)
+        if getattr(self, "_resumed_rng", None) is not None:
+            gen.set_state(self._resumed_rng)
+            self._resumed_rng = None
         vgen = torch.Generator().manual_seed(self.seed + 70007 + self.rank)
         log = open(os.path.join(self.summaries_dir, "losses.jsonl"), "a") if self.rank == 0 else None
         B, t0, itr0 = self.BATCH_SIZE, time.time(), self.itr
@@ -407,7 +469,13 @@ class SceneGraphGAN(object):
         dropped), all N samples of those images as one head pass of N x TEST_BATCH_SIZE rows (Generator.sample ->
         Discriminator.score_samples), tokens and critic outputs copied to the host once per batch.  Same samples as the reference's
         protocol: sample k = pass * TEST_BATCH_SIZE + j of an image uses row j of that image's pass-th [TEST_BATCH_SIZE, 512] noise
-        draw, drawn image after image.  Test-split images are decoded by a thread pool while the previous batch runs."""
+        draw, drawn image after image.  Test-split images are decoded by a thread pool while the previous batch runs.
+
+        With an average of G's weights (ema_decay, or one restored from the checkpoint) and eval_live off, G runs on the average."""
+        with self._eval_weights():
+            return self._test(max_images, out_path, reference_literal, items, return_details)
+
+    def _test(self, max_images, out_path, reference_literal, items, return_details):
         if self.step is None:
             images, _ = self._next_batch(0)
             self._constructOps(images)
@@ -484,10 +552,12 @@ class SceneGraphGAN(object):
         None).  Returns a dict of device tensors: tokens [B, 3] (argmax, as sample_triples), words, attention [B, 3, Hf, Wf] (the
         attention of each step), saliency [B, 3, S, S] = max over channels of |d logit[b, t, token_bt] / d image[b]| (Simonyan et
         al. 2014), and the noise used.  All three words share one noise draw and one forward pass; each word's gradient is its own
-        data-only backward from that pass (Generator.saliency_gradients).  The weights and optimiser state are not touched."""
+        data-only backward from that pass (Generator.saliency_gradients).  The weights and optimiser state are not touched.  With an
+        average of G's weights and eval_live off, G runs on the average."""
         if self.step is not None:
             self.step.flush()
-        tokens, grads, noise = self.g.saliency_gradients(images, noise)
+        with self._eval_weights() if self.evaluates_average else contextlib.nullcontext():      # (no networks are built here)
+            tokens, grads, noise = self.g.saliency_gradients(images, noise)
         B, S = int(images.shape[0]), int(images.shape[1])
         al = self.g.alphas
         side = int(round(al.shape[-1] ** 0.5))
@@ -515,19 +585,22 @@ class SceneGraphGAN(object):
         nb = max(1, min(self.TEST_BATCH_SIZE, len(items)))
         gen = torch.Generator().manual_seed(self.seed + 321)
         index = {}
-        for i0 in range(0, len(items), nb):
-            chunk = items[i0:i0 + nb]
-            imgs = [self._parseFunction(x) if isinstance(x, str) else x for _, x in chunk]
-            n = len(imgs)
-            images = torch.stack(imgs + [imgs[-1]] * (nb - n)).to(self.device)      # (the last batch padded with its last image)
-            noise = torch.randn((nb, 512), generator=gen).to(self.device)
-            r = self.saliency(images, noise)
-            tok, att, sal, nz = (r[k].cpu().numpy() for k in ("tokens", "attention", "saliency", "noise"))
-            for j in range(n):
-                name = "%06d.npz" % (i0 + j)
-                np.savez(os.path.join(out_dir, name), tokens=tok[j], words=np.array(r["words"][j]), attention=att[j], saliency=sal[j],
-                         noise=nz[j])
-                index[chunk[j][0]] = {"file": name, "words": r["words"][j]}
+        with self._eval_weights() as weights:
+            for i0 in range(0, len(items), nb):
+                chunk = items[i0:i0 + nb]
+                imgs = [self._parseFunction(x) if isinstance(x, str) else x for _, x in chunk]
+                n = len(imgs)
+                images = torch.stack(imgs + [imgs[-1]] * (nb - n)).to(self.device)      # (the last batch padded with its last image)
+                noise = torch.randn((nb, 512), generator=gen).to(self.device)
+                r = self.saliency(images, noise)
+                tok, att, sal, nz = (r[k].cpu().numpy() for k in ("tokens", "attention", "saliency", "noise"))
+                for j in range(n):
+                    name = "%06d.npz" % (i0 + j)
+                    np.savez(os.path.join(out_dir, name), tokens=tok[j], words=np.array(r["words"][j]), attention=att[j], saliency=sal[j],
+                             noise=nz[j])
+                    index[chunk[j][0]] = {"file": name, "words": r["words"][j]}
+        if weights == "ema":
+            index["generator_weights"] = "ema"
         with open(os.path.join(out_dir, "index.json"), "w") as f:
             json.dump(index, f, indent=1)
         if self.rank == 0:
@@ -660,23 +733,28 @@ class SceneGraphGAN(object):
         samples stay on the device).  Noise: per image ceil(n_samples / TEST_BATCH_SIZE) draws of [TEST_BATCH_SIZE, 512] from seed
         + 123, image after image, the first n_samples rows used - with the defaults the stream of test(), sample for sample.
         Touches no weights and no optimiser state; usable on an untrained model, as test() is."""
-        return list(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention, logits_budget_bytes))
+        with self._eval_weights():
+            return list(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention, logits_budget_bytes))
 
     def write_predictions(self, out_dir, max_images=None, n_samples=None, top_k=None, descending=False, items=None):
         """predict(with_attention=True) of the test images to disk: one <index>.npz per image (triples, words, scores, first_rank,
         first_sample, counts, n_distinct, attention) and index.json (image path or index -> npz file, n_distinct and the graph)."""
         os.makedirs(out_dir, exist_ok=True)
         index = {}
-        for i, r in enumerate(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention=True)):
-            name = "%06d.npz" % i
-            np.savez(os.path.join(out_dir, name), triples=r["triples"], words=np.array(r["words"], dtype=str).reshape(-1, 3),
-                     scores=r["scores"], first_rank=r["first_rank"], first_sample=r["first_sample"], counts=r["counts"],
-                     n_distinct=np.int32(r["n_distinct"]), attention=r["attention"])
-            index[r["image"]] = {"file": name, "n_distinct": r["n_distinct"], "graph": r["graph"]}
+        with self._eval_weights() as weights:
+            for i, r in enumerate(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention=True)):
+                name = "%06d.npz" % i
+                np.savez(os.path.join(out_dir, name), triples=r["triples"], words=np.array(r["words"], dtype=str).reshape(-1, 3),
+                         scores=r["scores"], first_rank=r["first_rank"], first_sample=r["first_sample"], counts=r["counts"],
+                         n_distinct=np.int32(r["n_distinct"]), attention=r["attention"])
+                index[r["image"]] = {"file": name, "n_distinct": r["n_distinct"], "graph": r["graph"]}
+        n_images = len(index)
+        if weights == "ema":
+            index["generator_weights"] = "ema"
         with open(os.path.join(out_dir, "index.json"), "w") as f:
             json.dump(index, f, indent=1)
         if self.rank == 0:
-            print({"predict_dir": out_dir, "images": len(index)})
+            print({"predict_dir": out_dir, "images": n_images})
         return index
 
 
@@ -712,7 +790,15 @@ class SceneGraphGAN(object):
 
         Schedule: the batches of predict(); per batch one copy to the device (the padded ground truth and its counts) and one
         copy back (pos, n_gt, n_distinct).  Ranked triples, tokens and scores stay on the device.  Touches no weights and no
-        optimiser state; usable on an untrained model, as test() and predict() are."""
+        optimiser state; usable on an untrained model, as test() and predict() are.
+
+        With an average of G's weights and eval_live off, G runs on the average and the result says "generator_weights": "ema"."""
+        with self._eval_weights() as weights:
+            return self._evaluate(items, max_images, ks, n_samples, descending, train_triples, return_details, out_path,
+                                  logits_budget_bytes, weights)
+
+    def _evaluate(self, items, max_images, ks, n_samples, descending, train_triples, return_details, out_path, logits_budget_bytes,
+                  weights):
         ks = tuple(sorted(set(int(k) for k in ks)))
         if not ks or ks[0] < 1:
             raise ValueError("evaluate: ks must be positive integers (got %r)" % (ks,))
@@ -769,6 +855,8 @@ class SceneGraphGAN(object):
                                   "the triples absent from the training set"})
         if return_details:
             res["details"] = details
+        if weights == "ema":
+            res["generator_weights"] = "ema"
         if self.rank == 0 and out_path:
             with open(out_path, "w") as f:
                 json.dump(res, f, indent=1)
@@ -836,6 +924,13 @@ def build_parser():
                         help="with --diagnostics_every: stop with NonFiniteError (network, tensor, gradient / parameter / update) on "
                              "the first reported iteration that counts an Inf or NaN; no checkpoint is written on the way out, so the "
                              "last good one in --checkpoints_dir survives")
+    parser.add_argument("--ema_decay", default=0.0, type=float,
+                        help="D in (0, 1): keep an exponential moving average of the generator's weights (decay min(D, (1 + k) / (10 + k)) "
+                             "at its k-th update, as tf.train.ExponentialMovingAverage), updated inside the generator's optimiser pass "
+                             "and saved in the checkpoint; evaluation (the test after training, --test_only, --saliency_dir, "
+                             "--predict_dir, --metrics_out) then runs the generator on the average (default 0: off)")
+    parser.add_argument("--eval_live", action="store_true",
+                        help="evaluate the generator's live weights even where an average exists (from --ema_decay or the checkpoint)")
     return parser
 
 
@@ -852,7 +947,8 @@ if __name__ == "__main__":
                         path_to_image_means=params["path_to_image_means"], path_to_image_stds=params["path_to_image_stds"],
                         critic_iters=params["critic_iters"], batch_size=params["batch_size"], lambda_=params["lambda"],
                         resume=params["resume"], synthetic=synthetic, two_streams=not params["single_stream"],
-                        reuse_g_encoder=not params["recompute_generator_encoder"], shuffle_buffer=not params["no_shuffle_buffer"])
+                        reuse_g_encoder=not params["recompute_generator_encoder"], shuffle_buffer=not params["no_shuffle_buffer"],
+                        ema_decay=params["ema_decay"], eval_live=params["eval_live"])
     if params["saliency_dir"]:
         if not gan.load_checkpoint():
             print("--saliency_dir: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
