@@ -134,17 +134,29 @@ int sgg_conv2d_nhwc_fwd_symbol(int B, int Hi, int Wi, int Cin, int Ho, int Wo, i
                                char* buf, int buf_len);
 int sgg_conv2d_nhwc_dgrad_symbol(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l,
                                  int precision, int w_split_layout, int has_w_split, int operand_format, char* buf, int buf_len);
-/* Conv2DBackpropFilter: dw (HWIO) from x and dy.  algo: 0 = automatic (halo-resident kernel where it applies), 1 = per-tap
- * kernels only (A/B measurements). */
+/* Conv2DBackpropFilter: dw (HWIO) from x and dy.  algo: 0 = automatic (the resident kernels where they apply), 1 = per-tap
+ * kernels only (A/B measurements).  One routing decision per launch: which kernel runs, with which template arguments and grid, into
+ * how many partial slabs of the workspace (summed by one deterministic reduce launch) follows from the scalar arguments alone -
+ * sgg_conv2d_nhwc_wgrad_symbol reports it.  The launch needs exactly the workspace the query reports (none where a per-tap kernel
+ * writes dw directly); sgg_conv2d_nhwc_wgrad_workspace_bytes, which knows neither precision nor stride, is an upper bound of it. */
 size_t sgg_conv2d_nhwc_wgrad_workspace_bytes(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW);
 int sgg_conv2d_nhwc_wgrad(const float* x, const float* dy, float* dw_hwio, int B, int Hi, int Wi, int Cin, int Ho,
                           int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int precision, int algo,
                           const float* amax_x, const float* amax_dy, const float* ln_stats, const float* ln_gamma, const float* ln_beta,
                           int operand_format, void* workspace, size_t workspace_bytes, void* stream);
+/* The convolution kernels the launch with these arguments starts, as sgg_conv2d_nhwc_fwd_symbol spells them, in launch order and
+ * separated by ';' into buf (buf_len >= 256): one for stride 1, the four tap-parity classes for a 5x5 stride-2 layer on the resident
+ * kernels (e.g. conv_wgrad_dma_kernel<4,3,2>;...); the slab reduce is not listed.  has_ln: ln_stats would not be NULL (gamma, beta,
+ * the required operands and the amax words count as given).  *workspace_bytes (may be NULL) receives the launch's exact need.  The
+ * launch's own validation and route: what it refuses is refused here in the same way (sgg_last_error).  No GPU needed. */
+int sgg_conv2d_nhwc_wgrad_symbol(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l,
+                                 int precision, int algo, int has_ln, int operand_format, size_t* workspace_bytes, char* buf, int buf_len);
 /* 0: the per-tap kernels serve this shape; 1: the halo-resident kernel does with algo 0 (it takes pre-split operands and stages them
  * through registers, without arithmetic); 2: as 1, and when BOTH operands are pre-split (operand_format 3, precision 2, no LN prologue)
  * the LDS-DMA kernel runs instead: 64 x 128 / 64 x 64 channel tiles, both operands copied HBM -> LDS by `buffer_load ... lds`, no
- * staging registers or arithmetic (csrc/conv_wgrad_dma.hip; channels % 64 == 0, 8-divisible grids or row bands of <= 112 pixels) */
+ * staging registers or arithmetic (csrc/conv_wgrad_dma.hip; channels % 64 == 0, 8-divisible grids or row bands of <= 112 pixels).
+ * Read off the route of the SAME-padded launch (x grid = stride x the Ho x Wo grid); where that launch would be refused the answer
+ * is 0 and sgg_last_error holds the reason. */
 int sgg_conv2d_nhwc_wgrad_resident(int B, int Ho, int Wo, int Cin, int Cout, int KH, int KW, int stride, int precision);
 
 /* ---- tf.contrib.layers.layer_norm(activation_fn=tf.nn.elu) over (H,W,C) per sample ------------------------

@@ -99,43 +99,49 @@ HaloPcRoute sgg_halo_pc_route(const HaloParams& p, int precision);
 int sgg_halo_pc_launch(const HaloPcRoute& r, const HaloParams& p, hipStream_t st);
 void sgg_halo_pc_symbol(const HaloPcRoute& r, char* buf, size_t len);
 
-// ---- halo-resident 3x3 stride-1 wgrad (conv_wgrad_halo.hip) ---------------------------------------------------
-struct WgradHaloPlan {
-  int ct, nt;           // channel chunk of a workgroup: 32*ct input x 32*nt output channels
-  int nbs;              // 8x8 blocks staged together
-  int spw;              // partial slabs a workgroup writes (waves that split the pixels of a chunk)
-  int pairs, pairs_n;   // (Cin chunk, Cout chunk) pairs; Cout chunks
-  int nsplit;           // workgroups along the pixel dimension
-  int stages;           // stages per workgroup
-  int nslabs;           // nsplit * spw
-  int geo;              // 0: 8x8 pixel blocks;  1: row bands (R full-width rows, up to 112 pixels) for grids that 8x8 blocks do not tile
-  int R, pc, xslots;    // geo 1: rows per band, patch pitch (W + 1: one shared zero column), patch slots ((R + 2) * pc + 1)
-  size_t ws_bytes;
+// ---- filter gradient (conv_wgrad.hip; resident kernels: conv_wgrad_halo.hip, conv_wgrad_dma.hip) ------------------------------------
+// One route per launch, as above: wgrad_route (conv_wgrad.hip) validates the launch's scalars and fills it, sgg_conv2d_nhwc_wgrad
+// switches on the family, sgg_conv2d_nhwc_wgrad_symbol prints it, sgg_conv2d_nhwc_wgrad_resident reads its family.
+enum { WGRAD_C3, WGRAD_TAP, WGRAD_TAP_TR, WGRAD_HALO, WGRAD_HALO_RB, WGRAD_DMA, WGRAD_DMA_RB };
+// The taps of one launch of the resident kernels.  Stride 1: one class, all 3x3 taps.  5x5 stride 2: the four parity classes (cy, cx)
+// of the x pixels, each a stride-1 problem on the sub-sampled x grid: taps kh with (kh - pad_t) mod 2 == cy, kh = kh0 + 2 ia, which
+// read sub-grid pixel (oy + a0y + ia, ox + a0x + ib).
+struct WgradTapClass {
+  int cy, cx, a0y, a0x, kh0, kw0;
+  int nkh, nkw;           // taps of the class: the kernels' NKH x NKW
 };
-// returns 1 and fills the plan if the shape is served (H, W = the dy grid; 3x3 stride 1 or 5x5 stride 2; channels % 32 == 0;
-// H % 8 == W % 8 == 0, or - channels % 64 == 0 - any H with W <= 28: row bands)
-int sgg_wgrad_halo_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, WgradHaloPlan* pl);
-// writes pl.nslabs partial dW slabs [slab][9][Cin][Cout] (unscaled f32) into `slabs`
-// operand_format: bit 0 = x, bit 1 = dy is a pre-split ("S16") tensor (split16.h)
-void sgg_wgrad_halo_launch(const float* x, const float* dy, float* slabs, int B, int H, int W, int Cin, int Cout, int stride,
-                           int pad_t, int pad_l, int precision, const float* amax_x, const float* amax_dy, const WgradHaloPlan& pl,
-                           hipStream_t st, const float* ln_stats = nullptr, const float* ln_gamma = nullptr,
-                           const float* ln_beta = nullptr, int operand_format = 0);
-
-// ---- filter gradient on pre-split operands staged by LDS-DMA (conv_wgrad_dma.hip) ---------------------------------------------
-struct WgradDmaPlan {
-  int nt;               // 32-column output tiles of a workgroup: 4 (64 x 128 channel tile) or 2 (64 x 64, two pixel halves)
-  int spw;              // partial slabs a workgroup writes
-  int pairs, pairs_n;   // channel tiles; Cout tiles
-  int nsplit, stages, nslabs;
-  int geo, R, pc, xslots; // geo 1: row bands as WgradHaloPlan (grids that 8x8 blocks do not tile; 64 x 64 tiles)
-  size_t ws_bytes;
+struct WgradRoute {
+  int family;
+  // template arguments.  WGRAD_C3: conv_c3_wgrad_kernel<false>; _TAP: conv_wgrad_kernel<BMC, BNC, WM, WN, P, HALF>; _TAP_TR:
+  // conv_wgrad_tr_kernel<P, HALF>; _HALO / _HALO_RB: conv_wgrad_halo3_kernel<CT, NT, HALF, CT == NT, NKH, NKW, LNP, GEO = 0 / 1, ONE>;
+  // _DMA: conv_wgrad_dma_kernel<NT, NKH, NKW>; _DMA_RB: conv_wgrad_dma_rb_kernel<NKH, NKW>  (NKH, NKW: of each tap class)
+  int BMC, BNC, WM, WN, P;
+  int CT, NT;             // channel chunk of a resident workgroup: 32*CT input x 32*NT output channels
+  bool HALF, LNP, ONE;
+  dim3 grid;
+  int nslabs;             // partial dW slabs [slab][taps][Cin][Cout] the launch writes; the slab reduce sums them into dw
+  size_t ws_bytes;        // of those slabs; 0: a single slab, written straight into dw (per-tap kernels only)
+  int ncls;
+  WgradTapClass cls[4];   // resident families: one launch per class, in this order
+  // launch geometry that goes into the kernels' params
+  int tiles, chunk;       // _C3: 8 x 32 pixel tiles, tiles per workgroup;  _TAP*: channel tiles, pixels per split
+  int stages;             // resident: stages per workgroup
+  int R, pc, xslots;      // row bands (_RB): rows per band (R * W <= 112 pixels), patch pitch (W + 1: one shared zero column), patch slots
 };
-// returns 1 and fills the plan if the shape is served (H, W = the dy grid: divisible by 8, or row bands of up to 112 pixels; 3x3 stride 1 or 5x5 stride 2; channels % 64 == 0)
-int sgg_wgrad_dma_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, WgradDmaPlan* pl);
-// x, dy: pre-split ("S16") tensors; writes pl.nslabs partial dW slabs [slab][taps][Cin][Cout] (unscaled f32) into `slabs`
-void sgg_wgrad_dma_launch(const void* x, const void* dy, float* slabs, int B, int H, int W, int Cin, int Cout, int stride, int pad_t,
-                          int pad_l, const float* amax_x, const float* amax_dy, const WgradDmaPlan& pl, hipStream_t st);
+// (cy, cx, ...) of a tap class, the tap step and the slab layout into either resident kernel's params
+template <class Params>
+inline void sgg_wgrad_set_class(Params& p, const WgradTapClass& c, int stride) {
+  p.cy = c.cy; p.cx = c.cx; p.a0y = c.a0y; p.a0x = c.a0x; p.kh0 = c.kh0; p.kw0 = c.kw0;
+  p.kstep = stride; p.KWt = stride == 1 ? 3 : 5; p.taps_total = p.KWt * p.KWt;
+}
+// H, W: the dy grid.  One launch per tap class of the route, each writing r.nslabs partial slabs (unscaled f32) into `slabs`.
+// SGG_OK, or SGG_ERR_ARG: no such instantiation.
+// halo: operand_format bit 0 = x, bit 1 = dy is a pre-split ("S16") tensor (split16.h); dma: both are
+int sgg_wgrad_halo_launch(const WgradRoute& r, const float* x, const float* dy, float* slabs, int B, int H, int W, int Cin, int Cout,
+                          int stride, const float* amax_x, const float* amax_dy, const float* ln_stats, const float* ln_gamma,
+                          const float* ln_beta, int operand_format, hipStream_t st);
+int sgg_wgrad_dma_launch(const WgradRoute& r, const void* x, const void* dy, float* slabs, int B, int H, int W, int Cin, int Cout, int stride,
+                         const float* amax_x, const float* amax_dy, hipStream_t st);
 
 // ---- band-resident 5x5 stride-2 convolution, forward and dgrad (conv_s2.hip) -----------------------------------------
 struct S2Params {

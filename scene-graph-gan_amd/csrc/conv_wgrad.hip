@@ -635,55 +635,196 @@ __global__ __launch_bounds__(256, LNB ? 2 : 3) void conv_c3_wgrad_kernel(const f
 // ---------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------
-struct WgradPlan {
-  int bmc, bnc, tiles, nsplit, chunk;
-  size_t ws_bytes;
-};
-
 constexpr int SGG_WGRAD_WGS = 1536;   // workgroups aimed at by the pixel split of the per-tap wgrad kernels
-static WgradPlan wgrad_plan(int B, int Ho, int Wo, int Cin, int Cout, int KH, int KW) {
-  WgradPlan pl;
+// the per-tap kernels' (and conv1_1's) work decomposition into r: channel tile, tiles, pixels (Cin = 3: tiles) per split, slabs
+static void wgrad_tap_plan(WgradRoute& r, int B, int Ho, int Wo, int Cin, int Cout, int KH, int KW) {
   const long long mpix = (long long)B * Ho * Wo;
   if (Cin == 3) {        // tiles of 8 x 32 pixels, `chunk` tiles per workgroup, one slab per workgroup
-    pl.bmc = 27; pl.bnc = 32;
-    pl.tiles = B * sgg_cdiv(Ho, 8) * sgg_cdiv(Wo, 32);
-    pl.chunk = sgg_cdiv(pl.tiles, 1024);
-    pl.nsplit = sgg_cdiv(pl.tiles, pl.chunk);
-    pl.ws_bytes = (size_t)pl.nsplit * 27 * 32 * sizeof(float);
-    return pl;
+    r.BMC = 27; r.BNC = 32;
+    r.tiles = B * sgg_cdiv(Ho, 8) * sgg_cdiv(Wo, 32);
+    r.chunk = sgg_cdiv(r.tiles, 1024);
+    r.nslabs = sgg_cdiv(r.tiles, r.chunk);
+    r.ws_bytes = (size_t)r.nslabs * 27 * 32 * sizeof(float);
+    return;
   }
-  pl.bmc = Cin >= 128 ? 128 : Cin;
-  pl.bnc = Cout >= 128 ? 128 : Cout;
-  pl.tiles = (Cin / pl.bmc) * (Cout / pl.bnc);
-  const int base = pl.tiles * KH * KW;
+  r.BMC = Cin >= 128 ? 128 : Cin;
+  r.BNC = Cout >= 128 ? 128 : Cout;
+  r.tiles = (Cin / r.BMC) * (Cout / r.BNC);
+  const int base = r.tiles * KH * KW;
   int ns = (SGG_WGRAD_WGS + base - 1) / base;
   const long long max_ns = mpix / 512 > 0 ? mpix / 512 : 1;
   if (ns > max_ns) ns = (int)max_ns;
   if (ns < 1) ns = 1;
-  pl.chunk = (int)(((mpix + ns - 1) / ns + 31) / 32 * 32);
-  pl.nsplit = (int)((mpix + pl.chunk - 1) / pl.chunk);
-  pl.ws_bytes = pl.nsplit > 1 ? (size_t)pl.nsplit * KH * KW * Cin * Cout * sizeof(float) : 0;
-  return pl;
+  r.chunk = (int)(((mpix + ns - 1) / ns + 31) / 32 * 32);
+  r.nslabs = (int)((mpix + r.chunk - 1) / r.chunk);
+  r.ws_bytes = r.nslabs > 1 ? (size_t)r.nslabs * KH * KW * Cin * Cout * sizeof(float) : 0;
 }
 
+// The resident kernels' work decomposition (conv_wgrad_halo.hip; dma: conv_wgrad_dma.hip) into r: channel chunk, grid, slabs, stage
+// geometry.  Returns 0 (8x8 pixel blocks), 1 (row bands: grids that blocks do not tile) or -1: shape not served.  H, W: the dy grid;
+// 3x3 stride 1 (x grid = dy grid) or 5x5 stride 2 (x grid = 2H x 2W); channels % 32 == 0 (dma, row bands: % 64).
+static int wgrad_block_plan(WgradRoute& r, bool dma, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride) {
+  const bool k3 = KH == 3 && KW == 3 && stride == 1, k5 = KH == 5 && KW == 5 && stride == 2;
+  const int cm = dma ? 64 : 32;
+  if (!((k3 || k5) && B > 0 && H > 0 && W > 0 && Cin % cm == 0 && Cout % cm == 0)) return -1;
+  if ((size_t)B * H * W * stride * stride * Cin * sizeof(float) >= 0x80000000ull || (size_t)B * H * W * Cout * sizeof(float) >= 0x80000000ull)
+    return -1;
+  const int geo = (H % 8 != 0 || W % 8 != 0) ? 1 : 0;
+  int R = 8, pc = 12, xslots = 120;     // blocks: 10 patch rows of pitch 12
+  if (geo) {
+    // R full-width rows with R * W <= 112 pixels (seven 16-pixel MFMA steps); patch of R + 2 rows of pitch W + 1 (one zero slot per row:
+    // right halo of row r, left halo of row r + 1) and one more slot, <= 176; 64 x 64 channel chunks only
+    R = 112 / W < H ? 112 / W : H;
+    while (R > 0 && (R + 2) * (W + 1) + 1 > 176) --R;
+    if (R < 1 || Cin % 64 != 0 || Cout % 64 != 0) return -1;
+    pc = W + 1; xslots = (R + 2) * pc + 1;
+  }
+  // halo: 32*CT x 32*NT channels on four waves; dma: 64 x 128 on eight, or 64 x 64 with a block's pixels split over two wave groups
+  r.CT = (dma || (Cin % 64 == 0 && Cout % 64 == 0)) ? 2 : 1;
+  r.NT = dma ? ((geo || Cout % 128 != 0) ? 2 : 4) : (Cout % 64 == 0 ? 2 : 1);
+  const int spw = dma ? (r.NT == 4 ? 1 : 2) : 4 / (r.CT * r.NT);      // slabs per workgroup: waves that split the pixels of a chunk
+  const int pairs = (Cin / (32 * r.CT)) * (Cout / (32 * r.NT));
+  const int nblk = geo ? B * sgg_cdiv(H, R) : B * (H / 8) * (W / 8);
+  const int total_stages = sgg_cdiv(nblk, r.CT == 2 ? 1 : 2);         // (32-channel chunks stage two blocks together)
+  // one resident round: two 4-wave workgroups (halo) or one 8-wave workgroup (dma) per CU, each with at least 8 resp. 4 stages
+  int ns = (dma ? 256 : 512) / pairs;
+  if (ns > total_stages / (dma ? 4 : 8)) ns = total_stages / (dma ? 4 : 8);
+  if (ns < 1) ns = 1;
+  r.stages = sgg_cdiv(total_stages, ns);
+  r.grid = dim3(sgg_cdiv(total_stages, r.stages), pairs);
+  r.nslabs = r.grid.x * spw;
+  r.ws_bytes = (size_t)r.nslabs * KH * KW * Cin * Cout * sizeof(float);
+  r.R = R; r.pc = pc; r.xslots = xslots;
+  return geo;
+}
+
+// The tap classes of a resident launch (WgradTapClass): stride^2 of them, the x pixels of parity (cy, cx).
+static int wgrad_tap_classes(int K, int stride, int pad_t, int pad_l, WgradTapClass* cls) {
+  int n = 0;
+  for (int cy = 0; cy < stride; ++cy)
+    for (int cx = 0; cx < stride; ++cx) {
+      WgradTapClass& c = cls[n++];
+      c.cy = cy; c.cx = cx;
+      c.kh0 = (pad_t + cy) % stride; c.kw0 = (pad_l + cx) % stride;
+      c.a0y = (c.kh0 - pad_t - cy) / stride;           // exact: kh0 - pad_t - cy is a multiple of the stride (and <= 0)
+      c.a0x = (c.kw0 - pad_l - cx) / stride;
+      c.nkh = (K - c.kh0 + stride - 1) / stride; c.nkw = (K - c.kw0 + stride - 1) / stride;
+    }
+  return n;
+}
+
+// Validates a launch and routes it: scalars only (has_*: that operand would not be NULL), no HIP call.
+static int wgrad_route(WgradRoute& r, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l,
+                       int precision, int algo, bool has_amax, bool has_ln, bool has_ln_params, int operand_format) {
+  SGG_CHECK_ARG(operand_format >= 0 && operand_format <= 3 && (operand_format == 0 || (sgg_prec_half(precision) && Cin != 3 && algo == 0)) &&
+                    !((operand_format & 1) && has_ln),
+                "sgg_conv2d_nhwc_wgrad: pre-split (S16) operands need precision 1 / 2 and the halo-resident kernel (algo 0); x with an LN "
+                "prologue is the f32 pre-LayerNorm tensor");
+  SGG_CHECK_ARG(!has_ln || has_ln_params, "sgg_conv2d_nhwc_wgrad: the LN prologue needs stats, gamma and beta");
+  SGG_CHECK_ARG(algo == 0 || algo == 1, "sgg_conv2d_nhwc_wgrad: algo must be 0 (auto) or 1 (per-tap kernels only)");
+  SGG_CHECK_ARG(precision == 0 || (precision >= 1 && precision <= 4) || precision == 6,
+                "sgg_conv2d_nhwc_wgrad: precision must be 0, 1, 2, 3, 4 or 6");
+  SGG_CHECK_ARG(!sgg_prec_half(precision) || Cin == 3 || has_amax, "sgg_conv2d_nhwc_wgrad: precision 1 / 2 need the amax words");
+  SGG_CHECK_ARG(!has_ln || !sgg_prec_one(precision), "sgg_conv2d_nhwc_wgrad: the LN prologue exists in the two-piece modes (2, 3) only");
+  SGG_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && stride >= 1 && stride <= 2, "sgg_conv2d_nhwc_wgrad: bad dims");
+  SGG_CHECK_ARG((long long)B * Hi * Wi * Cin < (1LL << 31) && (long long)B * Ho * Wo * Cout < (1LL << 31),
+                "sgg_conv2d_nhwc_wgrad: tensor exceeds 2^31 elements");
+  r = WgradRoute{};
+  r.HALF = sgg_prec_half(precision); r.ONE = sgg_prec_one(precision); r.LNP = has_ln; r.ncls = 1;
+  // the resident kernels: SAME padding on an x grid of stride x the dy grid, algo 0, the single- and two-piece 16-bit modes
+  const bool same = pad_t == 1 && pad_l == 1 && Hi == Ho * stride && Wi == Wo * stride && algo == 0 && Cin != 3;
+  // LDS-DMA staging where both operands come pre-split; else the halo-resident kernel, which splits f32 operands itself and has the
+  // LN prologue on 8x8 blocks
+  const bool try_dma = same && operand_format == 3 && precision == 2 && !has_ln;
+  int geo = try_dma ? wgrad_block_plan(r, true, B, Ho, Wo, Cin, Cout, KH, KW, stride) : -1;
+  const bool dma = geo >= 0;
+  if (!dma && same && sgg_prec_resident(precision)) geo = wgrad_block_plan(r, false, B, Ho, Wo, Cin, Cout, KH, KW, stride);
+  if (geo >= 0 && !(geo == 1 && has_ln)) {
+    r.family = dma ? (geo ? WGRAD_DMA_RB : WGRAD_DMA) : (geo ? WGRAD_HALO_RB : WGRAD_HALO);
+    r.ncls = wgrad_tap_classes(KH, stride, pad_t, pad_l, r.cls);
+    return SGG_OK;
+  }
+  SGG_CHECK_ARG(operand_format == 0, "sgg_conv2d_nhwc_wgrad: pre-split (S16) operands are served by the halo-resident kernel only");
+  SGG_CHECK_ARG(!has_ln, "sgg_conv2d_nhwc_wgrad: the LN prologue is served by the halo-resident kernel only (3x3 stride 1 or 5x5 "
+                         "stride 2 on grids divisible by 8, precision 2 or 3, algo 0)");
+  wgrad_tap_plan(r, B, Ho, Wo, Cin, Cout, KH, KW);
+  if (Cin == 3) {
+    SGG_CHECK_ARG(KH == 3 && KW == 3 && stride == 1 && Cout == 32, "sgg_conv2d_nhwc_wgrad: Cin=3 path needs 3x3 s1 Cout=32");
+    r.family = WGRAD_C3;
+    r.grid = dim3(r.nslabs);
+    return SGG_OK;
+  }
+  SGG_CHECK_ARG(Cin % 32 == 0 && Cout % 32 == 0, "sgg_conv2d_nhwc_wgrad: Cin and Cout must be multiples of 32 (or Cin == 3)");
+  SGG_CHECK_ARG(r.BMC == 32 || r.BMC == 64 || r.BMC == 128, "sgg_conv2d_nhwc_wgrad: unsupported Cin tile");
+  SGG_CHECK_ARG(r.BNC == 32 || r.BNC == 64 || r.BNC == 128, "sgg_conv2d_nhwc_wgrad: unsupported Cout tile");
+  // multiply-high division is exact while n * d < 2^32 (n = pixel index + 31, d = Wo; then n / Wo and Ho)
+  SGG_CHECK_ARG(Ho >= 2 && Wo >= 2, "sgg_conv2d_nhwc_wgrad: output grid must be at least 2x2");
+  SGG_CHECK_ARG(((unsigned long long)B * Ho * Wo + 64) * (unsigned long long)Wo < 0x100000000ull &&
+                    (size_t)B * Hi * Wi * Cin * sizeof(float) < 0x80000000ull && (size_t)B * Ho * Wo * Cout * sizeof(float) < 0x80000000ull,
+                "sgg_conv2d_nhwc_wgrad: tensor too large for the 32-bit offset path");
+  precision = sgg_prec_general(precision);      // (the per-tap kernels have no single-piece variant: modes 1 / 4 run as 2 / 3 here)
+  r.P = precision == 0 ? 0 : (precision == 6 ? 3 : 2);
+  r.ONE = false;
+  // 128 x 128 channel tiles in the split modes: split once at the LDS write, transposing LDS reads (conv_wgrad_tr_kernel)
+  r.family = (r.BMC == 128 && r.BNC == 128 && r.P != 0) ? WGRAD_TAP_TR : WGRAD_TAP;
+  r.WM = (r.BMC == 128 && r.BNC >= 64) ? 64 : 32;     // wave tiles: 32 x 32 channels, 64 along a 128-channel side once the other side has 64
+  r.WN = (r.BNC == 128 && r.BMC >= 64) ? 64 : 32;
+  r.grid = dim3(r.tiles, KH * KW, r.nslabs);
+  return SGG_OK;
+}
+
+// as rocprofv3 names the kernels of the launch (spaces removed), in launch order, ';' between the tap classes
+static void wgrad_symbol(const WgradRoute& r, char* buf, size_t len) {
+  size_t n = 0;
+  for (int i = 0; i < r.ncls && n < len; ++i) {
+    const WgradTapClass& c = r.cls[i];
+    const char* sep = i ? ";" : "";
+    if (r.family == WGRAD_C3) n += snprintf(buf, len, "conv_c3_wgrad_kernel<false>");
+    else if (r.family == WGRAD_TAP) n += snprintf(buf, len, "conv_wgrad_kernel<%d,%d,%d,%d,%d,%s>", r.BMC, r.BNC, r.WM, r.WN, r.P, sgg_tf(r.HALF));
+    else if (r.family == WGRAD_TAP_TR) n += snprintf(buf, len, "conv_wgrad_tr_kernel<%d,%s>", r.P, sgg_tf(r.HALF));
+    else if (r.family == WGRAD_DMA) n += snprintf(buf + n, len - n, "%sconv_wgrad_dma_kernel<%d,%d,%d>", sep, r.NT, c.nkh, c.nkw);
+    else if (r.family == WGRAD_DMA_RB) n += snprintf(buf + n, len - n, "%sconv_wgrad_dma_rb_kernel<%d,%d>", sep, c.nkh, c.nkw);
+    else      // (fourth argument: the next stage is loaded under the MFMAs, except by the 32 x 64 chunks)
+      n += snprintf(buf + n, len - n, "%sconv_wgrad_halo3_kernel<%d,%d,%s,%s,%d,%d,%s,%d,%s>", sep, r.CT, r.NT, sgg_tf(r.HALF),
+                    sgg_tf(r.CT == r.NT), c.nkh, c.nkw, sgg_tf(r.LNP), r.family == WGRAD_HALO_RB, sgg_tf(r.ONE));
+  }
+}
+
+static int launch_tap(const WgradRoute& r, const WgradParams& p, hipStream_t st);
+
+// (precision and stride are not known here: an upper bound over the per-tap and both resident decompositions)
 extern "C" size_t sgg_conv2d_nhwc_wgrad_workspace_bytes(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH,
                                                         int KW) {
-  size_t need = wgrad_plan(B, Ho, Wo, Cin, Cout, KH, KW).ws_bytes;
-  WgradHaloPlan hp;     // (precision and stride are not known here: upper bound over both kernels)
+  WgradRoute r;
+  wgrad_tap_plan(r, B, Ho, Wo, Cin, Cout, KH, KW);
+  size_t need = r.ws_bytes;
   const int st_guess = (Hi == Ho && Wi == Wo) ? 1 : ((Hi == 2 * Ho && Wi == 2 * Wo) ? 2 : 0);
-  if (st_guess && Cin != 3 && sgg_wgrad_halo_plan(B, Ho, Wo, Cin, Cout, KH, KW, st_guess, &hp) && hp.ws_bytes > need) need = hp.ws_bytes;
-  WgradDmaPlan dp;
-  if (st_guess && Cin != 3 && sgg_wgrad_dma_plan(B, Ho, Wo, Cin, Cout, KH, KW, st_guess, &dp) && dp.ws_bytes > need) need = dp.ws_bytes;
+  for (int dma = 0; dma < 2; ++dma)
+    if (st_guess && Cin != 3 && wgrad_block_plan(r, dma, B, Ho, Wo, Cin, Cout, KH, KW, st_guess) >= 0 && r.ws_bytes > need) need = r.ws_bytes;
   return need;
 }
 
-// 0: per-tap kernels (or conv1_1's own); 1: the halo-resident kernel (takes pre-split operands, stages them through registers);
-// 2: with BOTH operands pre-split in precision 2 the LDS-DMA kernel runs instead (conv_wgrad_dma.hip)
+// 0 / 1 / 2 (include/sgg_hip.h): the family of the SAME-padded launch with algo 0 - in precision 2 that of pre-split operands, which
+// the LDS-DMA kernel takes where it serves the shape and the halo-resident kernel elsewhere
 extern "C" int sgg_conv2d_nhwc_wgrad_resident(int B, int Ho, int Wo, int Cin, int Cout, int KH, int KW, int stride, int precision) {
-  WgradHaloPlan hp;
-  if (!(sgg_prec_resident(precision) && Cin != 3 && B > 0 && sgg_wgrad_halo_plan(B, Ho, Wo, Cin, Cout, KH, KW, stride, &hp))) return 0;
-  WgradDmaPlan dp;
-  return (precision == 2 && sgg_wgrad_dma_plan(B, Ho, Wo, Cin, Cout, KH, KW, stride, &dp)) ? 2 : 1;
+  WgradRoute r;
+  if (wgrad_route(r, B, Ho * stride, Wo * stride, Cin, Ho, Wo, Cout, KH, KW, stride, 1, 1, precision, 0, true, false, false,
+                  precision == 2 ? 3 : 0) != SGG_OK)
+    return 0;
+  return r.family >= WGRAD_DMA ? 2 : (r.family >= WGRAD_HALO ? 1 : 0);
+}
+
+// The kernels the launch with these arguments starts and the workspace it needs (include/sgg_hip.h): the launch's validation and route.
+extern "C" int sgg_conv2d_nhwc_wgrad_symbol(int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t,
+                                            int pad_l, int precision, int algo, int has_ln, int operand_format, size_t* workspace_bytes,
+                                            char* buf, int buf_len) {
+  WgradRoute r;
+  const int rc = wgrad_route(r, B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l, precision, algo, true, has_ln != 0, true, operand_format);
+  if (rc != SGG_OK) return rc;
+  SGG_CHECK_ARG(buf && buf_len >= 256, "sgg_conv2d_nhwc_wgrad_symbol: the buffer must hold at least 256 bytes");
+  wgrad_symbol(r, buf, (size_t)buf_len);
+  if (workspace_bytes) *workspace_bytes = r.ws_bytes;
+  return SGG_OK;
 }
 
 extern "C" int sgg_conv2d_nhwc_wgrad(const float* x, const float* dy, float* dw, int B, int Hi, int Wi, int Cin, int Ho,
@@ -691,115 +832,76 @@ extern "C" int sgg_conv2d_nhwc_wgrad(const float* x, const float* dy, float* dw,
                                      const float* amax_x, const float* amax_dy, const float* ln_stats, const float* ln_gamma,
                                      const float* ln_beta, int operand_format, void* workspace, size_t workspace_bytes, void* stream) {
   SGG_CHECK_ARG(x && dy && dw, "sgg_conv2d_nhwc_wgrad: null pointer");
-  SGG_CHECK_ARG(operand_format >= 0 && operand_format <= 3 && (operand_format == 0 || (sgg_prec_half(precision) && Cin != 3 && algo == 0)) &&
-                    !((operand_format & 1) && ln_stats),
-                "sgg_conv2d_nhwc_wgrad: pre-split (S16) operands need precision 1 / 2 and the halo-resident kernel (algo 0); x with an LN "
-                "prologue is the f32 pre-LayerNorm tensor");
-  SGG_CHECK_ARG(!ln_stats || (ln_gamma && ln_beta), "sgg_conv2d_nhwc_wgrad: the LN prologue needs stats, gamma and beta");
-  SGG_CHECK_ARG(algo == 0 || algo == 1, "sgg_conv2d_nhwc_wgrad: algo must be 0 (auto) or 1 (per-tap kernels only)");
-  SGG_CHECK_ARG(precision == 0 || (precision >= 1 && precision <= 4) || precision == 6,
-                "sgg_conv2d_nhwc_wgrad: precision must be 0, 1, 2, 3, 4 or 6");
-  SGG_CHECK_ARG(!sgg_prec_half(precision) || Cin == 3 || (amax_x && amax_dy), "sgg_conv2d_nhwc_wgrad: precision 1 / 2 need the amax words");
-  SGG_CHECK_ARG(!ln_stats || !sgg_prec_one(precision), "sgg_conv2d_nhwc_wgrad: the LN prologue exists in the two-piece modes (2, 3) only");
-  SGG_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && stride >= 1 && stride <= 2, "sgg_conv2d_nhwc_wgrad: bad dims");
-  SGG_CHECK_ARG((long long)B * Hi * Wi * Cin < (1LL << 31) && (long long)B * Ho * Wo * Cout < (1LL << 31),
-                "sgg_conv2d_nhwc_wgrad: tensor exceeds 2^31 elements");
+  WgradRoute r;
+  int rc = wgrad_route(r, B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l, precision, algo, amax_x && amax_dy, ln_stats != nullptr,
+                       ln_gamma && ln_beta, operand_format);
+  if (rc != SGG_OK) return rc;
+  if (r.ws_bytes > 0 && (!workspace || workspace_bytes < r.ws_bytes)) {
+    sgg_set_error("sgg_conv2d_nhwc_wgrad: workspace too small (%zu < %zu)", workspace_bytes, r.ws_bytes);
+    return SGG_ERR_WORKSPACE;
+  }
   hipStream_t st = (hipStream_t)stream;
-  const WgradPlan pl = wgrad_plan(B, Ho, Wo, Cin, Cout, KH, KW);
-  if (pl.ws_bytes > 0) {
-    if (!workspace || workspace_bytes < pl.ws_bytes) {
-      sgg_set_error("sgg_conv2d_nhwc_wgrad: workspace too small (%zu < %zu)", workspace_bytes, pl.ws_bytes);
-      return SGG_ERR_WORKSPACE;
+  float* const slabs = r.ws_bytes > 0 ? (float*)workspace : dw;      // (no workspace: the per-tap kernels' single slab is dw itself)
+  switch (r.family) {
+    case WGRAD_C3:
+      hipLaunchKernelGGL(conv_c3_wgrad_kernel<false>, r.grid, dim3(256), 0, st, x, dy, slabs, Hi, Wi, pad_t, pad_l, sgg_cdiv(Wo, 32),
+                         sgg_cdiv(Ho, 8), r.tiles, r.chunk, C3LnArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
+      break;
+    case WGRAD_TAP:
+    case WGRAD_TAP_TR: {
+      WgradParams p;
+      p.x = x; p.dy = dy; p.out = slabs;
+      p.B = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.KH = KH; p.KW = KW;
+      p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
+      p.Mpix = B * Ho * Wo; p.chunk = r.chunk; p.ntile_n = Cout / r.BNC;
+      p.magic_wo = (unsigned)((0x100000000ull + Wo - 1) / Wo);
+      p.magic_ho = (unsigned)((0x100000000ull + Ho - 1) / Ho);
+      p.amax_x = amax_x; p.amax_dy = amax_dy;
+      p.x_bytes = (unsigned)((size_t)B * Hi * Wi * Cin * sizeof(float));
+      p.dy_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * sizeof(float));
+      rc = launch_tap(r, p, st);
+      break;
     }
+    case WGRAD_HALO:
+    case WGRAD_HALO_RB:
+      rc = sgg_wgrad_halo_launch(r, x, dy, slabs, B, Ho, Wo, Cin, Cout, stride, amax_x, amax_dy, ln_stats, ln_gamma, ln_beta, operand_format, st);
+      break;
+    default:
+      rc = sgg_wgrad_dma_launch(r, x, dy, slabs, B, Ho, Wo, Cin, Cout, stride, amax_x, amax_dy, st);
   }
-  const long long nout = (long long)KH * KW * Cin * Cout;
-  WgradDmaPlan dp;
-  if (operand_format == 3 && precision == 2 && !ln_stats && algo == 0 && pad_t == 1 && pad_l == 1 && Hi == Ho * stride &&
-      Wi == Wo * stride && sgg_wgrad_dma_plan(B, Ho, Wo, Cin, Cout, KH, KW, stride, &dp)) {
-    // both operands pre-split: staged by LDS-DMA, no staging arithmetic (conv_wgrad_dma.hip)
-    if (!workspace || workspace_bytes < dp.ws_bytes) {
-      sgg_set_error("sgg_conv2d_nhwc_wgrad: workspace too small (%zu < %zu)", workspace_bytes, dp.ws_bytes);
-      return SGG_ERR_WORKSPACE;
-    }
-    sgg_wgrad_dma_launch(x, dy, (float*)workspace, B, Ho, Wo, Cin, Cout, stride, pad_t, pad_l, amax_x, amax_dy, dp, st);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad(dma)");
-    launch_slab_reduce((const float*)workspace, dw, nout / 4, dp.nslabs, st);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad(dma reduce)");
-    return SGG_OK;
-  }
-  WgradHaloPlan hp;
-  if (sgg_prec_resident(precision) && Cin != 3 && pad_t == 1 && pad_l == 1 && Hi == Ho * stride && Wi == Wo * stride &&
-      algo == 0 && sgg_wgrad_halo_plan(B, Ho, Wo, Cin, Cout, KH, KW, stride, &hp) && !(hp.geo == 1 && ln_stats)) {
-    // halo-resident kernel: the nine taps of a channel chunk from one LDS-resident patch (conv_wgrad_halo.hip)
-    if (!workspace || workspace_bytes < hp.ws_bytes) {
-      sgg_set_error("sgg_conv2d_nhwc_wgrad: workspace too small (%zu < %zu)", workspace_bytes, hp.ws_bytes);
-      return SGG_ERR_WORKSPACE;
-    }
-    sgg_wgrad_halo_launch(x, dy, (float*)workspace, B, Ho, Wo, Cin, Cout, stride, pad_t, pad_l, precision, amax_x, amax_dy, hp, st,
-                          ln_stats, ln_gamma, ln_beta, operand_format);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad(halo)");
-    launch_slab_reduce((const float*)workspace, dw, nout / 4, hp.nslabs, st);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad(halo reduce)");
-    return SGG_OK;
-  }
-  SGG_CHECK_ARG(operand_format == 0, "sgg_conv2d_nhwc_wgrad: pre-split (S16) operands are served by the halo-resident kernel only");
-  SGG_CHECK_ARG(!ln_stats, "sgg_conv2d_nhwc_wgrad: the LN prologue is served by the halo-resident kernel only (3x3 stride 1 or 5x5 "
-                           "stride 2 on grids divisible by 8, precision 2 or 3, algo 0)");
-  if (Cin == 3) {
-    SGG_CHECK_ARG(KH == 3 && KW == 3 && stride == 1 && Cout == 32, "sgg_conv2d_nhwc_wgrad: Cin=3 path needs 3x3 s1 Cout=32");
-    hipLaunchKernelGGL(conv_c3_wgrad_kernel<false>, dim3(pl.nsplit), dim3(256), 0, st, x, dy, (float*)workspace, Hi, Wi, pad_t, pad_l,
-                       sgg_cdiv(Wo, 32), sgg_cdiv(Ho, 8), pl.tiles, pl.chunk, C3LnArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad(c3)");
-    launch_slab_reduce((const float*)workspace, dw, nout / 4, pl.nsplit, st);
-    SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad(c3 reduce)");
-    return SGG_OK;
-  }
-  SGG_CHECK_ARG(Cin % 32 == 0 && Cout % 32 == 0, "sgg_conv2d_nhwc_wgrad: Cin and Cout must be multiples of 32 (or Cin == 3)");
-  SGG_CHECK_ARG(pl.bmc == 32 || pl.bmc == 64 || pl.bmc == 128, "sgg_conv2d_nhwc_wgrad: unsupported Cin tile");
-  SGG_CHECK_ARG(pl.bnc == 32 || pl.bnc == 64 || pl.bnc == 128, "sgg_conv2d_nhwc_wgrad: unsupported Cout tile");
-  WgradParams p;
-  p.x = x; p.dy = dy; p.out = pl.nsplit > 1 ? (float*)workspace : dw;
-  p.B = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.KH = KH; p.KW = KW;
-  p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-  p.Mpix = B * Ho * Wo; p.chunk = pl.chunk; p.ntile_n = Cout / pl.bnc;
-  p.magic_wo = (unsigned)((0x100000000ull + Wo - 1) / Wo);
-  p.magic_ho = (unsigned)((0x100000000ull + Ho - 1) / Ho);
-  p.amax_x = amax_x; p.amax_dy = amax_dy;
-  p.x_bytes = (unsigned)((size_t)B * Hi * Wi * Cin * sizeof(float));
-  p.dy_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * sizeof(float));
-  // multiply-high division is exact while n * d < 2^32 (n = pixel index + 31, d = Wo; then n / Wo and Ho)
-  SGG_CHECK_ARG(Ho >= 2 && Wo >= 2, "sgg_conv2d_nhwc_wgrad: output grid must be at least 2x2");
-  SGG_CHECK_ARG(((unsigned long long)B * Ho * Wo + 64) * (unsigned long long)Wo < 0x100000000ull &&
-                    (size_t)B * Hi * Wi * Cin * sizeof(float) < 0x80000000ull && (size_t)B * Ho * Wo * Cout * sizeof(float) < 0x80000000ull,
-                "sgg_conv2d_nhwc_wgrad: tensor too large for the 32-bit offset path");
-  dim3 grid(pl.tiles, KH * KW, pl.nsplit);
-  precision = sgg_prec_general(precision);      // (the per-tap kernels have no single-piece variant: modes 1 / 4 run as 2 / 3 here)
-#define SGG_WG(BMC, BNC, WM, WN)                                                                        \
-  do {                                                                                                \
-    if (precision == 0) hipLaunchKernelGGL((conv_wgrad_kernel<BMC, BNC, WM, WN, 0, false>), grid, dim3(256), 0, st, p);      \
-    else if (precision == 2) hipLaunchKernelGGL((conv_wgrad_kernel<BMC, BNC, WM, WN, 2, true>), grid, dim3(256), 0, st, p);  \
-    else if (precision == 3) hipLaunchKernelGGL((conv_wgrad_kernel<BMC, BNC, WM, WN, 2, false>), grid, dim3(256), 0, st, p); \
-    else hipLaunchKernelGGL((conv_wgrad_kernel<BMC, BNC, WM, WN, 3, false>), grid, dim3(256), 0, st, p);                     \
-  } while (0)
-  if (pl.bmc == 32 && pl.bnc == 32) SGG_WG(32, 32, 32, 32);
-  else if (pl.bmc == 32 && pl.bnc == 64) SGG_WG(32, 64, 32, 32);
-  else if (pl.bmc == 64 && pl.bnc == 32) SGG_WG(64, 32, 32, 32);
-  else if (pl.bmc == 64 && pl.bnc == 64) SGG_WG(64, 64, 32, 32);
-  else if (pl.bmc == 32 && pl.bnc == 128) SGG_WG(32, 128, 32, 32);
-  else if (pl.bmc == 128 && pl.bnc == 32) SGG_WG(128, 32, 32, 32);
-  else if (pl.bmc == 64 && pl.bnc == 128) SGG_WG(64, 128, 32, 64);
-  else if (pl.bmc == 128 && pl.bnc == 64) SGG_WG(128, 64, 64, 32);
-  else if (precision == 2) hipLaunchKernelGGL((conv_wgrad_tr_kernel<2, true>), grid, dim3(256), 0, st, p);
-  else if (precision == 3) hipLaunchKernelGGL((conv_wgrad_tr_kernel<2, false>), grid, dim3(256), 0, st, p);
-  else if (precision == 6) hipLaunchKernelGGL((conv_wgrad_tr_kernel<3, false>), grid, dim3(256), 0, st, p);
-  else SGG_WG(128, 128, 64, 64);
-#undef SGG_WG
+  if (rc != SGG_OK) return rc;
   SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad");
-  if (pl.nsplit > 1) {
-    launch_slab_reduce((const float*)workspace, dw, nout / 4, pl.nsplit, st);
+  if (r.ws_bytes > 0) {     // sums the slabs in a fixed order (a copy where the kernels of the family wrote a single one)
+    launch_slab_reduce(slabs, dw, (long long)KH * KW * Cin * Cout / 4, r.nslabs, st);
     SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad(reduce)");
   }
   return SGG_OK;
+}
+
+// the per-tap instantiations: nine channel tiles x (f32, fp16 pieces, two and three bf16 pieces); 128 x 128 split: conv_wgrad_tr_kernel
+static int launch_tap(const WgradRoute& r, const WgradParams& p, hipStream_t st) {
+#define SGG_WG(BMC_, BNC_, WM_, WN_, P_, HALF_)                                                                                   \
+  SGG_LAUNCH_ARM(r.family == WGRAD_TAP && r.BMC == BMC_ && r.BNC == BNC_ && r.WM == WM_ && r.WN == WN_ && r.P == P_ && r.HALF == HALF_, \
+                 (conv_wgrad_kernel<BMC_, BNC_, WM_, WN_, P_, HALF_>), r.grid, dim3(256), 0, st, p)
+#define SGG_WG_TILE(BMC, BNC, WM, WN) \
+  SGG_WG(BMC, BNC, WM, WN, 0, false) SGG_WG(BMC, BNC, WM, WN, 2, true) SGG_WG(BMC, BNC, WM, WN, 2, false) SGG_WG(BMC, BNC, WM, WN, 3, false)
+#define SGG_WT(P_, HALF_) \
+  SGG_LAUNCH_ARM(r.family == WGRAD_TAP_TR && r.P == P_ && r.HALF == HALF_, (conv_wgrad_tr_kernel<P_, HALF_>), r.grid, dim3(256), 0, st, p)
+  SGG_WG_TILE(32, 32, 32, 32)
+  SGG_WG_TILE(32, 64, 32, 32)
+  SGG_WG_TILE(64, 32, 32, 32)
+  SGG_WG_TILE(64, 64, 32, 32)
+  SGG_WG_TILE(32, 128, 32, 32)
+  SGG_WG_TILE(128, 32, 32, 32)
+  SGG_WG_TILE(64, 128, 32, 64)
+  SGG_WG_TILE(128, 64, 64, 32)
+  SGG_WT(2, true) SGG_WT(2, false) SGG_WT(3, false)
+  SGG_WG_TILE(128, 128, 64, 64)      // (its split forms are instantiated but never routed: conv_wgrad_tr_kernel serves them)
+#undef SGG_WT
+#undef SGG_WG_TILE
+#undef SGG_WG
+  sgg_set_error("sgg_conv2d_nhwc_wgrad: no instantiation for this route");
+  return SGG_ERR_ARG;
 }
 
 // conv1_1's filter gradient FUSED with the apply half of the LayerNorm backward of its output (conv_c3_wgrad_kernel<true>):
@@ -812,16 +914,17 @@ extern "C" int sgg_conv2d_nhwc_wgrad_c3_ln(const float* x, const float* y, const
   SGG_CHECK_ARG(x && y && da && gamma && beta && stats && means && dw, "sgg_conv2d_nhwc_wgrad_c3_ln: null pointer");
   SGG_CHECK_ARG(B > 0 && H > 0 && W > 0 && pad_t == 1 && pad_l == 1, "sgg_conv2d_nhwc_wgrad_c3_ln: bad dims (3x3 stride 1, SAME padding)");
   SGG_CHECK_ARG((long long)B * H * W * 32 < (1LL << 31), "sgg_conv2d_nhwc_wgrad_c3_ln: tensor exceeds 2^31 elements");
-  const WgradPlan pl = wgrad_plan(B, H, W, 3, 32, 3, 3);
+  WgradRoute pl;
+  wgrad_tap_plan(pl, B, H, W, 3, 32, 3, 3);
   if (!workspace || workspace_bytes < pl.ws_bytes) {
     sgg_set_error("sgg_conv2d_nhwc_wgrad_c3_ln: workspace too small (%zu < %zu)", workspace_bytes, pl.ws_bytes);
     return SGG_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(conv_c3_wgrad_kernel<true>, dim3(pl.nsplit), dim3(256), 0, st, x, (const float*)nullptr, (float*)workspace, H, W, pad_t,
+  hipLaunchKernelGGL(conv_c3_wgrad_kernel<true>, dim3(pl.nslabs), dim3(256), 0, st, x, (const float*)nullptr, (float*)workspace, H, W, pad_t,
                      pad_l, sgg_cdiv(W, 32), sgg_cdiv(H, 8), pl.tiles, pl.chunk, C3LnArgs{y, da, gamma, beta, stats, means});
   SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad_c3_ln");
-  launch_slab_reduce((const float*)workspace, dw, 27LL * 32 / 4, pl.nsplit, st);
+  launch_slab_reduce((const float*)workspace, dw, 27LL * 32 / 4, pl.nslabs, st);
   SGG_LAUNCH_CHECK("sgg_conv2d_nhwc_wgrad_c3_ln(reduce)");
   return SGG_OK;
 }

@@ -375,90 +375,43 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_dma_rb_kernel(WgradDmaRbPar
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------
-// H, W: the dy grid (both divisible by 8); 3x3 stride 1 or 5x5 stride 2 with an even x grid; Cin, Cout % 64 == 0.
-int sgg_wgrad_dma_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, WgradDmaPlan* pl) {
-  const bool k3 = KH == 3 && KW == 3 && stride == 1, k5 = KH == 5 && KW == 5 && stride == 2;
-  if (!((k3 || k5) && B > 0 && H > 0 && W > 0 && Cin % 64 == 0 && Cout % 64 == 0)) return 0;
-  if ((size_t)B * H * W * stride * stride * Cin * sizeof(float) >= 0x80000000ull || (size_t)B * H * W * Cout * sizeof(float) >= 0x80000000ull)
-    return 0;
-  pl->geo = 0; pl->R = 8; pl->pc = 12; pl->xslots = 120;
-  if (H % 8 != 0 || W % 8 != 0) {
-    // row bands (conv_wgrad_halo.hip: sgg_wgrad_halo_plan): R full-width rows, R * W <= 112 pixels, (R + 2) * (W + 1) + 1 <= 176 slots
-    int R = 112 / W;
-    if (R > H) R = H;
-    while (R > 0 && (R + 2) * (W + 1) + 1 > 176) --R;
-    if (R < 1) return 0;
-    pl->geo = 1; pl->R = R; pl->pc = W + 1; pl->xslots = (R + 2) * (W + 1) + 1;
-    pl->nt = 2; pl->spw = 2;
-    pl->pairs_n = Cout / 64;
-    pl->pairs = (Cin / 64) * pl->pairs_n;
-    const int nb = B * ((H + R - 1) / R);
-    int nsr = 256 / pl->pairs;
-    if (nsr > nb / 4) nsr = nb / 4;
-    if (nsr < 1) nsr = 1;
-    pl->stages = (nb + nsr - 1) / nsr;
-    pl->nsplit = (nb + pl->stages - 1) / pl->stages;
-    pl->nslabs = pl->nsplit * pl->spw;
-    pl->ws_bytes = (size_t)pl->nslabs * KH * KW * Cin * Cout * sizeof(float);
-    return 1;
-  }
-  pl->nt = Cout % 128 == 0 ? 4 : 2;
-  pl->spw = pl->nt == 4 ? 1 : 2;
-  pl->pairs_n = Cout / (32 * pl->nt);
-  pl->pairs = (Cin / 64) * pl->pairs_n;
-  const int nblk = B * (H / 8) * (W / 8);
-  int ns = 256 / pl->pairs;                       // one workgroup per CU
-  if (ns > nblk / 4) ns = nblk / 4;
-  if (ns < 1) ns = 1;
-  pl->stages = (nblk + ns - 1) / ns;
-  pl->nsplit = (nblk + pl->stages - 1) / pl->stages;
-  pl->nslabs = pl->nsplit * pl->spw;
-  pl->ws_bytes = (size_t)pl->nslabs * KH * KW * Cin * Cout * sizeof(float);
-  return 1;
-}
-
-template <int NKH, int NKW>
-static void wgrad_dma_launch_class(const WgradDmaParams& p, const WgradDmaPlan& pl, hipStream_t st) {
-  const dim3 grid(pl.nsplit, pl.pairs);
-  if (pl.geo == 1) {
-    WgradDmaRbParams pr;
+static int wgrad_dma_launch_class(const WgradRoute& r, const WgradTapClass& c, const WgradDmaParams& p, hipStream_t st) {
+  WgradDmaRbParams pr;
+  if (r.family == WGRAD_DMA_RB) {
     pr.d = p;
-    pr.d.bh = (p.H + pl.R - 1) / pl.R; pr.d.bw = 1; pr.d.nblk = p.B * pr.d.bh;
-    pr.R = pl.R; pr.pc = pl.pc; pr.xslots = pl.xslots; pr.npx = pl.R * p.W;
+    pr.d.bh = (p.H + r.R - 1) / r.R; pr.d.bw = 1; pr.d.nblk = p.B * pr.d.bh;
+    pr.R = r.R; pr.pc = r.pc; pr.xslots = r.xslots; pr.npx = r.R * p.W;
     pr.magic_w = (unsigned)((0x100000000ull + p.W - 1) / p.W);
-    pr.magic_pc = (unsigned)((0x100000000ull + pl.pc - 1) / pl.pc);
-    hipLaunchKernelGGL((conv_wgrad_dma_rb_kernel<NKH, NKW>), grid, dim3(512), 0, st, pr);
-    return;
+    pr.magic_pc = (unsigned)((0x100000000ull + r.pc - 1) / r.pc);
   }
-  if (pl.nt == 4) hipLaunchKernelGGL((conv_wgrad_dma_kernel<4, NKH, NKW>), grid, dim3(512), 0, st, p);
-  else hipLaunchKernelGGL((conv_wgrad_dma_kernel<2, NKH, NKW>), grid, dim3(512), 0, st, p);
+#define SGG_WD_CLASS(NKH, NKW)                                                                                                           \
+  SGG_LAUNCH_ARM(r.family == WGRAD_DMA_RB && c.nkh == NKH && c.nkw == NKW, (conv_wgrad_dma_rb_kernel<NKH, NKW>), r.grid, dim3(512), 0, st, pr)   \
+  SGG_LAUNCH_ARM(r.family == WGRAD_DMA && r.NT == 4 && c.nkh == NKH && c.nkw == NKW, (conv_wgrad_dma_kernel<4, NKH, NKW>), r.grid, dim3(512), 0, \
+                 st, p)                                                                                                                  \
+  SGG_LAUNCH_ARM(r.family == WGRAD_DMA && r.NT == 2 && c.nkh == NKH && c.nkw == NKW, (conv_wgrad_dma_kernel<2, NKH, NKW>), r.grid, dim3(512), 0, \
+                 st, p)
+  SGG_WD_CLASS(3, 3)
+  SGG_WD_CLASS(3, 2)
+  SGG_WD_CLASS(2, 3)
+  SGG_WD_CLASS(2, 2)
+#undef SGG_WD_CLASS
+  sgg_set_error("sgg_wgrad_dma_launch: no instantiation for this route");
+  return SGG_ERR_ARG;
 }
 
-void sgg_wgrad_dma_launch(const void* x, const void* dy, float* slabs, int B, int H, int W, int Cin, int Cout, int stride, int pad_t,
-                          int pad_l, const float* amax_x, const float* amax_dy, const WgradDmaPlan& pl, hipStream_t st) {
+int sgg_wgrad_dma_launch(const WgradRoute& r, const void* x, const void* dy, float* slabs, int B, int H, int W, int Cin, int Cout, int stride,
+                         const float* amax_x, const float* amax_dy, hipStream_t st) {
   WgradDmaParams p;
   p.x = x; p.dy = dy; p.slabs = slabs; p.amax_x = amax_x; p.amax_dy = amax_dy;
   p.B = B; p.H = H; p.W = W; p.C = Cin; p.N = Cout; p.bh = H / 8; p.bw = W / 8; p.nblk = B * p.bh * p.bw;
   p.Hx = H * stride; p.Wx = W * stride; p.sxy = stride;
-  p.pairs_n = pl.pairs_n; p.stages = pl.stages;
+  p.pairs_n = Cout / (32 * r.NT); p.stages = r.stages;
   p.x_bytes = (unsigned)((size_t)B * p.Hx * p.Wx * Cin * sizeof(float));
   p.dy_bytes = (unsigned)((size_t)B * H * W * Cout * sizeof(float));
-  if (stride == 1) {
-    p.cy = p.cx = 0; p.a0y = p.a0x = -1; p.kh0 = p.kw0 = 0; p.kstep = 1; p.KWt = 3; p.taps_total = 9;
-    wgrad_dma_launch_class<3, 3>(p, pl, st);
-    return;
+  for (int i = 0; i < r.ncls; ++i) {
+    sgg_wgrad_set_class(p, r.cls[i], stride);
+    const int rc = wgrad_dma_launch_class(r, r.cls[i], p, st);
+    if (rc != SGG_OK) return rc;
   }
-  p.kstep = 2; p.KWt = 5; p.taps_total = 25;
-  for (int cy = 0; cy < 2; ++cy)
-    for (int cx = 0; cx < 2; ++cx) {      // the four parity classes of the taps (conv_wgrad_halo.hip: sgg_wgrad_halo_launch)
-      const int kh0 = (pad_t + cy) % 2, kw0 = (pad_l + cx) % 2;
-      p.cy = cy; p.cx = cx; p.kh0 = kh0; p.kw0 = kw0;
-      p.a0y = (kh0 - pad_t - cy) / 2;
-      p.a0x = (kw0 - pad_l - cx) / 2;
-      const int nkh = (5 - kh0 + 1) / 2, nkw = (5 - kw0 + 1) / 2;
-      if (nkh == 3 && nkw == 3) wgrad_dma_launch_class<3, 3>(p, pl, st);
-      else if (nkh == 3) wgrad_dma_launch_class<3, 2>(p, pl, st);
-      else if (nkw == 3) wgrad_dma_launch_class<2, 3>(p, pl, st);
-      else wgrad_dma_launch_class<2, 2>(p, pl, st);
-    }
+  return SGG_OK;
 }

@@ -442,103 +442,51 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_halo3_kernel(WgradHaloParam
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------
-// H, W: the dy grid.  Served: 3x3 stride 1 (x grid = dy grid) and 5x5 stride 2 with an even x grid (= 2H x 2W, SAME pads
-// (1, 2)); H % 8 == W % 8 == 0, channels % 32 == 0.
-int sgg_wgrad_halo_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, WgradHaloPlan* pl) {
-  const bool k3 = KH == 3 && KW == 3 && stride == 1, k5 = KH == 5 && KW == 5 && stride == 2;
-  if (!((k3 || k5) && H > 0 && W > 0 && Cin % 32 == 0 && Cout % 32 == 0 && B > 0)) return 0;
-  if ((size_t)B * H * W * stride * stride * Cin * sizeof(float) >= 0x80000000ull || (size_t)B * H * W * Cout * sizeof(float) >= 0x80000000ull)
-    return 0;
-  pl->geo = 0; pl->R = 8; pl->pc = 12; pl->xslots = 120;
-  if (H % 8 != 0 || W % 8 != 0) {
-    // row bands: R full-width rows with R * W <= 112 pixels and a patch of (R + 2) * (W + 1) + 1 <= 176 slots; 64 x 64 channel chunks
-    int R = 112 / W;
-    if (R > H) R = H;
-    while (R > 0 && (R + 2) * (W + 1) + 1 > 176) --R;
-    if (R < 1 || Cin % 64 != 0 || Cout % 64 != 0) return 0;
-    pl->geo = 1; pl->R = R; pl->pc = W + 1; pl->xslots = (R + 2) * (W + 1) + 1;
-  }
-  if (Cin % 64 == 0 && Cout % 64 == 0) { pl->ct = 2; pl->nt = 2; }
-  else if (Cout % 64 == 0) { pl->ct = 1; pl->nt = 2; }
-  else { pl->ct = 1; pl->nt = 1; }
-  pl->nbs = pl->ct == 2 ? 1 : 2;
-  pl->spw = 4 / (pl->ct * pl->nt);
-  pl->pairs_n = Cout / (32 * pl->nt);
-  pl->pairs = (Cin / (32 * pl->ct)) * pl->pairs_n;
-  const int nblk = pl->geo ? B * ((H + pl->R - 1) / pl->R) : B * (H / 8) * (W / 8);
-  const int total_stages = (nblk + pl->nbs - 1) / pl->nbs;
-  int ns = 512 / pl->pairs;                       // one resident round of 2 workgroups per CU
-  if (ns > total_stages / 8) ns = total_stages / 8;
-  if (ns < 1) ns = 1;
-  pl->stages = (total_stages + ns - 1) / ns;
-  pl->nsplit = (total_stages + pl->stages - 1) / pl->stages;
-  pl->nslabs = pl->nsplit * pl->spw;
-  pl->ws_bytes = (size_t)pl->nslabs * KH * KW * Cin * Cout * sizeof(float);
-  return 1;
-}
-
-template <int NKH, int NKW>
-static void wgrad_halo_launch_class(const WgradHaloParams& p, const WgradHaloPlan& pl, bool half, bool one, hipStream_t st) {
-  const dim3 grid(pl.nsplit, pl.pairs);
-  if (pl.geo == 1) {   // row bands (64 x 64 channel chunks, no LN prologue: host checks)
-    if (one) {
-      if (half) hipLaunchKernelGGL((conv_wgrad_halo3_kernel<2, 2, true, true, NKH, NKW, false, 1, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((conv_wgrad_halo3_kernel<2, 2, false, true, NKH, NKW, false, 1, true>), grid, dim3(256), 0, st, p);
-    } else if (half) hipLaunchKernelGGL((conv_wgrad_halo3_kernel<2, 2, true, true, NKH, NKW, false, 1>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv_wgrad_halo3_kernel<2, 2, false, true, NKH, NKW, false, 1>), grid, dim3(256), 0, st, p);
-    return;
-  }
-#define SGG_WH(CT, NT, PF)                                                                                          \
-  do {                                                                                                              \
-    if (one) {                                                                                                      \
-      if (half) hipLaunchKernelGGL((conv_wgrad_halo3_kernel<CT, NT, true, PF, NKH, NKW, false, 0, true>), grid, dim3(256), 0, st, p);   \
-      else hipLaunchKernelGGL((conv_wgrad_halo3_kernel<CT, NT, false, PF, NKH, NKW, false, 0, true>), grid, dim3(256), 0, st, p);       \
-    } else if (p.ln_stats) {                                                                                        \
-      if (half) hipLaunchKernelGGL((conv_wgrad_halo3_kernel<CT, NT, true, PF, NKH, NKW, true>), grid, dim3(256), 0, st, p);   \
-      else hipLaunchKernelGGL((conv_wgrad_halo3_kernel<CT, NT, false, PF, NKH, NKW, true>), grid, dim3(256), 0, st, p);       \
-    } else if (half) hipLaunchKernelGGL((conv_wgrad_halo3_kernel<CT, NT, true, PF, NKH, NKW, false>), grid, dim3(256), 0, st, p);   \
-    else hipLaunchKernelGGL((conv_wgrad_halo3_kernel<CT, NT, false, PF, NKH, NKW, false>), grid, dim3(256), 0, st, p);       \
-  } while (0)
-  if (pl.ct == 2) SGG_WH(2, 2, true);
-  else if (pl.nt == 2) SGG_WH(1, 2, false);
-  else SGG_WH(1, 1, true);
+// the instantiations of one tap class: row bands, then per channel chunk single-piece / LN prologue / plain, each in fp16 and bf16
+static int wgrad_halo_launch_class(const WgradRoute& r, const WgradTapClass& c, const WgradHaloParams& p, hipStream_t st) {
+  const int geo = r.family == WGRAD_HALO_RB;
+#define SGG_WH(CT_, NT_, HALF_, PF_, NKH_, NKW_, LNP_, GEO_, ONE_)                                                                      \
+  SGG_LAUNCH_ARM(r.CT == CT_ && r.NT == NT_ && r.HALF == HALF_ && c.nkh == NKH_ && c.nkw == NKW_ && r.LNP == LNP_ && \
+                     geo == GEO_ && r.ONE == ONE_,                                                                                      \
+                 (conv_wgrad_halo3_kernel<CT_, NT_, HALF_, PF_, NKH_, NKW_, LNP_, GEO_, ONE_>), r.grid, dim3(256), 0, st, p)
+#define SGG_WH_CHUNK(CT, NT, PF, NKH, NKW)                                                                       \
+  SGG_WH(CT, NT, true, PF, NKH, NKW, false, 0, true) SGG_WH(CT, NT, false, PF, NKH, NKW, false, 0, true)         \
+  SGG_WH(CT, NT, true, PF, NKH, NKW, true, 0, false) SGG_WH(CT, NT, false, PF, NKH, NKW, true, 0, false)         \
+  SGG_WH(CT, NT, true, PF, NKH, NKW, false, 0, false) SGG_WH(CT, NT, false, PF, NKH, NKW, false, 0, false)
+#define SGG_WH_CLASS(NKH, NKW)                                                                                   \
+  SGG_WH(2, 2, true, true, NKH, NKW, false, 1, true) SGG_WH(2, 2, false, true, NKH, NKW, false, 1, true)         \
+  SGG_WH(2, 2, true, true, NKH, NKW, false, 1, false) SGG_WH(2, 2, false, true, NKH, NKW, false, 1, false)       \
+  SGG_WH_CHUNK(2, 2, true, NKH, NKW) SGG_WH_CHUNK(1, 2, false, NKH, NKW) SGG_WH_CHUNK(1, 1, true, NKH, NKW)
+  SGG_WH_CLASS(3, 3)
+  SGG_WH_CLASS(3, 2)
+  SGG_WH_CLASS(2, 3)
+  SGG_WH_CLASS(2, 2)
+#undef SGG_WH_CLASS
+#undef SGG_WH_CHUNK
 #undef SGG_WH
+  sgg_set_error("sgg_wgrad_halo_launch: no instantiation for this route");
+  return SGG_ERR_ARG;
 }
 
-// stride: 1 (3x3) or 2 (5x5, one launch per parity class of the taps); pad_t / pad_l: SAME padding before
-void sgg_wgrad_halo_launch(const float* x, const float* dy, float* slabs, int B, int H, int W, int Cin, int Cout, int stride,
-                           int pad_t, int pad_l, int precision, const float* amax_x, const float* amax_dy, const WgradHaloPlan& pl,
-                           hipStream_t st, const float* ln_stats, const float* ln_gamma, const float* ln_beta, int operand_format) {
+int sgg_wgrad_halo_launch(const WgradRoute& r, const float* x, const float* dy, float* slabs, int B, int H, int W, int Cin, int Cout,
+                          int stride, const float* amax_x, const float* amax_dy, const float* ln_stats, const float* ln_gamma,
+                          const float* ln_beta, int operand_format, hipStream_t st) {
   WgradHaloParams p;
   p.x_s16 = operand_format & 1; p.dy_s16 = (operand_format >> 1) & 1;
   p.x = x; p.dy = dy; p.slabs = slabs; p.amax_x = amax_x; p.amax_dy = amax_dy;
   p.ln_stats = ln_stats; p.ln_gamma = ln_gamma; p.ln_beta = ln_beta; p.B = B;
   p.H = H; p.W = W; p.C = Cin; p.N = Cout; p.bh = H / 8; p.bw = W / 8; p.nblk = B * p.bh * p.bw;
-  p.R = pl.R; p.pc = pl.pc; p.xslots = pl.xslots; p.npx = pl.R * W; p.magic_w = (unsigned)((0x100000000ull + W - 1) / W);
-  p.magic_pc = (unsigned)((0x100000000ull + pl.pc - 1) / pl.pc);
-  if (pl.geo == 1) { p.bh = (H + pl.R - 1) / pl.R; p.bw = 1; p.nblk = B * p.bh; }
+  p.R = r.R; p.pc = r.pc; p.xslots = r.xslots; p.npx = r.R * W; p.magic_w = (unsigned)((0x100000000ull + W - 1) / W);
+  p.magic_pc = (unsigned)((0x100000000ull + r.pc - 1) / r.pc);
+  if (r.family == WGRAD_HALO_RB) { p.bh = (H + r.R - 1) / r.R; p.bw = 1; p.nblk = B * p.bh; }
   p.Hx = H * stride; p.Wx = W * stride; p.sxy = stride;
-  p.pairs_n = pl.pairs_n; p.stages = pl.stages;
+  p.pairs_n = Cout / (32 * r.NT); p.stages = r.stages;
   p.x_bytes = (unsigned)((size_t)B * p.Hx * p.Wx * Cin * sizeof(float));
   p.dy_bytes = (unsigned)((size_t)B * H * W * Cout * sizeof(float));
-  const bool half = sgg_prec_half(precision), one = sgg_prec_one(precision);
-  if (stride == 1) {
-    p.cy = p.cx = 0; p.a0y = p.a0x = -1; p.kh0 = p.kw0 = 0; p.kstep = 1; p.KWt = 3; p.taps_total = 9;
-    wgrad_halo_launch_class<3, 3>(p, pl, half, one, st);
-    return;
+  for (int i = 0; i < r.ncls; ++i) {
+    sgg_wgrad_set_class(p, r.cls[i], stride);
+    const int rc = wgrad_halo_launch_class(r, r.cls[i], p, st);
+    if (rc != SGG_OK) return rc;
   }
-  p.kstep = 2; p.KWt = 5; p.taps_total = 25;
-  for (int cy = 0; cy < 2; ++cy)
-    for (int cx = 0; cx < 2; ++cx) {
-      // taps kh with (kh - pad_t) mod 2 == cy: kh0 = first such tap, sub-grid offset a0 = floor((kh0 - pad_t - cy) / 2) + ... = (kh0 - pad_t - cy) / 2
-      const int kh0 = (pad_t + cy) % 2, kw0 = (pad_l + cx) % 2;
-      p.cy = cy; p.cx = cx; p.kh0 = kh0; p.kw0 = kw0;
-      p.a0y = (kh0 - pad_t - cy) / 2;           // exact: kh0 - pad_t - cy is even (and <= 0)
-      p.a0x = (kw0 - pad_l - cx) / 2;
-      const int nkh = (5 - kh0 + 1) / 2, nkw = (5 - kw0 + 1) / 2;
-      if (nkh == 3 && nkw == 3) wgrad_halo_launch_class<3, 3>(p, pl, half, one, st);
-      else if (nkh == 3) wgrad_halo_launch_class<3, 2>(p, pl, half, one, st);
-      else if (nkw == 3) wgrad_halo_launch_class<2, 3>(p, pl, half, one, st);
-      else wgrad_halo_launch_class<2, 2>(p, pl, half, one, st);
-    }
+  return SGG_OK;
 }

@@ -45,6 +45,7 @@ SIGNATURES = {
     "sgg_conv2d_nhwc_wgrad_workspace_bytes": (_sz, [_i] * 9),
     "sgg_conv2d_nhwc_wgrad": (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "sgg_conv2d_nhwc_wgrad_resident": (_i, [_i] * 9),
+    "sgg_conv2d_nhwc_wgrad_symbol": (_i, [_i] * 16 + [_vp, c_char_p, _i]),
     "sgg_layernorm_hwc_elu_workspace_bytes": (_sz, [_i, _i, _i]),
     "sgg_layernorm_hwc_elu_fwd": (_i, [_vp] * 7 + [_i] * 10 + [_vp, _sz, _vp]),
     "sgg_layernorm_hwc_elu_bwd": (_i, [_vp] * 10 + [_i] * 9 + [_vp, _vp, _sz, _vp]),
@@ -90,6 +91,12 @@ SIGNATURES = {
     "sgg_vector_stats": (_i, [_vp, _i, _f, _vp, _vp]),
     "sgg_fill": (_i, [_vp, _ll, _f, _vp]),
 }
+
+# timing label of a conv_wgrad call by the first matching prefix of the kernel the library routes it to (bench.py's output and
+# DESIGN.md are keyed by the labels)
+WGRAD_LABELS = (("conv_c3_wgrad", "conv_c3_wgrad(call: kernel + slab reduce)"),
+                ("conv_wgrad_dma", "conv_wgrad_dma(call: LDS-DMA kernel on pre-split operands + slab reduce)"),
+                ("conv_wgrad", "conv_wgrad(call: wgrad kernel + slab reduce)"))
 
 _lib = None
 
@@ -415,11 +422,11 @@ class HipKernels:
         return self.lib.sgg_conv2d_nhwc_fwd_tile_stats(y_shape[1], y_shape[2], cin, y_shape[3], k, k, stride, self.conv_precision,
                                                        layout)
 
-    def _conv_symbol(self, query, *args):
-        """The kernel symbol of a forward / dgrad launch, as the library's own routing reports it (sgg_conv2d_nhwc_fwd_symbol /
-        _dgrad_symbol: the launch's validation and route, scalars only).  Asked only while kernel timing is on."""
-        buf = ctypes.create_string_buffer(128)
-        self._check(getattr(self.lib, query)(*args, buf, len(buf)), query)
+    def _conv_symbol(self, query, *args, name=None):
+        """The kernel symbol(s) of a convolution launch, as the library's own routing reports them (sgg_conv2d_nhwc_fwd_symbol /
+        _dgrad_symbol / _wgrad_symbol: the launch's validation and route, scalars only).  Asked only while kernel timing is on."""
+        buf = ctypes.create_string_buffer(256)
+        self._check(getattr(self.lib, query)(*args, buf, len(buf)), name or query)      # (name: a refusal reads as the launch's own)
         return buf.value.decode()
 
     def conv_fwd(self, x, w_hwio, w_fwd, bias, y, stride, w_split=None, amax_x=None, amax_w=None, tile_stats=None, w_split_layout=0,
@@ -476,17 +483,19 @@ class HipKernels:
         need = self.lib.sgg_conv2d_nhwc_wgrad_workspace_bytes(*d[:9])
         ws = self.workspace(need)
         flops = 2.0 * d[0] * d[4] * d[5] * d[6] * d[7] * d[8] * d[3]
-        sym, nb = "conv_wgrad(call: wgrad kernel + slab reduce)", 0.0
-        if x_s16 and dy_s16 and ln is None and self.conv_precision == 2 and self.conv_halo and \
-                self.lib.sgg_conv2d_nhwc_wgrad_resident(d[0], d[4], d[5], d[3], d[6], d[7], d[8], stride, 2) == 2:
-            sym = "conv_wgrad_dma(call: LDS-DMA kernel on pre-split operands + slab reduce)"
+        fmt = int(bool(x_s16)) | (int(bool(dy_s16)) << 1)
+        sym, nb = "", 0.0
+        if self.timing is not None:
+            kernels = self._conv_symbol("sgg_conv2d_nhwc_wgrad_symbol", *d, self.conv_precision, 0 if self.conv_halo else 1, ln is not None,
+                                        fmt, None, name="sgg_conv2d_nhwc_wgrad")
+            sym = next(label for prefix, label in WGRAD_LABELS if kernels.startswith(prefix))
         if d[3] != 3:
             amax_x, amax_dy = self._amax_or_compute(x, amax_x, 0), self._amax_or_compute(dy, amax_dy, 1)
         else:
-            sym, nb = "conv_c3_wgrad(call: kernel + slab reduce)", 4.0 * (x.numel() + dy.numel())      # conv1_1: HBM-bound
+            nb = 4.0 * (x.numel() + dy.numel())      # conv1_1: HBM-bound
         self._check(self._timed(sym, flops, lambda: self.lib.sgg_conv2d_nhwc_wgrad(
             _p(x), _p(dy), _p(dw), *d, self.conv_precision, 0 if self.conv_halo else 1, _p(amax_x), _p(amax_dy), _p(ln_s), _p(ln_g), _p(ln_b),
-            int(bool(x_s16)) | (int(bool(dy_s16)) << 1), _p(ws), ws.numel(), self._stream()), nb),
+            fmt, _p(ws), ws.numel(), self._stream()), nb),
             "sgg_conv2d_nhwc_wgrad")
 
     @staticmethod
@@ -529,9 +538,12 @@ class HipKernels:
         its four parity-class launches; the C ABI rejects the prologue elsewhere)."""
         if not (self.conv_halo and self.conv_precision in (2, 3) and cin <= 512):
             return False
-        lay = self.lib.sgg_conv_wsplit_layout(k, k, stride, H, W, cin, cout, self.conv_precision)
-        # (layout 2: the band-resident forward has the prologue; its wgrad only on grids the 8x8-block halo kernel tiles)
-        return lay in (1, 3, 4) or (lay == 2 and (H // 2) % 8 == 0 and (W // 2) % 8 == 0)
+        if self.lib.sgg_conv_wsplit_layout(k, k, stride, H, W, cin, cout, self.conv_precision) not in (1, 2, 3, 4):
+            return False
+        # the filter gradient: does the library route the launch with an LN prologue?  (one sample: short of the 2 GiB tensor limits the family does not depend on the batch)
+        (Ho, pad_t, _), (Wo, pad_l, _) = same_pads(H, k, stride), same_pads(W, k, stride)
+        return self.lib.sgg_conv2d_nhwc_wgrad_symbol(1, H, W, cin, Ho, Wo, cout, k, k, stride, pad_t, pad_l, self.conv_precision, 0, 1, 0,
+                                                     None, ctypes.create_string_buffer(256), 256) == 0
 
     def ln_prologue_fwd_ok(self, k, stride, H, W, cin, cout):
         """True if conv_fwd of this layer can apply the producing layer's LayerNorm + ELU itself (forward-only passes): the
