@@ -343,6 +343,13 @@ int sgg_adam_tf_multi_ema(float* params, const float* grads, float* m, float* v,
                           float beta2, float eps, float grad_scale, float one_minus_decay, void* stream);
 int sgg_swap_f32(float* a, float* b, long long n, void* stream);
 
+/* ---- gradient accumulation over micro-batches (csrc/ema.hip) -----------------------------------------------------------------
+ * The reference takes every update from one minibatch; every loss term is a mean over rows and no op couples samples, so the mean
+ * of the gradients of N equal micro-batches is the gradient of their union (sgg_amd/step.py: Network.end_micro_batch).
+ * acc[i] = g[i] (first != 0; a bit copy) or acc[i] = acc[i] + g[i] (one fp32 addition per element; no atomics: the result is a pure
+ * function of the inputs).  Both 16-byte aligned, n > 0, the ranges must not overlap (argument error, nothing is launched). */
+int sgg_grad_accumulate(float* acc, const float* g, long long n, int first, void* stream);
+
 /* ---- tf.argmax(x, axis=-1): train.py:270-271 ---------------------------------------------------------------- */
 int sgg_argmax_rows(const float* x, long long* out, int rows, int V, int ld, void* stream);
 

@@ -5,6 +5,9 @@
 //                     ten a separate averaging pass behind adam_kernel moves.
 //   swap_kernel       exchanges two ranges bit for bit (Network.averaged(): the average takes the place of the live parameters, so
 //                     every view, descriptor and pre-split copy that points into the arena stays valid).
+//   grad_accumulate_kernel   gradient accumulation over micro-batches (Network.end_micro_batch): acc = g (first) or acc = acc + g, one
+//                     fp32 addition per element, no atomics - a pure function of the inputs for any grid.  Three streams (two when
+//                     first) against the seven of adam_kernel.
 #include "sgg_common.h"
 
 __global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -55,6 +58,24 @@ __global__ void swap_kernel(float* __restrict__ a, float* __restrict__ b, long l
   }
 }
 
+template <bool FIRST>
+__global__ void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, long long n) {
+  const long long n4 = n >> 2;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    if (FIRST) {
+      reinterpret_cast<f32x4*>(acc)[i] = gv;
+    } else {
+      const f32x4 av = reinterpret_cast<f32x4*>(acc)[i];
+      reinterpret_cast<f32x4*>(acc)[i] = av + gv;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long long i = (n4 << 2) + threadIdx.x;
+    acc[i] = FIRST ? g[i] : acc[i] + g[i];
+  }
+}
+
 // ---- C ABI ------------------------------------------------------------------------------------------
 static inline int grid_for(long long n, int block) {
   long long g = (n + block - 1) / block;
@@ -91,5 +112,18 @@ extern "C" int sgg_swap_f32(float* a, float* b, long long n, void* stream) {
   SGG_CHECK_ARG(!ranges_overlap(a, b, n), "sgg_swap_f32: the ranges overlap");
   hipLaunchKernelGGL(swap_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, a, b, n);
   SGG_LAUNCH_CHECK("sgg_swap_f32");
+  return SGG_OK;
+}
+
+extern "C" int sgg_grad_accumulate(float* acc, const float* g, long long n, int first, void* stream) {
+  SGG_CHECK_ARG(acc && g && n > 0, "sgg_grad_accumulate: bad argument");
+  SGG_CHECK_ARG((((uintptr_t)acc | (uintptr_t)g) & 15) == 0, "sgg_grad_accumulate: pointers must be 16-byte aligned");
+  SGG_CHECK_ARG(!ranges_overlap(acc, g, n), "sgg_grad_accumulate: the ranges overlap");
+  const dim3 grid(grid_for(n / 4 + 1, 256)), block(256);
+  if (first)
+    hipLaunchKernelGGL(grad_accumulate_kernel<true>, grid, block, 0, (hipStream_t)stream, acc, g, n);
+  else
+    hipLaunchKernelGGL(grad_accumulate_kernel<false>, grid, block, 0, (hipStream_t)stream, acc, g, n);
+  SGG_LAUNCH_CHECK("sgg_grad_accumulate");
   return SGG_OK;
 }

@@ -81,6 +81,7 @@ SIGNATURES = {
     "sgg_adam_tf_multi": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _vp]),
     "sgg_adam_tf_multi_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _f, _vp]),
     "sgg_swap_f32": (_i, [_vp, _vp, _ll, _vp]),
+    "sgg_grad_accumulate": (_i, [_vp, _vp, _ll, _i, _vp]),
     "sgg_argmax_rows": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sgg_rank_triples": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgg_match_triples": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
@@ -887,6 +888,14 @@ class HipKernels:
         assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (a, b))
         self._check(self._timed("swap_kernel", 0.0, lambda: self.lib.sgg_swap_f32(_p(a), _p(b), n, self._stream()), 16.0 * n),
                     "sgg_swap_f32")
+
+    def grad_accumulate(self, acc, g, first=False):
+        """acc = g (first) or acc += g, one fp32 addition per element (csrc/ema.hip): the pass of gradient accumulation."""
+        self._dev(acc, g)
+        n = acc.numel()
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (acc, g))
+        self._check(self._timed("grad_accumulate_kernel", 0.0, lambda: self.lib.sgg_grad_accumulate(
+            _p(acc), _p(g), n, int(bool(first)), self._stream()), (8.0 if first else 12.0) * n), "sgg_grad_accumulate")
 
     # -- training diagnostics (csrc/stats.hip) ---------------------------------------------------------
     def arena_stats_chunk(self):

@@ -68,19 +68,51 @@ class Network:
         assert self.pending is None
         self.K.fill(self.arena.live(self.grad_flat), 0.0)
 
-    def update(self, reducer):
+    def update(self, reducer, grad_scale=1.0):
         """Gradients are complete: start their all-reduce (if data parallel) and defer the Adam step until the
-        weights are next needed (finish_update), so the collective overlaps with the other network's encoder."""
+        weights are next needed (finish_update), so the collective overlaps with the other network's encoder.
+        grad_scale: 1 / N after N accumulated micro-batches (end_micro_batch); multiplies the reducer's scale."""
         if reducer is None:
-            self.adam_step(1.0)
+            self.adam_step(grad_scale)
         else:
             self.pending = reducer(self)
+            if grad_scale != 1.0:
+                self.opt["pending_scale"] = grad_scale
 
     def finish_update(self):
         if self.pending is not None:
             scale = self.pending.wait()
             self.pending = None
-            self.adam_step(scale)
+            extra = self.opt.pop("pending_scale", None)
+            self.adam_step(scale if extra is None else scale * extra)
+
+    # ---- gradient accumulation (csrc/ema.hip: grad_accumulate_kernel) ------------------------------------
+    def _acc_flat(self):
+        """The second gradient arena: allocated the first time an update spans more than one micro-batch, state of the ARENA."""
+        acc = self.opt.get("acc")
+        if acc is None:
+            if not hasattr(self.K, "grad_accumulate"):
+                raise RuntimeError("gradient accumulation needs the grad_accumulate kernel; the %r kernel set has none"
+                                   % getattr(self.K, "name", self.K))
+            acc = self.opt["acc"] = self.arena.like()[0]
+        return acc
+
+    def end_micro_batch(self, k, N, reducer):
+        """The gradients of micro-batch k of N are complete in grad_flat (every filter-gradient kernel overwrites its range, so each
+        micro-step starts from zero_grads as a whole step does).  k < N - 1: they are added to the second arena (k = 0: copied) and
+        nothing else happens - no optimiser step, no collective.  k = N - 1 > 0: the sum so far is added to grad_flat, which then
+        holds the sum over all N, and update() runs with the gradient scale 1 / N: the reducer, both Adam passes and the statistics
+        pass read the MEAN gradient, which is the gradient of the N * B rows (every loss term is a mean over rows, no op couples
+        samples).  N = 1: update(reducer), call for call.  On the current stream, behind the step's last gradient kernel."""
+        assert 0 <= k < N
+        if N == 1:
+            return self.update(reducer)
+        a, acc = self.arena, self._acc_flat()
+        if k < N - 1:
+            self.K.grad_accumulate(a.live(acc), a.live(self.grad_flat), first=(k == 0))
+            return
+        self.K.grad_accumulate(a.live(self.grad_flat), a.live(acc))
+        self.update(reducer, 1.0 / N)
 
     def adam_step(self, grad_scale=1.0):
         self._not_swapped("adam_step")
@@ -263,6 +295,8 @@ class GanStep:
         # the MFMA-bound convolutions of the other, launch tails are filled).  Measured +3 % triples/s; off by
         # default because concurrent kernels make per-kernel durations (the roofline measurement) meaningless.
         self._g_reuse, self._g_reuse_armed = None, False       # (images, ctx) of G's encoder within one train_iteration
+        self._g_reuse_slots = {}                 # accumulation: micro-batch k -> (images, copy of ctx, guard) (generator_forward)
+        self._loss_acc, self._loss_n = {}, {"d": 1, "g": 1}    # sums of the four loss numbers over the micro-batches of an update
         # (option side_priority: priority of the side streams - everything on them is off the critical chain of the main stream)
         prio = int(option(K, "side_priority"))
         self.side = torch.cuda.Stream(device=dev, priority=prio) if (overlap_streams and dev.type == "cuda") else None
@@ -284,7 +318,7 @@ class GanStep:
         self.D.head.enable_side_stream(self.head_side)
 
     # ------------------------------------------------------------------------------------------------
-    def _g_early_stream(self, images):
+    def _g_early_stream(self, images, N=1):
         """Option g_early (default on, two-stream schedule): G's encoder forward of THIS update depends on nothing the previous update
         still computes once that update's G head has run (a critic update leaves G's weights alone): it may start on a stream of its
         own right there - beside the critic's heads, which are a chain of short launches that leaves the chip idle, and its encoder
@@ -293,6 +327,8 @@ class GanStep:
         ev, ev_images = getattr(self, "_ev_g_free", None), getattr(self, "_ev_g_images", None)
         self._ev_g_free = self._ev_g_images = None
         if self.side is None or ev is None or not option(self.K, "g_early") or self.G.pending is not None or self._g_reuse is not None:
+            return None
+        if N > 1 and self._g_reuse_armed:        # accumulation with reuse: G's encoder output is kept per micro-batch on the main stream
             return None
         # only for the minibatch tensor the critic update ran on, unmodified (train.py:175-190 repeats each batch for every update of an
         # iteration): the early stream waits for nothing the main stream enqueued after that update's G head, so a tensor produced there
@@ -312,7 +348,7 @@ class GanStep:
         self.xs.wait_event(ev)
         return self.xs
 
-    def generator_forward(self, images, noise, for_backward=True, early=None):
+    def generator_forward(self, images, noise, for_backward=True, early=None, micro=None):
         """Generator.build_generator: fake logits [B,3,V] (a view of the critic's input slab).
 
         Inside train_iteration(..., reuse_g_encoder=True) G's ENCODER runs once per iteration: every update of an iteration sees
@@ -320,7 +356,28 @@ class GanStep:
         the encoder output, the step-invariant attention product and the activations kept for G's backward are those of the first
         call; only the recurrent head (fresh noise) is re-run.  bench.py never does this (every update recomputes everything)."""
         G = self.G
-        if self._g_reuse is not None and self._g_reuse[0] is images:
+        k, N = micro if micro is not None else (0, 1)
+        if N > 1:
+            # An update over N micro-batches (train_iteration_accumulated).  With reuse armed, the critic updates (forward-only
+            # passes) of an iteration share G's encoder output per micro-batch: the first one keeps a COPY of ctx (the trunk's output
+            # buffer is overwritten by the next micro-batch's forward), later ones re-run only the step-invariant attention product
+            # (the head has one P buffer) and the head.  Same forward-only schedule on the same weights: bit-equal to recomputing.
+            # The generator update (for_backward) always runs the encoder afresh: there is one set of backward activations.
+            guard = (images.data_ptr(), images._version, G.adam_t)
+            slot = self._g_reuse_slots.get(k) if (self._g_reuse_armed and not for_backward) else None
+            if slot is not None:
+                assert slot[0] is images and slot[2] == guard, \
+                    "G-encoder reuse: micro-batch %d was modified in place or replaced (or G was updated) inside one iteration" % k
+                ctx = slot[1]
+                G.head.precompute(ctx)
+            elif early is not None:
+                ctx = self._encode(G, images, for_backward, early, int(option(self.K, "g_early_cus")))
+                torch.cuda.current_stream().wait_stream(early)
+            else:
+                ctx = self._encode(G, images, for_backward)
+                if self._g_reuse_armed and not for_backward:
+                    self._g_reuse_slots[k] = (images, ctx.clone(), guard)
+        elif self._g_reuse is not None and self._g_reuse[0] is images:
             # the kept encoder output is only valid for the tensor's contents at the first call: an in-place write to the minibatch
             # (augmentation, a loader refilling its device buffer) or an optimiser step of G since then would silently train on stale
             # activations.  (Invariant of the schedule: no G.head.backward runs between the first generator_forward of an iteration
@@ -368,23 +425,27 @@ class GanStep:
         if self.side is not None:
             torch.cuda.current_stream().wait_stream(self.side)
 
-    def critic_step(self, images, labels, noise, alpha):
+    def critic_step(self, images, labels, noise, alpha, micro=None):
         """One disc_train_op (train.py:365). labels int64 [B,3]; noise [B,512]; alpha [B]. Returns self.d_losses
-        = (disc_cost, wasserstein term, gradient penalty, mean D(fake)) as a device tensor."""
+        = (disc_cost, wasserstein term, gradient penalty, mean D(fake)) as a device tensor.
+        micro = (k, N): this is micro-batch k of an update over N (Network.end_micro_batch); None = (0, 1), the whole update."""
         K, B, V, D = self.K, self.B, self.V, self.D
+        mk, mN = micro if micro is not None else (0, 1)
+        if mN > 1:
+            D._acc_flat()                         # (raises before anything is launched if the kernel set cannot accumulate)
         fake_rows, real_rows, hat_rows = self.TRI[:B], self.TRI[B:2 * B], self.TRI[2 * B:]
         # Data parallel: the network WITHOUT a gradient all-reduce in flight goes first, so that its encoder forward
         # runs under the other network's collective before anything waits for it (critic_iters = 1: G's reduce from the
         # last generator step hides under D's encoder; critic_iters > 1: D's reduce from the previous critic update
         # hides under G's forward).  With a side stream the wait is enqueued there and never blocks the main stream.
         if D.pending is None or self.side is not None:
-            early = self._g_early_stream(images)      # (critic_iters > 1: after another critic update)
+            early = self._g_early_stream(images, mN)  # (critic_iters > 1: after another critic update)
             ctx = self._d_encoder_on_side_stream(images, zero_grads=True)
             self.G.finish_update()
-            gst, _ = self.generator_forward(images, noise, for_backward=False, early=early)     # the critic update never differentiates G
+            gst, _ = self.generator_forward(images, noise, for_backward=False, early=early, micro=micro)     # the critic update never differentiates G
         else:
             self.G.finish_update()
-            gst, _ = self.generator_forward(images, noise, for_backward=False)
+            gst, _ = self.generator_forward(images, noise, for_backward=False, micro=micro)
             ctx = self._d_encoder_on_side_stream(images, zero_grads=True)
         if self.side is not None and option(K, "g_early"):
             # G's encoder buffers are free from here on, and this critic update does not touch G's weights (_g_early_stream)
@@ -420,7 +481,8 @@ class GanStep:
         dctx = D.head.finish_backward(ctx)
         D.trunk.backward(dctx)
         D.head.join()
-        D.update(self.reducer)
+        self._sum_losses("d", self.d_losses, mk, mN)
+        D.end_micro_batch(mk, mN, self.reducer)
         return self.d_losses
 
     def critic_loss(self, images, labels, noise, alpha, out=None):
@@ -453,19 +515,22 @@ class GanStep:
         K.wgan_losses(st.OUT[0].view(3 * B, T_STEPS), self.pen, self.lam, B, T_STEPS, True, out)
         return out
 
-    def generator_step(self, images, noise):
-        """One gen_train_op (train.py:368). Returns self.g_losses; g_losses[3] = mean D(fake) = -gen_cost."""
+    def generator_step(self, images, noise, micro=None):
+        """One gen_train_op (train.py:368). Returns self.g_losses; g_losses[3] = mean D(fake) = -gen_cost.  micro: as critic_step."""
         K, B, G, D = self.K, self.B, self.G, self.D
+        mk, mN = micro if micro is not None else (0, 1)
+        if mN > 1:
+            G._acc_flat()
         G.finish_update()
         G.zero_grads()
         if D.pending is None or self.side is not None:
-            early = self._g_early_stream(images)
+            early = self._g_early_stream(images, mN)
             ctx = self._d_encoder_on_side_stream(images, zero_grads=False, for_backward=False)   # independent of G's forward
-            gst, gctx = self.generator_forward(images, noise, early=early)
+            gst, gctx = self.generator_forward(images, noise, early=early, micro=micro)
         else:
             # the critic-gradient all-reduce launched at the end of critic_step runs under G's forward; only then does
             # D.finish_update() wait for it
-            gst, gctx = self.generator_forward(images, noise)
+            gst, gctx = self.generator_forward(images, noise, micro=micro)
             ctx = self._d_encoder_on_side_stream(images, zero_grads=False, for_backward=False)   # only D's head is differentiated here
         fake = gst.OUT[0]
         self._join_side()
@@ -481,8 +546,30 @@ class GanStep:
         dctx = G.head.finish_backward(gctx)
         G.trunk.backward(dctx)
         G.head.join()
-        G.update(self.reducer)
+        self._sum_losses("g", self.g_losses, mk, mN)
+        G.end_micro_batch(mk, mN, self.reducer)
         return self.g_losses
+
+    # ---- loss numbers of an update over N micro-batches --------------------------------------------------
+    def _sum_losses(self, which, losses, k, N):
+        """Every loss number is a mean over rows: the mean over N equal micro-batches is the number of the N * B rows.  The sum is
+        kept on the device by the accumulate kernel (k = 0: copy), the division by N happens on read.  N = 1: nothing is launched."""
+        self._loss_n[which] = N
+        if N == 1:
+            return
+        acc = self._loss_acc.get(which)
+        if acc is None:
+            acc = self._loss_acc[which] = torch.zeros_like(losses)
+        self.K.grad_accumulate(acc, losses, first=(k == 0))
+
+    def _losses_mean(self, which, losses):
+        n = self._loss_n[which]
+        return losses if n == 1 else self._loss_acc[which] / n
+
+    # (disc_cost, wasserstein term, gradient penalty, mean D(fake)) / (-, -, -, mean D(fake)) of the LAST update as means over its
+    # micro-batches; without accumulation d_losses / g_losses themselves
+    d_losses_mean = property(lambda self: self._losses_mean("d", self.d_losses))
+    g_losses_mean = property(lambda self: self._losses_mean("g", self.g_losses))
 
     def flush(self):
         """Apply any deferred optimiser update (before reading weights / at the end of the timed region)."""
@@ -530,14 +617,33 @@ class GanStep:
                 self.critic_step(images, labels, noises[i], alphas[i])
             self.generator_step(images, noises[critic_iters])
 
+    def train_iteration_accumulated(self, batches, noises, alphas, critic_iters=1, reuse_g_encoder=False):
+        """train_iteration with every update taken from N = len(batches) micro-batches of B rows: the update of the N * B rows.
+        batches: [(images, labels)] * N, all resident on the device for the whole iteration (every update reads all of them);
+        noises[i][k] / alphas[i][k]: update i (critic updates first, the generator update last), micro-batch k.  Order: per critic
+        update all N micro-batches, then ONE optimiser step; then the generator update the same way.  reuse_g_encoder: G's encoder
+        runs 2 N times per iteration instead of N * (critic_iters + 1) (generator_forward).  N = 1 is train_iteration."""
+        N = len(batches)
+        if N == 1:
+            return self.train_iteration(batches[0][0], batches[0][1], [n[0] for n in noises], [a[0] for a in alphas],
+                                        critic_iters, reuse_g_encoder)
+        with self.iteration(reuse_g_encoder):
+            for i in range(critic_iters):
+                for k, (images, labels) in enumerate(batches):
+                    self.critic_step(images, labels, noises[i][k], alphas[i][k], micro=(k, N))
+            for k, (images, _) in enumerate(batches):
+                self.generator_step(images, noises[critic_iters][k], micro=(k, N))
+
     @contextlib.contextmanager
     def iteration(self, reuse_g_encoder=False):
-        """The updates of ONE minibatch (train.py:362-368).  reuse_g_encoder: see generator_forward."""
+        """The updates of ONE minibatch (train.py:362-368), or of one group of micro-batches.  reuse_g_encoder: see generator_forward."""
         self._g_reuse, self._g_reuse_armed = None, bool(reuse_g_encoder)
+        self._g_reuse_slots = {}
         try:
             yield self
         finally:
             self._g_reuse, self._g_reuse_armed = None, False
+            self._g_reuse_slots = {}
 
     def argmax_tokens(self, logits):
         """tf.argmax(fake_inputs, -1) (train.py:270)."""

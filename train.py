@@ -5,6 +5,7 @@
     python train.py --checkpoints_dir ckpt --predict_dir graphs            # ranked scene graph of every test image
     python train.py --checkpoints_dir ckpt --metrics_out metrics.json      # R@K, mR@K, zsR@K of the test split
     python train.py --ema_decay 0.999 ...                                  # keep an average of G's weights; evaluation then uses it
+    python train.py --batch_size 64 --accumulate 8 ...                     # every update from 8 micro-batches: the batch-512 update
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -57,6 +58,13 @@ class ValidationEarlyStop(object):
         return False
 
 
+def micro_batch_ids(it, N):
+    """The micro-batches of the example stream that iteration `it` consumes with --accumulate N: m = it * N + k, k = 0 .. N - 1.
+    Micro-batch m is what iteration m of a run without accumulation reads (ShuffledStream.batch(m, B, rank, world)), so the update
+    of iteration `it` covers stream elements [it * N * B * world, (it + 1) * N * B * world)."""
+    return range(it * N, (it + 1) * N)
+
+
 class SceneGraphGAN(object):
 
     ############################################################
@@ -65,7 +73,7 @@ class SceneGraphGAN(object):
     def __init__(self, checkpoints_dir, summaries_dir, path_to_ims_to_triples, path_to_vocab, path_to_word_embeddings,
                  path_to_image_means, path_to_image_stds, critic_iters, batch_size, lambda_, resume,
                  synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True,
-                 ema_decay=0.0, eval_live=False):
+                 ema_decay=0.0, eval_live=False, accumulate=1):
         # Hyperparameters (train.py:26-32)
         self.CRITIC_ITERS = int(critic_iters)
         self.BATCH_SIZE = int(batch_size)
@@ -87,6 +95,12 @@ class SceneGraphGAN(object):
             raise ValueError("ema_decay must be 0 (off) or lie strictly between 0 and 1 (got %r)" % (ema_decay,))
         self.eval_live = bool(eval_live)
         self._in_eval = False
+        # accumulate = N > 1: every optimiser step is taken from N micro-batches of BATCH_SIZE rows (GanStep.train_iteration_accumulated:
+        # the mean of their gradients is the gradient of the N * BATCH_SIZE rows - every loss term is a mean over rows and no op couples
+        # samples); iteration `it` consumes micro-batches it * N .. it * N + N - 1 of the example stream (micro_batch_ids)
+        self.ACCUMULATE = int(accumulate)
+        if self.ACCUMULATE < 1:
+            raise ValueError("accumulate must be a positive number of micro-batches per update (got %r)" % (accumulate,))
         self.shuffle_buffer = bool(shuffle_buffer)      # tf.data shuffle(buffer_size = 10 * batch) on the repeated stream (train.py:176-179)
         self.checkpoints_dir, self.summaries_dir = checkpoints_dir, summaries_dir
         self.rank, self.world, local = dpmod.init_from_env()
@@ -235,7 +249,7 @@ class SceneGraphGAN(object):
 
     def _prefetcher(self, start, stop, workers=16):
         """tf.contrib.data.map_and_batch + prefetch (train.py:181-187) as decode threads + a pinned double buffer whose
-        host-to-device copy runs on its own stream while the previous batch trains."""
+        host-to-device copy runs on its own stream while the previous batch trains.  start / stop count (micro-)batches."""
         files, labs = self.dataset["train"]
         return PrefetchLoader(files, labs, self.BATCH_SIZE, lambda it: self._batch_indices(it, "loader"), self.image_means.numpy(),
                               self.image_stds.numpy(), self.device, stop, start=start, workers=workers, processes=workers > 2)
@@ -256,6 +270,8 @@ class SceneGraphGAN(object):
                   # the validation state of the loop (train.py:358-384): last loss, consecutive increases, batches consumed
                   "val": {"last": stopper.last if stopper else float("inf"), "count": stopper.count if stopper else 0,
                           "history": list(getattr(self, "val_history", []))}}
+            if self.ACCUMULATE > 1:         # (only a run that accumulates writes the key)
+                ck["accumulate"] = self.ACCUMULATE
             if self.step.G.has_average:     # (only a run that averages writes these keys: without it the checkpoint is what it was)
                 ck["G_ema"] = self.step.G.average_state()
                 # ... and where its noise stream stands, so that a resumed run continues the stream and its average is the one of
@@ -285,6 +301,9 @@ class SceneGraphGAN(object):
                 G.enable_averaging(saved["decay"])
                 G.restore_average(saved["flat"], saved["updates"])
         self.itr = ck["itr"]
+        if for_training and int(ck.get("accumulate", 1)) != self.ACCUMULATE and self.rank == 0:
+            print("resuming with --accumulate %d a run saved with %d: the data stream continues at micro-batch itr * %d = %d"
+                  % (self.ACCUMULATE, int(ck.get("accumulate", 1)), self.ACCUMULATE, self.itr * self.ACCUMULATE))
         self._resumed_val = ck.get("val")
         self._resumed_rng = ck.get("noise_rng") if (for_training and self.ema_decay > 0.0 and self.world == 1) else None
 
@@ -323,6 +342,21 @@ class SceneGraphGAN(object):
                             overlap_streams=self.two_streams)
         if self.ema_decay > 0.0:            # G only: the critic keeps its live weights everywhere
             self.step.G.enable_averaging(self.ema_decay)
+
+    def _accumulated_iteration(self, batches, gen):
+        """One iteration with every update taken from the N = len(batches) micro-batches: noise and alpha are drawn from `gen` in
+        the order (update, micro-batch) - with N = 1 the stream of the plain loop - and each update runs all micro-batches before
+        its one optimiser step (GanStep.train_iteration_accumulated)."""
+        B, C, N = self.BATCH_SIZE, self.CRITIC_ITERS, len(batches)
+        noises, alphas = [], []
+        for i in range(C + 1):
+            noises.append([])
+            alphas.append([])
+            for _ in range(N):
+                noises[i].append(torch.randn((B, 512), generator=gen).to(self.device))
+                if i < C:
+                    alphas[i].append(torch.rand((B,), generator=gen).to(self.device))
+        self.step.train_iteration_accumulated(batches, noises, alphas[:C], critic_iters=C, reuse_g_encoder=self.reuse_g_encoder)
 
     def load_checkpoint(self):
         """Build both networks and load the checkpoint in checkpoints_dir (weights, Adam state, iteration) as --resume does;
@@ -363,8 +397,8 @@ class SceneGraphGAN(object):
             self._resumed_rng = None
         vgen = torch.Generator().manual_seed(self.seed + 70007 + self.rank)
         log = open(os.path.join(self.summaries_dir, "losses.jsonl"), "a") if self.rank == 0 else None
-        B, t0, itr0 = self.BATCH_SIZE, time.time(), self.itr
-        loader = self._prefetcher(self.itr, n_it) if self.dataset is not None else None
+        B, t0, itr0, N = self.BATCH_SIZE, time.time(), self.itr, self.ACCUMULATE
+        loader = self._prefetcher(self.itr * N, n_it * N) if self.dataset is not None else None
         stopper, self.stopped_early, self.val_history = ValidationEarlyStop(patience), False, []
         rv = getattr(self, "_resumed_val", None)
         if rv is not None:          # a resumed run carries on with the validation iterator and the early-stop counters where it stopped
@@ -375,27 +409,37 @@ class SceneGraphGAN(object):
         diag_log = open(os.path.join(self.summaries_dir, "diagnostics.jsonl"), "a") if (self.rank == 0 and diagnostics_every > 0) else None
         try:
             while self.itr < n_it:
-                images, labels = next(loader) if loader is not None else self._next_batch(self.itr)
+                if N == 1:
+                    images, labels = next(loader) if loader is not None else self._next_batch(self.itr)
+                else:                       # all N micro-batches stay on the device for the whole iteration: every update reads all of them
+                    batches = [next(loader) if loader is not None else self._next_batch(m) for m in micro_batch_ids(self.itr, N)]
                 report = diagnostics_every > 0 and (self.itr + 1) % diagnostics_every == 0
                 if diagnostics_every > 0:
                     self.step.arm_diagnostics(report)
                 # every update of an iteration sees the same minibatch (train.py:175-190) and G's weights change only at its end: G's
                 # encoder runs once per iteration (exact; 10 of 11 encoder forwards of G saved at CRITIC_ITERS = 10)
-                with self.step.iteration(reuse_g_encoder=self.reuse_g_encoder):
-                    for _ in range(self.CRITIC_ITERS):                                  # train.py:364-365
+                if N > 1:
+                    self._accumulated_iteration(batches, gen)
+                else:
+                    with self.step.iteration(reuse_g_encoder=self.reuse_g_encoder):
+                        for _ in range(self.CRITIC_ITERS):                              # train.py:364-365
+                            noise = torch.randn((B, 512), generator=gen).to(self.device)
+                            alpha = torch.rand((B,), generator=gen).to(self.device)
+                            self.step.critic_step(images, labels, noise, alpha)
                         noise = torch.randn((B, 512), generator=gen).to(self.device)
-                        alpha = torch.rand((B,), generator=gen).to(self.device)
-                        self.step.critic_step(images, labels, noise, alpha)
-                    noise = torch.randn((B, 512), generator=gen).to(self.device)
-                    self.step.generator_step(images, noise)                             # train.py:368
+                        self.step.generator_step(images, noise)                         # train.py:368
                 itr = self.itr                                                          # the reference's 0-based loop variable
                 self.itr += 1
                 diag = self.step.diagnostics() if report else None
                 tensors = diag.pop("tensors") if diag is not None else None
+                if diag is not None and N > 1:
+                    diag["gp_slope_rows"] = B       # the slopes are those of the last micro-batch of the last critic update
                 if log is not None and self.itr % log_every == 0:
-                    d, g = self.step.d_losses.cpu().tolist(), self.step.g_losses.cpu().tolist()
-                    rate = B * self.world * (self.itr - itr0) / (time.time() - t0)      # of this run (a resumed run starts at itr0 > 0)
+                    d, g = self.step.d_losses_mean.cpu().tolist(), self.step.g_losses_mean.cpu().tolist()   # (N = 1: d_losses / g_losses)
+                    rate = B * N * self.world * (self.itr - itr0) / (time.time() - t0)  # of this run (a resumed run starts at itr0 > 0)
                     rec = {"itr": self.itr, "disc_loss": d[0], "gen_loss": -g[3], "gp": d[2], "triples_per_s": rate}
+                    if N > 1:
+                        rec["accumulate"] = N
                     if diag is not None:
                         rec["diag"] = diag
                     log.write(json.dumps(rec) + "\n"); log.flush()
@@ -929,6 +973,10 @@ def build_parser():
                              "at its k-th update, as tf.train.ExponentialMovingAverage), updated inside the generator's optimiser pass "
                              "and saved in the checkpoint; evaluation (the test after training, --test_only, --saliency_dir, "
                              "--predict_dir, --metrics_out) then runs the generator on the average (default 0: off)")
+    parser.add_argument("--accumulate", default=1, type=int,
+                        help="N >= 1: take every optimiser step from N micro-batches of --batch_size rows (gradients summed on the "
+                             "device, scaled by 1 / N inside the Adam pass): the update of N x batch_size rows per GPU; iteration "
+                             "i reads micro-batches i * N .. i * N + N - 1 of the example stream (default 1: off)")
     parser.add_argument("--eval_live", action="store_true",
                         help="evaluate the generator's live weights even where an average exists (from --ema_decay or the checkpoint)")
     return parser
@@ -948,7 +996,7 @@ if __name__ == "__main__":
                         critic_iters=params["critic_iters"], batch_size=params["batch_size"], lambda_=params["lambda"],
                         resume=params["resume"], synthetic=synthetic, two_streams=not params["single_stream"],
                         reuse_g_encoder=not params["recompute_generator_encoder"], shuffle_buffer=not params["no_shuffle_buffer"],
-                        ema_decay=params["ema_decay"], eval_live=params["eval_live"])
+                        ema_decay=params["ema_decay"], eval_live=params["eval_live"], accumulate=params["accumulate"])
     if params["saliency_dir"]:
         if not gan.load_checkpoint():
             print("--saliency_dir: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
