@@ -350,6 +350,40 @@ int sgg_swap_f32(float* a, float* b, long long n, void* stream);
  * function of the inputs).  Both 16-byte aligned, n > 0, the ranges must not overlap (argument error, nothing is launched). */
 int sgg_grad_accumulate(float* acc, const float* g, long long n, int first, void* stream);
 
+/* ---- guarded updates: global-norm clipping and the non-finite skip, decided on the device (csrc/guard.hip) ---------------------
+ * The reference clips nothing and checks nothing; a trainer of its kind is expected to bound an outlier update by the gradient's
+ * global norm and to drop an update whose gradient is not finite.  Both decisions need a reduction over the whole gradient arena;
+ * it is taken on the device and consumed by the Adam pass from device memory - no host read-back.
+ * sgg_grad_guard: reads grads[0 .. n) and writes `record`, eight fp64 values that persist from call to call:
+ *   per element x = grads[i] * grad_scale in fp32, as sgg_adam_tf_multi forms it; a finite x adds (double)x * (double)x to ss, a
+ *   non-finite one (Inf, NaN: the test of sgg_arena_stats) is only counted.
+ *     [0] ss     sum of squares of the finite elements          [1] the non-finite count
+ *     [2] norm   sqrt(ss) in fp64
+ *     [3] coef   (max_norm > 0 && norm > max_norm) ? (double)max_norm / norm : 1.0
+ *     [4] s_eff  (double)(float)((double)grad_scale * coef): the gradient scale the guarded Adam pass applies
+ *     [5] apply  (skip_nonfinite && [1] > 0) ? 0.0 : 1.0
+ *     [6] += 1 if coef < 1 and apply (updates clipped so far)   [7] += 1 if apply == 0 (updates skipped so far)
+ *   [6] and [7] are read-modify-written by one thread: the caller zero-fills the record once.  coef is EXACTLY 1 while the
+ *   threshold is not exceeded - on purpose not TF's clip_norm * min(1 / norm, 1 / clip_norm), from which it differs by at most an
+ *   ulp: a run whose threshold is never reached stays bit-identical to an unguarded one.  With skip_nonfinite = 0 and non-finite
+ *   elements present, norm is that of the finite elements and the step is applied as without a guard.
+ *   Two launches on `stream`: per-chunk rows (chunks of sgg_arena_stats_chunk() elements of the flat range) into `workspace`
+ *   (sgg_grad_guard_workspace_bytes(n), plain stores), then one workgroup sums the rows in a fixed order and writes the record.  No
+ *   atomics: bit-identical from call to call and for every `grid` (workgroups of the first launch; 0 = the default,
+ *   min(chunks, 4096)).  grads 16-byte aligned, record and workspace 8-byte aligned, n > 0, max_norm finite and >= 0 (0 = no
+ *   clipping), grad_scale finite (argument errors, nothing is launched); a workspace too small: SGG_ERR_WORKSPACE.
+ * sgg_adam_tf_multi_guarded / sgg_adam_tf_multi_ema_guarded: sgg_adam_tf_multi / sgg_adam_tf_multi_ema with `record` (device, as
+ *   sgg_grad_guard left it on the same stream) in place of grad_scale.  record[5] == 0: the kernel writes nothing - params, m, v
+ *   and ema keep every bit, NaN payloads included.  Otherwise the results are bit-identical to the unguarded entry point called
+ *   with grad_scale = (float)record[4].  Pointer rules of the unguarded entry points; record 8-byte aligned. */
+size_t sgg_grad_guard_workspace_bytes(long long n);
+int sgg_grad_guard(const float* grads, long long n, float grad_scale, float max_norm, int skip_nonfinite, int grid, void* workspace,
+                   size_t workspace_bytes, double* record, void* stream);
+int sgg_adam_tf_multi_guarded(float* params, const float* grads, float* m, float* v, long long n, float lr_t, float beta1,
+                              float beta2, float eps, const double* record, void* stream);
+int sgg_adam_tf_multi_ema_guarded(float* params, const float* grads, float* m, float* v, float* ema, long long n, float lr_t,
+                                  float beta1, float beta2, float eps, const double* record, float one_minus_decay, void* stream);
+
 /* ---- tf.argmax(x, axis=-1): train.py:270-271 ---------------------------------------------------------------- */
 int sgg_argmax_rows(const float* x, long long* out, int rows, int V, int ld, void* stream);
 

@@ -82,6 +82,10 @@ SIGNATURES = {
     "sgg_adam_tf_multi_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _f, _vp]),
     "sgg_swap_f32": (_i, [_vp, _vp, _ll, _vp]),
     "sgg_grad_accumulate": (_i, [_vp, _vp, _ll, _i, _vp]),
+    "sgg_grad_guard_workspace_bytes": (_sz, [_ll]),
+    "sgg_grad_guard": (_i, [_vp, _ll, _f, _f, _i, _i, _vp, _sz, _vp, _vp]),
+    "sgg_adam_tf_multi_guarded": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _vp, _vp]),
+    "sgg_adam_tf_multi_ema_guarded": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _vp, _f, _vp]),
     "sgg_argmax_rows": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sgg_rank_triples": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgg_match_triples": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
@@ -896,6 +900,46 @@ class HipKernels:
         assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (acc, g))
         self._check(self._timed("grad_accumulate_kernel", 0.0, lambda: self.lib.sgg_grad_accumulate(
             _p(acc), _p(g), n, int(bool(first)), self._stream()), (8.0 if first else 12.0) * n), "sgg_grad_accumulate")
+
+    # -- guarded updates (csrc/guard.hip, sgg_amd/guard.py) ---------------------------------------------
+    def grad_guard_workspace_bytes(self, n):
+        return int(self.lib.sgg_grad_guard_workspace_bytes(int(n)))
+
+    def grad_guard(self, grads, record, grad_scale=1.0, max_norm=0.0, skip_nonfinite=False, ws=None, grid=0):
+        """The decision of a guarded update (include/sgg_hip.h): the global norm and non-finite count of grads * grad_scale into the
+        persistent fp64 record [8] (zero-filled once by the caller; sgg_amd.guard.FIELDS), which the guarded Adam passes read on the
+        same stream.  ws: a uint8 buffer of grad_guard_workspace_bytes(n) (default: the stream's scratch buffer).  grid: workgroups
+        of the first launch (0 = default); the record does not depend on it.  Reads grads only."""
+        self._dev(grads, record, ws)
+        n = grads.numel()
+        assert grads.dtype == torch.float32 and grads.is_contiguous()
+        assert record.dtype == torch.float64 and tuple(record.shape) == (8,) and record.is_contiguous()
+        if ws is None:
+            ws = self.workspace(self.grad_guard_workspace_bytes(n))
+        self._check(self._timed("grad_guard(call: chunk rows + record)", 0.0, lambda: self.lib.sgg_grad_guard(
+            _p(grads), n, float(grad_scale), float(max_norm), int(bool(skip_nonfinite)), int(grid), _p(ws),
+            ws.numel() * ws.element_size(), _p(record), self._stream()), 4.0 * n), "sgg_grad_guard")
+        return record
+
+    def adam_guarded(self, params, grads, m, v, lr_t, b1, b2, eps, record):
+        """adam() with the gradient scale (float)record[4] read on the device, or nothing at all where record[5] == 0."""
+        self._dev(params, grads, m, v, record)
+        n = params.numel()
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (params, grads, m, v))
+        assert record.dtype == torch.float64 and tuple(record.shape) == (8,) and record.is_contiguous()
+        self._check(self._timed("adam_guarded_kernel", 0.0, lambda: self.lib.sgg_adam_tf_multi_guarded(
+            _p(params), _p(grads), _p(m), _p(v), n, float(lr_t), float(b1), float(b2), float(eps), _p(record), self._stream()),
+            28.0 * n), "sgg_adam_tf_multi_guarded")
+
+    def adam_ema_guarded(self, params, grads, m, v, ema, lr_t, b1, b2, eps, record, one_minus_decay=0.0):
+        """adam_ema() with the gradient scale (float)record[4] read on the device, or nothing at all where record[5] == 0."""
+        self._dev(params, grads, m, v, ema, record)
+        n = params.numel()
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (params, grads, m, v, ema))
+        assert record.dtype == torch.float64 and tuple(record.shape) == (8,) and record.is_contiguous()
+        self._check(self._timed("adam_ema_guarded_kernel", 0.0, lambda: self.lib.sgg_adam_tf_multi_ema_guarded(
+            _p(params), _p(grads), _p(m), _p(v), _p(ema), n, float(lr_t), float(b1), float(b2), float(eps), _p(record),
+            float(one_minus_decay), self._stream()), 36.0 * n), "sgg_adam_tf_multi_ema_guarded")
 
     # -- training diagnostics (csrc/stats.hip) ---------------------------------------------------------
     def arena_stats_chunk(self):

@@ -22,6 +22,7 @@ from collections import OrderedDict
 import torch
 
 from . import diagnostics, ema
+from . import guard as guardmod
 from .head import Head
 from .lib import option
 from .params import ADAM_B1, ADAM_B2, ADAM_EPS, ADAM_LR, EMBED_DIM, FEAT_C, NUM_UNITS, T_STEPS, ParamArena, tf_variable_name
@@ -120,7 +121,9 @@ class Network:
         a = self.arena
         lr_t = tf_adam_lr_t(self.adam_t)
         avg = self.opt.get("ema")
-        if avg is None:
+        if self.opt.get("guard") is not None:   # the decision on the device, then the Adam pass that reads it (csrc/guard.hip)
+            self._guarded_adam(lr_t, grad_scale, avg)
+        elif avg is None:
             self.K.adam(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat),
                         lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale)
         else:                                # the same step with the shadow update of the average in the same pass (csrc/ema.hip)
@@ -131,6 +134,72 @@ class Network:
             self.arena_stats(lr_t, grad_scale)
         a.version += 1                       # (encoders of other batch sizes on this arena re-derive their operand formats lazily)
         self.trunk.refresh_weights()
+
+    # ---- guarded updates (sgg_amd/guard.py, csrc/guard.hip) -----------------------------------------------
+    # opt["guard"] = {"record": fp64 [8] on the device, "ws": the reduction's workspace, "max_norm", "skip_nonfinite"}: state of the
+    # ARENA, like ema / diag.  What the host does NOT learn: whether a step was dropped - so a dropped step still advances adam_t
+    # (it consumes its number in the bias correction: with beta = (0.5, 0.9) the correction is within 1e-3 of 1 after about 60
+    # steps), the average's update count and arena.version.  The statistics pass describes the UNCLIPPED g * grad_scale, and an
+    # update delta that a dropped step did not apply; the record says which it was.
+    has_guard = property(lambda self: self.opt.get("guard") is not None)
+
+    def enable_guard(self, max_norm=0.0, skip_nonfinite=False):
+        """From now on every optimiser step of this arena is guarded: one reduction over the scaled gradient (grad_guard), then the
+        Adam pass reading the decision from device memory - clipped to the global norm max_norm (0: no clipping) and, with
+        skip_nonfinite, dropped as a whole where the gradient holds an Inf or NaN.  The first call allocates the record (zeroed)
+        and the workspace; a later call changes the settings only and keeps the counters."""
+        max_norm, skip_nonfinite = guardmod.check_settings(max_norm, skip_nonfinite)
+        gd = self.opt.get("guard")
+        if gd is None:
+            missing = [n for n in ("grad_guard", "adam_guarded", "adam_ema_guarded") if not hasattr(self.K, n)]
+            if missing:
+                raise RuntimeError("guarded updates need the grad_guard, adam_guarded and adam_ema_guarded kernels; the %r kernel "
+                                   "set lacks %s" % (getattr(self.K, "name", self.K), ", ".join(missing)))
+            dev = self.arena.flat.device
+            nbytes = self.K.grad_guard_workspace_bytes(self.arena.live_numel) if hasattr(self.K, "grad_guard_workspace_bytes") else 0
+            gd = self.opt["guard"] = {"record": torch.zeros(guardmod.NREC, dtype=torch.float64, device=dev),
+                                      "ws": torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)}
+        gd["max_norm"], gd["skip_nonfinite"] = max_norm, skip_nonfinite
+
+    def disable_guard(self):
+        """Stop guarding and free the record (its counters with it): the next optimiser step is the plain one again."""
+        self.finish_update()
+        self.opt.pop("guard", None)
+
+    def _guard(self, what):
+        gd = self.opt.get("guard")
+        if gd is None:
+            raise RuntimeError("%s: this network's updates are not guarded (enable_guard first)" % what)
+        return gd
+
+    def _guarded_adam(self, lr_t, grad_scale, avg):
+        a, gd = self.arena, self.opt["guard"]
+        self.K.grad_guard(a.live(self.grad_flat), gd["record"], grad_scale, gd["max_norm"], gd["skip_nonfinite"], ws=gd["ws"])
+        if avg is None:
+            self.K.adam_guarded(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat),
+                                lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, gd["record"])
+        else:
+            self.K.adam_ema_guarded(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat), a.live(avg["flat"]),
+                                    lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, gd["record"], ema.one_minus_decay(avg["decay"], avg["updates"]))
+            avg["updates"] += 1              # (also for a dropped step: the host does not know)
+
+    def guard_report(self):
+        """The record of the LAST guarded step as a dict (guard.report: norm, coef, s_eff, nonfinite, apply, and the cumulative
+        clipped / skipped counts; all zero before the first step).  Applies a pending update first; one device read."""
+        gd = self._guard("guard_report")
+        self.finish_update()
+        return guardmod.report(gd["record"].cpu().tolist(), gd["max_norm"], gd["skip_nonfinite"])
+
+    def guard_state(self):
+        """What a checkpoint keeps of the guard: the two cumulative counters {"clipped", "skipped"}."""
+        r = self.guard_report()
+        return {"clipped": r["clipped"], "skipped": r["skipped"]}
+
+    def restore_guard(self, clipped, skipped):
+        """Put saved counters back (guard_state; the settings in force stay)."""
+        gd = self._guard("restore_guard")
+        self.finish_update()
+        gd["record"][6:8] = torch.tensor([float(int(clipped)), float(int(skipped))], dtype=torch.float64)
 
     # ---- weight averaging (sgg_amd/ema.py, csrc/ema.hip) -------------------------------------------------
     # opt["ema"] = {"flat": buffer of the arena's layout, "decay", "updates": shadow updates applied, "swapped"}: state of the ARENA,
@@ -583,6 +652,28 @@ class GanStep:
         self.G.arm_diagnostics(on)
         self.D.arm_diagnostics(on)
 
+    # ---- guarded updates ---------------------------------------------------------------------------
+    def set_guard(self, max_norm=0.0, skip_nonfinite=False):
+        """Guard the updates of both networks (Network.enable_guard).  max_norm: one number for both, or (critic's, generator's);
+        0 = no clipping.  A network with neither control on is left - or put back - on the plain Adam pass."""
+        d_norm, g_norm = max_norm if isinstance(max_norm, (tuple, list)) else (max_norm, max_norm)
+        for net, mx in ((self.D, d_norm), (self.G, g_norm)):
+            mx, skip = guardmod.check_settings(mx, skip_nonfinite)
+            if mx > 0.0 or skip:
+                net.enable_guard(mx, skip)
+            else:
+                net.disable_guard()
+
+    def guard_reports(self):
+        """{"D": Network.guard_report(), "G": ...} of the guarded networks (empty: no guard is on).  ONE device read for both."""
+        self.flush()
+        nets = [(n, net) for n, net in (("D", self.D), ("G", self.G)) if net.has_guard]
+        if not nets:
+            return {}
+        host = torch.cat([net.opt["guard"]["record"] for _, net in nets]).cpu().tolist()
+        return {n: guardmod.report(host[i * guardmod.NREC:(i + 1) * guardmod.NREC], net.opt["guard"]["max_norm"],
+                                   net.opt["guard"]["skip_nonfinite"]) for i, (n, net) in enumerate(nets)}
+
     def diagnostics(self):
         """The statistics of each network's LAST optimiser step while armed, and of the critic's per-row slopes
         ||d sum(D(x_hat)) / d x_hat|| that the last critic update's gradient penalty left on the device:
@@ -607,6 +698,9 @@ class GanStep:
         out["gp_slope"] = {"min": mn if finite else None, "mean": total / finite if finite else None, "max": mx if finite else None,
                            "share_above_1": above / finite if finite else None, "nonfinite": int(bad)}
         out["tensors"] = {n: diagnostics.tensor_rows(rows[n], st["names"]) for n, st in (("G", gd), ("D", dd))}
+        if self.G.has_guard or self.D.has_guard:
+            # the rows above describe the unclipped gradient, and an update delta that a dropped step did not apply: the records say
+            out["guard"] = self.guard_reports()
         return out
 
     def train_iteration(self, images, labels, noises, alphas, critic_iters=1, reuse_g_encoder=False):

@@ -6,6 +6,7 @@
     python train.py --checkpoints_dir ckpt --metrics_out metrics.json      # R@K, mR@K, zsR@K of the test split
     python train.py --ema_decay 0.999 ...                                  # keep an average of G's weights; evaluation then uses it
     python train.py --batch_size 64 --accumulate 8 ...                     # every update from 8 micro-batches: the batch-512 update
+    python train.py --clip_grad_norm 5,50 --skip_nonfinite ...             # clip D / G updates by global norm, drop non-finite ones
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -33,6 +34,7 @@ from architectures.discriminator_with_attention import Discriminator
 
 import sgg_amd  # noqa: F401
 from sgg_amd import dp as dpmod
+from sgg_amd import guard as guardmod
 from sgg_amd.api import kernels_for
 from sgg_amd.data import PrefetchLoader, ShuffledStream, parse_image
 from sgg_amd.diagnostics import raise_if_nonfinite
@@ -73,7 +75,7 @@ class SceneGraphGAN(object):
     def __init__(self, checkpoints_dir, summaries_dir, path_to_ims_to_triples, path_to_vocab, path_to_word_embeddings,
                  path_to_image_means, path_to_image_stds, critic_iters, batch_size, lambda_, resume,
                  synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True,
-                 ema_decay=0.0, eval_live=False, accumulate=1):
+                 ema_decay=0.0, eval_live=False, accumulate=1, clip_grad_norm=0.0, skip_nonfinite=False):
         # Hyperparameters (train.py:26-32)
         self.CRITIC_ITERS = int(critic_iters)
         self.BATCH_SIZE = int(batch_size)
@@ -101,6 +103,15 @@ class SceneGraphGAN(object):
         self.ACCUMULATE = int(accumulate)
         if self.ACCUMULATE < 1:
             raise ValueError("accumulate must be a positive number of micro-batches per update (got %r)" % (accumulate,))
+        # clip_grad_norm = X or (critic's, generator's) or "X[,Y]", 0 = off: each network's update is scaled down to that global norm
+        # where its gradient exceeds it; skip_nonfinite: an update whose gradient holds an Inf or NaN is dropped.  Both are decided on
+        # the device inside the optimiser step (step.Network.enable_guard; the host learns of it through the record it logs)
+        self.clip_norms = tuple(guardmod.check_settings(x)[0] for x in clip_grad_norm) if isinstance(clip_grad_norm, (tuple, list)) \
+            else guardmod.parse_clip_grad_norm(clip_grad_norm)
+        if len(self.clip_norms) != 2:
+            raise ValueError("clip_grad_norm takes one number or (critic's, generator's) (got %r)" % (clip_grad_norm,))
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.skip_nonfinite or any(x > 0.0 for x in self.clip_norms)
         self.shuffle_buffer = bool(shuffle_buffer)      # tf.data shuffle(buffer_size = 10 * batch) on the repeated stream (train.py:176-179)
         self.checkpoints_dir, self.summaries_dir = checkpoints_dir, summaries_dir
         self.rank, self.world, local = dpmod.init_from_env()
@@ -272,6 +283,8 @@ class SceneGraphGAN(object):
                           "history": list(getattr(self, "val_history", []))}}
             if self.ACCUMULATE > 1:         # (only a run that accumulates writes the key)
                 ck["accumulate"] = self.ACCUMULATE
+            if self.step.D.has_guard or self.step.G.has_guard:      # (only a guarded run writes the key: the clipped / skipped counts)
+                ck["guard"] = {n: net.guard_state() for n, net in (("D", self.step.D), ("G", self.step.G)) if net.has_guard}
             if self.step.G.has_average:     # (only a run that averages writes these keys: without it the checkpoint is what it was)
                 ck["G_ema"] = self.step.G.average_state()
                 # ... and where its noise stream stands, so that a resumed run continues the stream and its average is the one of
@@ -300,6 +313,14 @@ class SceneGraphGAN(object):
             else:                           # evaluation-only modes use the checkpoint's average without the flag
                 G.enable_averaging(saved["decay"])
                 G.restore_average(saved["flat"], saved["updates"])
+        saved_guard = ck.get("guard")
+        if saved_guard is not None and for_training:
+            kept = [n for n, net in (("D", self.step.D), ("G", self.step.G)) if net.has_guard and n in saved_guard]
+            for n in kept:
+                getattr(self.step, n).restore_guard(saved_guard[n]["clipped"], saved_guard[n]["skipped"])
+            if len(kept) < len(saved_guard) and self.rank == 0:
+                print("resuming without --clip_grad_norm / --skip_nonfinite for %s: the checkpoint's clipped / skipped counts are dropped"
+                      % ", ".join(n for n in saved_guard if n not in kept))
         self.itr = ck["itr"]
         if for_training and int(ck.get("accumulate", 1)) != self.ACCUMULATE and self.rank == 0:
             print("resuming with --accumulate %d a run saved with %d: the data stream continues at micro-batch itr * %d = %d"
@@ -342,6 +363,8 @@ class SceneGraphGAN(object):
                             overlap_streams=self.two_streams)
         if self.ema_decay > 0.0:            # G only: the critic keeps its live weights everywhere
             self.step.G.enable_averaging(self.ema_decay)
+        if self.guarded:                    # (never called otherwise: an unguarded run launches what it always did)
+            self.step.set_guard(self.clip_norms, self.skip_nonfinite)
 
     def _accumulated_iteration(self, batches, gen):
         """One iteration with every update taken from the N = len(batches) micro-batches: noise and alpha are drawn from `gen` in
@@ -440,6 +463,8 @@ class SceneGraphGAN(object):
                     rec = {"itr": self.itr, "disc_loss": d[0], "gen_loss": -g[3], "gp": d[2], "triples_per_s": rate}
                     if N > 1:
                         rec["accumulate"] = N
+                    if self.guarded:        # the records of each network's last update and the clipped / skipped counts so far
+                        rec["guard"] = self.step.guard_reports()
                     if diag is not None:
                         rec["diag"] = diag
                     log.write(json.dumps(rec) + "\n"); log.flush()
@@ -918,6 +943,13 @@ def _str2bool(v):
     raise argparse.ArgumentTypeError("expected a boolean, got %r" % (v,))
 
 
+def _clip_arg(text):
+    try:
+        return guardmod.parse_clip_grad_norm(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--checkpoints_dir", help="Where to save the checkpoints", default="./checkpoints")
@@ -977,6 +1009,15 @@ def build_parser():
                         help="N >= 1: take every optimiser step from N micro-batches of --batch_size rows (gradients summed on the "
                              "device, scaled by 1 / N inside the Adam pass): the update of N x batch_size rows per GPU; iteration "
                              "i reads micro-batches i * N .. i * N + N - 1 of the example stream (default 1: off)")
+    parser.add_argument("--clip_grad_norm", default=(0.0, 0.0), type=_clip_arg, metavar="X[,Y]",
+                        help="clip every update to this global gradient norm (the gradient is scaled by X / norm where its norm "
+                             "exceeds X; decided on the device inside the optimiser step): one number applies to both networks, two "
+                             "are the critic's, then the generator's; 0 means off (default 0)")
+    parser.add_argument("--skip_nonfinite", action="store_true",
+                        help="drop an update whose gradient holds an Inf or NaN: parameters, Adam moments and the weight average keep "
+                             "every bit (decided on the device; the step count still advances); the counts of clipped and skipped "
+                             "updates are logged under \"guard\" in losses.jsonl and saved in the checkpoint")
+    parser.add_argument("--log_every", default=10, type=int, help="iterations between the loss records of losses.jsonl (default 10)")
     parser.add_argument("--eval_live", action="store_true",
                         help="evaluate the generator's live weights even where an average exists (from --ema_decay or the checkpoint)")
     return parser
@@ -996,7 +1037,8 @@ if __name__ == "__main__":
                         critic_iters=params["critic_iters"], batch_size=params["batch_size"], lambda_=params["lambda"],
                         resume=params["resume"], synthetic=synthetic, two_streams=not params["single_stream"],
                         reuse_g_encoder=not params["recompute_generator_encoder"], shuffle_buffer=not params["no_shuffle_buffer"],
-                        ema_decay=params["ema_decay"], eval_live=params["eval_live"], accumulate=params["accumulate"])
+                        ema_decay=params["ema_decay"], eval_live=params["eval_live"], accumulate=params["accumulate"],
+                        clip_grad_norm=params["clip_grad_norm"], skip_nonfinite=params["skip_nonfinite"])
     if params["saliency_dir"]:
         if not gan.load_checkpoint():
             print("--saliency_dir: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
@@ -1026,6 +1068,6 @@ if __name__ == "__main__":
             sys.exit(2)
         gan.test(max_images=params["max_test_images"])
     else:
-        gan.train(max_iterations=params["max_iterations"], validate_every=params["validate_every"],
+        gan.train(max_iterations=params["max_iterations"], log_every=max(1, params["log_every"]), validate_every=params["validate_every"],
                   test_max_images=params["max_test_images"], diagnostics_every=params["diagnostics_every"],
                   halt_on_nonfinite=params["halt_on_nonfinite"])
