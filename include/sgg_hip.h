@@ -420,6 +420,35 @@ int sgg_rank_triples(const long long* tokens, const float* d, int N, int nb, int
 int sgg_match_triples(const long long* ranked, const int* n_distinct, int nb, int K, const long long* gt, const int* gt_count, int M,
                       int V, int* pos, int* n_gt, void* stream);
 
+/* ---- K-best decoding: ranked distinct triples from the generator's softmax (csrc/kbest.hip) --------------------------------
+ * The three decoder outputs of a head row (generator_with_attention.py:88, the tf.layers.dense of each step) depend on the noise and
+ * the LSTM state, never on the token of the step before: given one noise vector the distribution over triples is the product of
+ * the three softmaxes.  Finite logits are a precondition of both entry points.
+ * sgg_kbest_triples: the K most probable triples of every head row, one workgroup per row.
+ *   logits fp32 [R][3][V], rows `ld` >= 3 V floats apart.  lse fp32 [R][3]: the log-sum-exp of each slot, stabilised by its maximum,
+ *   fixed summation order.  a_t(x) = logits[t][x] - lse[t] and lp(s, p, o) = (a_0(s) + a_1(p)) + a_2(o), fp32 in that association.
+ *   Tokens of a slot rank by (logit descending, token ascending); triples rank by (lp descending, then the tuple of slot ranks
+ *   (i, j, l) ascending lexicographically).  triples int64 [R][K][3] and logp fp32 [R][K]: the first K triples in that order and
+ *   their lp.  Exact: only the top min(K, V) tokens of a slot and the rank tuples with (i+1)(j+1)(l+1) <= K can take part (at most
+ *   2045 at K = 128).  R >= 1, 1 <= V <= 2^21, 1 <= K <= min(128, V^3).  Two calls give the same bits.
+ * sgg_kbest_merge: the lists of an image's N samples merged into one ranked distinct list, one workgroup per image.
+ *   lists int64 [N][nb][Kc][3] (sample k of image j is row k * nb + j, as everywhere; the triples of one list are distinct - the
+ *   output of sgg_kbest_triples on the same logits), logits and ld as above with R = N * nb, lse fp32 [N][nb][3].  An entry with a
+ *   token outside [0, V) is ignored.  For every distinct triple c of the image's N * Kc entries and EVERY sample k (whether or not
+ *   its own list held c): lp_k(c) from logits and lse as above; m = max_k lp_k(c);
+ *   score(c) = m + (log(sum_k exp(lp_k(c) - m)) - log N), summed in sample order in fp32: the log-probability of c under the
+ *   mixture of the N noise draws.  Order: score descending, ties by the packed triple (s, p, o) ascending.  For image j and
+ *   u < min(n_distinct[j], K): triples int64 [nb][K][3], scores fp32 [nb][K], best_sample int32 [nb][K] (the smallest k with
+ *   lp_k = m), best_logp fp32 [nb][K] (m), counts int32 [nb][K] (the lists that hold c); n_distinct int32 [nb].  Slots behind
+ *   n_distinct[j] hold -1, NaN, -1, NaN, 0.  triples / n_distinct have the layout of sgg_rank_triples (sgg_match_triples takes
+ *   them).  N = 1: the list itself.  N > 1: the candidates are the union of the N lists, which approximates the mixture's own K
+ *   best (a triple that is in no sample's list cannot appear).  N * Kc <= 4096, 1 <= K <= N * Kc, 1 <= V <= 2^21. */
+int sgg_kbest_triples(const float* logits, long long ld, int R, int V, int K, long long* triples, float* logp, float* lse,
+                      void* stream);
+int sgg_kbest_merge(const long long* lists, const float* logits, long long ld, const float* lse, int N, int nb, int Kc, int V, int K,
+                    long long* triples, float* scores, int* best_sample, float* best_logp, int* counts, int* n_distinct,
+                    void* stream);
+
 /* ---- training diagnostics: per-tensor norms and non-finite counts of a network's arenas (csrc/stats.hip) ----------------------
  * One read-only streaming pass over params, grads, m and v: fp32 arenas of ONE layout, every tensor 16-byte aligned and rounded up
  * to 4 elements (the arena ends on such a boundary), as sgg_adam_tf_multi takes them.

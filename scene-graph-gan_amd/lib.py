@@ -89,6 +89,8 @@ SIGNATURES = {
     "sgg_argmax_rows": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sgg_rank_triples": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgg_match_triples": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "sgg_kbest_triples": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "sgg_kbest_merge": (_i, [_vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgg_arena_stats_chunk": (_i, []),
     "sgg_arena_stats_nstat": (_i, []),
     "sgg_arena_stats_workspace_bytes": (_sz, [_i]),
@@ -1040,6 +1042,63 @@ class HipKernels:
             res[name] = t
         self._check(self.lib.sgg_match_triples(_p(ranked), _p(n_distinct), nb, K, _p(gt), _p(gt_count), M, V, _p(res["pos"]),
                                                _p(res["n_gt"]), self._stream()), "sgg_match_triples")
+        return res
+
+    @staticmethod
+    def _logit_rows(logits):
+        """[..., 3, V] logits whose leading dimensions are rows a fixed stride apart (Generator.sample's view of the head rows, or a
+        column slice of a wider buffer) -> ([R, 3, V] view, row stride)."""
+        assert logits.dtype == torch.float32 and logits.dim() >= 3 and logits.shape[-2] == 3
+        V = int(logits.shape[-1])
+        x = logits.reshape(-1, 3, V)
+        assert x.data_ptr() == logits.data_ptr() and (x.stride(2) == 1 or V == 1) and x.stride(1) == V, "logits rows must be [3, V] contiguous"
+        ld = x.stride(0) if x.shape[0] > 1 else max(x.stride(0), 3 * V)
+        return x, int(ld)
+
+    def _out_tensors(self, spec, out, device):
+        res = {}
+        for name, (shape, dtype) in spec.items():
+            t = out[name] if out is not None else torch.empty(shape, dtype=dtype, device=device)
+            self._dev(t)
+            assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous(), name
+            res[name] = t
+        return res
+
+    def kbest_triples(self, logits, K, out=None):
+        """The K most probable triples of every head row under the product of its three softmaxes (csrc/kbest.hip): logits fp32
+        [..., 3, V] (R rows a fixed stride apart) -> dict of device tensors: triples int64 [R, K, 3], logp [R, K] (descending; ties by
+        the slot ranks (i, j, l)), lse [R, 3].  Exact and deterministic; 1 <= K <= min(128, V^3); finite logits are a precondition.
+        out: optional dict of preallocated contiguous tensors under those names."""
+        self._dev(logits)
+        x, ld = self._logit_rows(logits)
+        R, V, K = int(x.shape[0]), int(x.shape[2]), max(int(K), 0)
+        res = self._out_tensors({"triples": ((R, K, 3), torch.int64), "logp": ((R, K), torch.float32), "lse": ((R, 3), torch.float32)},
+                                out, logits.device)
+        self._check(self.lib.sgg_kbest_triples(_p(x), ld, R, V, K, _p(res["triples"]), _p(res["logp"]), _p(res["lse"]), self._stream()),
+                    "sgg_kbest_triples")
+        return res
+
+    def kbest_merge(self, triples, logits, lse, K, out=None):
+        """The K-best lists of an image's N samples merged into one ranked DISTINCT list (csrc/kbest.hip): triples int64
+        [N, nb, Kc, 3] and lse [N, nb, 3] (kbest_triples' outputs on `logits`, reshaped), logits fp32 [N, nb, 3, V] -> dict of device
+        tensors: triples int64 [nb, K, 3], scores [nb, K] (log-probability under the mixture of the N samples, descending; ties by
+        the triple), best_sample int32 [nb, K] (the sample that gives the triple its highest probability), best_logp [nb, K] (that
+        probability's log), counts int32 [nb, K] (lists that hold the triple), n_distinct int32 [nb]; slots behind n_distinct hold
+        -1 / NaN / -1 / NaN / 0.  N = 1: the exact K-best list.  N > 1: the candidates are the union of the N lists, which
+        approximates the mixture's own K best.  N * Kc <= 4096, 1 <= K <= N * Kc.  out: optional dict of preallocated tensors."""
+        self._dev(triples, logits, lse)
+        assert triples.dtype == torch.int64 and triples.dim() == 4 and triples.shape[3] == 3 and triples.is_contiguous()
+        N, nb, Kc = int(triples.shape[0]), int(triples.shape[1]), int(triples.shape[2])
+        assert logits.dim() == 4 and tuple(logits.shape[:3]) == (N, nb, 3), "logits must be [N, nb, 3, V]"
+        x, ld = self._logit_rows(logits)
+        V, K = int(x.shape[2]), max(int(K), 0)
+        assert lse.dtype == torch.float32 and lse.numel() == N * nb * 3 and lse.is_contiguous(), "lse must be contiguous [N, nb, 3]"
+        res = self._out_tensors({"triples": ((nb, K, 3), torch.int64), "scores": ((nb, K), torch.float32),
+                                 "best_sample": ((nb, K), torch.int32), "best_logp": ((nb, K), torch.float32),
+                                 "counts": ((nb, K), torch.int32), "n_distinct": ((nb,), torch.int32)}, out, triples.device)
+        self._check(self.lib.sgg_kbest_merge(_p(triples), _p(x), ld, _p(lse), N, nb, Kc, V, K, _p(res["triples"]), _p(res["scores"]),
+                                             _p(res["best_sample"]), _p(res["best_logp"]), _p(res["counts"]), _p(res["n_distinct"]),
+                                             self._stream()), "sgg_kbest_merge")
         return res
 
     def fill(self, t, value):

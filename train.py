@@ -35,6 +35,7 @@ from architectures.discriminator_with_attention import Discriminator
 import sgg_amd  # noqa: F401
 from sgg_amd import dp as dpmod
 from sgg_amd import guard as guardmod
+from sgg_amd import kbest as kbestmod
 from sgg_amd.api import kernels_for
 from sgg_amd.data import PrefetchLoader, ShuffledStream, parse_image
 from sgg_amd.diagnostics import raise_if_nonfinite
@@ -691,13 +692,17 @@ class SceneGraphGAN(object):
             out.append((x if isinstance(x, str) else str(i), x))
         return out
 
-    def _sampling_setup(self, who, n_samples, top_k):
-        """(kernels, V, TEST_BATCH_SIZE, samples per image, list slots) of predict() / evaluate(); builds the networks if needed."""
+    def _sampling_setup(self, who, n_samples, top_k, decode="samples"):
+        """(kernels, V, TEST_BATCH_SIZE, samples per image, list slots) of predict() / evaluate(); builds the networks if needed.
+        decode="kbest": the defaults and limits of sgg_amd.kbest.setup."""
         if self.step is None:
             images, _ = self._next_batch(0)
             self._constructOps(images)
         self.step.flush()
         TB = max(1, self.TEST_BATCH_SIZE)
+        if decode == "kbest":
+            N, _, top_k = kbestmod.setup(who, n_samples, top_k, len(self.vocab), TB)
+            return kernels_for(self.device), len(self.vocab), TB, N, top_k
         N = int(n_samples) if n_samples is not None else self.TEST_BATCH_MULTIPLIER * TB
         top_k = int(top_k) if top_k is not None else N
         if not 1 <= top_k <= N <= 4096:
@@ -718,17 +723,16 @@ class SceneGraphGAN(object):
         views = lambda host: {name: host[offs[name]:offs[name] + size(dt, shape)].view(dt).reshape(shape) for name, dt, shape in parts}
         return packed, out, views
 
-    def _ranked_batches(self, K, items, N, nb, top_k, descending, out):
-        """The sampling passes predict() and evaluate() share.  items: [(key, image tensor or path)]; per batch of nb images (the
-        last one padded with its last image): Generator.sample -> argmax_rows -> Discriminator.score_samples -> rank_triples into
-        `out`; yields (i0, n) = first item and number of real images of the batch, with `out` (and self.g.alphas) holding its
-        results.  Noise: per image ceil(N / TEST_BATCH_SIZE) draws of [TEST_BATCH_SIZE, 512] from seed + 123, image after image."""
-        V, TB = len(self.vocab), max(1, self.TEST_BATCH_SIZE)
+    def _sample_batches(self, items, N, nb):
+        """The generator passes both decoding modes share.  items: [(key, image tensor or path)]; per batch of nb images (the last
+        one padded with its last image): Generator.sample; yields (i0, n, images, logits) = first item and number of real images of
+        the batch, its images and its logits [N, nb, 3, V] (a view of the head rows: the next batch overwrites it).  Noise: per
+        image ceil(N / TEST_BATCH_SIZE) draws of [TEST_BATCH_SIZE, 512] from seed + 123, image after image."""
+        TB = max(1, self.TEST_BATCH_SIZE)
         passes = -(-N // TB)
         load = lambda x: self._parseFunction(x) if isinstance(x, str) else x
         pool = ThreadPoolExecutor(max_workers=min(16, nb)) if any(isinstance(x, str) for _, x in items) else None
         fetch = lambda i0: [pool.submit(load, x) if pool is not None else x for _, x in items[i0:i0 + nb]]
-        toks = torch.empty((N, nb, 3), dtype=torch.int64, device=self.device)
         gen = torch.Generator().manual_seed(self.seed + 123)
         try:
             pending = fetch(0)
@@ -741,32 +745,62 @@ class SceneGraphGAN(object):
                 for j in range(n):
                     for p in range(passes):
                         noise[p * TB:(p + 1) * TB, j] = torch.randn((TB, 512), generator=gen)
-                logits = self.g.sample(images, N, noise[:N].to(self.device))
-                K.argmax_rows(logits, toks.view(-1))
-                d = self.d.score_samples(logits, images)
-                K.rank_triples(toks, d.view(N, nb, 3), top_k, descending=descending, vocab=V, out=out)
-                yield i0, n
+                yield i0, n, images, self.g.sample(images, N, noise[:N].to(self.device))
         finally:
             if pool is not None:
                 pool.shutdown(wait=True, cancel_futures=True)
 
+    def _ranked_batches(self, K, items, N, nb, top_k, descending, out):
+        """The sampling passes predict() and evaluate() share: per batch of _sample_batches, argmax_rows ->
+        Discriminator.score_samples -> rank_triples into `out`; yields (i0, n) with `out` (and self.g.alphas) holding the batch's
+        results."""
+        V = len(self.vocab)
+        toks = torch.empty((N, nb, 3), dtype=torch.int64, device=self.device)
+        with contextlib.closing(self._sample_batches(items, N, nb)) as batches:
+            for i0, n, images, logits in batches:
+                K.argmax_rows(logits, toks.view(-1))
+                d = self.d.score_samples(logits, images)
+                K.rank_triples(toks, d.view(N, nb, 3), top_k, descending=descending, vocab=V, out=out)
+                yield i0, n
+
+    def _kbest_batches(self, K, items, N, nb, top_k, out):
+        """K-best decoding of the same passes: per batch of _sample_batches, kbest_triples (the list_width most probable triples of
+        every head row) -> kbest_merge into `out`.  The discriminator is not run."""
+        width = kbestmod.list_width(N, len(self.vocab))
+        lists = {"triples": torch.empty((N * nb, width, 3), dtype=torch.int64, device=self.device),
+                 # (the per-row logp is an output the binding requires; nothing here reads it: the merge scores every triple anew
+                 #  over all N samples)
+                 "logp": torch.empty((N * nb, width), dtype=torch.float32, device=self.device),
+                 "lse": torch.empty((N * nb, 3), dtype=torch.float32, device=self.device)}
+        with contextlib.closing(self._sample_batches(items, N, nb)) as batches:
+            for i0, n, images, logits in batches:
+                K.kbest_triples(logits, width, out=lists)
+                K.kbest_merge(lists["triples"].view(N, nb, width, 3), logits, lists["lse"], top_k, out=out)
+                yield i0, n
+
     def _predict_iter(self, items=None, max_images=None, n_samples=None, top_k=None, descending=False, with_attention=False,
-                      logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
+                      logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES, decode="samples"):
         """predict(), one image at a time (write_predictions streams it to disk)."""
-        K, V, TB, N, top_k = self._sampling_setup("predict", n_samples, top_k)
+        kbest = kbestmod.check_decode(decode, descending) == "kbest"
+        K, V, TB, N, top_k = self._sampling_setup("predict", n_samples, top_k, decode)
         items = self._predict_items(items, max_images)
         if not items:
             return
         nb = images_per_pass(N, V, TB, len(items), logits_budget_bytes)
-        ordering = "%s mean critic score" % ("descending" if descending else "ascending")
+        ordering = kbestmod.ORDERING if kbest else "%s mean critic score" % ("descending" if descending else "ascending")
         # the ranked outputs of a batch live in ONE device buffer (carved into the kernel's output tensors): one copy to the host
-        packed, out, views = self._device_pack(
-            [("triples", np.int64, (nb, top_k, 3)), ("scores", np.float32, (nb, top_k)), ("first_rank", np.int32, (nb, top_k)),
-             ("first_sample", np.int32, (nb, top_k)), ("counts", np.int32, (nb, top_k)), ("n_distinct", np.int32, (nb,))], self.device)
+        # (K-best: the kernel's best_sample is the record's first_sample, the sample that gives the triple its highest probability)
+        fields = [("scores", np.float32), ("best_sample", np.int32), ("best_logp", np.float32), ("counts", np.int32)] if kbest else \
+                 [("scores", np.float32), ("first_rank", np.int32), ("first_sample", np.int32), ("counts", np.int32)]
+        packed, out, views = self._device_pack([("triples", np.int64, (nb, top_k, 3))] + [(f, dt, (nb, top_k)) for f, dt in fields] +
+                                               [("n_distinct", np.int32, (nb,))], self.device)
+        sample_of = "best_sample" if kbest else "first_sample"
         col = torch.arange(nb, device=self.device).view(nb, 1)
-        for i0, n in self._ranked_batches(K, items, N, nb, top_k, descending, out):
+        batches = self._kbest_batches(K, items, N, nb, top_k, out) if kbest else \
+            self._ranked_batches(K, items, N, nb, top_k, descending, out)
+        for i0, n in batches:
             if with_attention:      # the attention of every triple's first-occurrence sample: head row first_sample * nb + j
-                rows = out["first_sample"].long().clamp_(min=0) * nb + col
+                rows = out[sample_of].long().clamp_(min=0) * nb + col
                 al = self.g.alphas
                 side = int(round(al.shape[-1] ** 0.5))
                 att_h = al[rows.view(-1)].view(nb, top_k, 3, side, side).cpu().numpy()
@@ -775,8 +809,8 @@ class SceneGraphGAN(object):
                 nd = int(h["n_distinct"][j])
                 U = min(nd, top_k)
                 r = {"image": items[i0 + j][0], "n_distinct": nd, "ordering": ordering}
-                for name in ("triples", "scores", "first_rank", "first_sample", "counts"):
-                    r[name] = h[name][j, :U].copy()
+                for name in ["triples"] + [f for f, _ in fields]:
+                    r["first_sample" if name == "best_sample" else name] = h[name][j, :U].copy()
                 r["words"] = [[self.reverse_vocab.get(int(i), "UNK") for i in row] for row in r["triples"]]
                 r["graph"] = scene_graph(r["triples"], r["scores"], r["counts"], self.reverse_vocab)
                 if with_attention:
@@ -784,7 +818,7 @@ class SceneGraphGAN(object):
                 yield r
 
     def predict(self, items=None, max_images=None, n_samples=None, top_k=None, descending=False, with_attention=False,
-                logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
+                logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES, decode="samples"):
         """The scene graph of every image: its n_samples generator samples (default TEST_BATCH_MULTIPLIER x TEST_BATCH_SIZE) scored by
         the critic as in test(), reduced on the device to the DISTINCT triples in ranked order (K.rank_triples: ascending mean
         critic score - the order of test() - or descending=True for the highest score first; ties by sample index), the first top_k
@@ -801,25 +835,44 @@ class SceneGraphGAN(object):
         Discriminator.score_samples -> rank_triples, one copy of the ranked outputs to the host per batch (tokens and scores of the
         samples stay on the device).  Noise: per image ceil(n_samples / TEST_BATCH_SIZE) draws of [TEST_BATCH_SIZE, 512] from seed
         + 123, image after image, the first n_samples rows used - with the defaults the stream of test(), sample for sample.
-        Touches no weights and no optimiser state; usable on an untrained model, as test() is."""
-        with self._eval_weights():
-            return list(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention, logits_budget_bytes))
+        Touches no weights and no optimiser state; usable on an untrained model, as test() is.
 
-    def write_predictions(self, out_dir, max_images=None, n_samples=None, top_k=None, descending=False, items=None):
+        decode="kbest" (default "samples": everything above): no tokens are sampled and the critic is not run.  The generator's three
+        softmaxes are independent given the noise, so each of the n_samples head rows (default here: TEST_BATCH_SIZE) yields its
+        sgg_amd.kbest.list_width most probable triples exactly (K.kbest_triples), and K.kbest_merge ranks the distinct triples of an
+        image's lists by their log-probability under the mixture of its n_samples noise draws, highest first (ties by the triple).
+        Same batches, padding, noise stream (the first n_samples rows are the same draws) and weights.  The record then holds
+        triples, words, scores [U] (the mixture log-probability), first_sample [U] (the sample that gives the triple its highest
+        probability: with_attention shows that sample's attention), best_logp [U] (that probability's log), counts [U] (lists that
+        hold the triple), n_distinct, graph, ordering and image, and no first_rank.  top_k <= n_samples x list width (default: all
+        of them); descending=True is rejected.  With one sample the list is the exact K-best list; with more, the candidates are the
+        union of the per-sample lists, which approximates the mixture's own K best."""
+        kbestmod.check_decode(decode, descending)
+        with self._eval_weights():
+            return list(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention, logits_budget_bytes,
+                                           decode))
+
+    def write_predictions(self, out_dir, max_images=None, n_samples=None, top_k=None, descending=False, items=None, decode="samples"):
         """predict(with_attention=True) of the test images to disk: one <index>.npz per image (triples, words, scores, first_rank,
-        first_sample, counts, n_distinct, attention) and index.json (image path or index -> npz file, n_distinct and the graph)."""
+        first_sample, counts, n_distinct, attention) and index.json (image path or index -> npz file, n_distinct and the graph).
+        decode="kbest": the arrays of that record (best_logp in place of first_rank), and index.json says "decode": "kbest"."""
+        kbestmod.check_decode(decode, descending)
         os.makedirs(out_dir, exist_ok=True)
         index = {}
+        extra = "best_logp" if decode == "kbest" else "first_rank"
         with self._eval_weights() as weights:
-            for i, r in enumerate(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention=True)):
+            for i, r in enumerate(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention=True,
+                                                     decode=decode)):
                 name = "%06d.npz" % i
                 np.savez(os.path.join(out_dir, name), triples=r["triples"], words=np.array(r["words"], dtype=str).reshape(-1, 3),
-                         scores=r["scores"], first_rank=r["first_rank"], first_sample=r["first_sample"], counts=r["counts"],
-                         n_distinct=np.int32(r["n_distinct"]), attention=r["attention"])
+                         scores=r["scores"], first_sample=r["first_sample"], counts=r["counts"],
+                         n_distinct=np.int32(r["n_distinct"]), attention=r["attention"], **{extra: r[extra]})
                 index[r["image"]] = {"file": name, "n_distinct": r["n_distinct"], "graph": r["graph"]}
         n_images = len(index)
         if weights == "ema":
             index["generator_weights"] = "ema"
+        if decode == "kbest":
+            index["decode"] = "kbest"
         with open(os.path.join(out_dir, "index.json"), "w") as f:
             json.dump(index, f, indent=1)
         if self.rank == 0:
@@ -843,7 +896,7 @@ class SceneGraphGAN(object):
         return [(k, k, real) for k, real in self.test_items[:max_images]]
 
     def evaluate(self, items=None, max_images=None, ks=(20, 50, 100), n_samples=None, descending=False, train_triples=None,
-                 return_details=False, out_path=None, logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
+                 return_details=False, out_path=None, logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES, decode="samples"):
         """R@K, mR@K and zsR@K of the model (sgg_amd.metrics.RecallAccumulator has the definitions): per image the ranked list of
         DISTINCT triples of predict() - same passes, same noise stream, same order - cut at max(ks), and the image's true triples
         matched against it on the device (K.match_triples).  Distinct predictions, denominators |GT|: not the protocol of test(),
@@ -861,13 +914,19 @@ class SceneGraphGAN(object):
         copy back (pos, n_gt, n_distinct).  Ranked triples, tokens and scores stay on the device.  Touches no weights and no
         optimiser state; usable on an untrained model, as test() and predict() are.
 
-        With an average of G's weights and eval_live off, G runs on the average and the result says "generator_weights": "ema"."""
+        With an average of G's weights and eval_live off, G runs on the average and the result says "generator_weights": "ema".
+
+        decode="kbest": the ranked list is that of predict(decode="kbest") - the K-best triples of n_samples head rows (default
+        TEST_BATCH_SIZE) merged by mixture log-probability, no critic pass - cut at min(max(ks), n_samples x list width); the
+        result says "decode": "kbest".  descending=True is rejected."""
+        kbestmod.check_decode(decode, descending)
         with self._eval_weights() as weights:
             return self._evaluate(items, max_images, ks, n_samples, descending, train_triples, return_details, out_path,
-                                  logits_budget_bytes, weights)
+                                  logits_budget_bytes, weights, decode)
 
     def _evaluate(self, items, max_images, ks, n_samples, descending, train_triples, return_details, out_path, logits_budget_bytes,
-                  weights):
+                  weights, decode="samples"):
+        kbest = decode == "kbest"
         ks = tuple(sorted(set(int(k) for k in ks)))
         if not ks or ks[0] < 1:
             raise ValueError("evaluate: ks must be positive integers (got %r)" % (ks,))
@@ -881,17 +940,18 @@ class SceneGraphGAN(object):
                     raise ValueError("evaluate: image %s: ground-truth triple %r is not three tokens in [0, %d)" % (key, list(t), V))
         if train_triples is None and self.dataset is not None:
             train_triples = set(map(tuple, np.concatenate([self.dataset["train"][1], self.dataset["val"][1]]).tolist()))
-        K, V, TB, N, _ = self._sampling_setup("evaluate", n_samples, None)
-        top_k = min(max(ks), N)
+        K, V, TB, N, slots = self._sampling_setup("evaluate", n_samples, None, decode)
+        top_k = min(max(ks), slots)
         acc = RecallAccumulator(ks, V)
         details, nd_all = [], []
         if items:
             nb = images_per_pass(N, V, TB, len(items), logits_budget_bytes)
             M = max(1, max(len(real) for _, _, real in items))
             ranked = {name: torch.empty(shape, dtype=dt, device=self.device) for name, shape, dt in
-                      [("triples", (nb, top_k, 3), torch.int64), ("scores", (nb, top_k), torch.float32),
-                       ("first_rank", (nb, top_k), torch.int32), ("first_sample", (nb, top_k), torch.int32),
-                       ("counts", (nb, top_k), torch.int32)]}
+                      [("triples", (nb, top_k, 3), torch.int64), ("scores", (nb, top_k), torch.float32)] +
+                      ([("best_sample", (nb, top_k), torch.int32), ("best_logp", (nb, top_k), torch.float32)] if kbest else
+                       [("first_rank", (nb, top_k), torch.int32), ("first_sample", (nb, top_k), torch.int32)]) +
+                      [("counts", (nb, top_k), torch.int32)]}
             packed, back, views = self._device_pack([("pos", np.int32, (nb, M)), ("n_gt", np.int32, (nb,)),
                                                      ("n_distinct", np.int32, (nb,))], self.device)
             ranked["n_distinct"] = back["n_distinct"]
@@ -899,7 +959,10 @@ class SceneGraphGAN(object):
             gt_host, _, gt_views = self._device_pack(gt_parts, "cpu")
             gt_h = gt_views(gt_host.numpy())                    # (numpy views of the host buffer: filled in place)
             gt_packed, gt_d, _ = self._device_pack(gt_parts, self.device)
-            for i0, n in self._ranked_batches(K, [(key, x) for key, x, _ in items], N, nb, top_k, descending, ranked):
+            plain = [(key, x) for key, x, _ in items]
+            batches = self._kbest_batches(K, plain, N, nb, top_k, ranked) if kbest else \
+                self._ranked_batches(K, plain, N, nb, top_k, descending, ranked)
+            for i0, n in batches:
                 gt_h["gt"][:] = 0
                 gt_h["gt_count"][:] = 0                  # (the padded images of the last batch: no ground truth)
                 for j in range(n):
@@ -917,7 +980,8 @@ class SceneGraphGAN(object):
                     if return_details:
                         details.append({"image": key, "pos": pos.tolist(), "n_gt": int(h["n_gt"][j]), "n_distinct": nd_all[-1]})
         res = acc.result(self.reverse_vocab)
-        res.update({"ks": list(ks), "samples_per_image": N, "ordering": "%s mean critic score" % ("descending" if descending else "ascending"),
+        res.update({"ks": list(ks), "samples_per_image": N,
+                    "ordering": kbestmod.ORDERING if kbest else "%s mean critic score" % ("descending" if descending else "ascending"),
                     "mean_n_distinct": float(np.mean(nd_all)) if nd_all else None,
                     "definition": "distinct predictions, denominators |GT|: R@K = mean over images of hits in the first K distinct "
                                   "triples / |GT|; mR@K = mean over predicates of the per-predicate mean over images; zsR@K = R@K on "
@@ -926,6 +990,8 @@ class SceneGraphGAN(object):
             res["details"] = details
         if weights == "ema":
             res["generator_weights"] = "ema"
+        if kbest:
+            res["decode"] = "kbest"
         if self.rank == 0 and out_path:
             with open(out_path, "w") as f:
                 json.dump(res, f, indent=1)
@@ -988,6 +1054,11 @@ def build_parser():
     parser.add_argument("--top_k", default=None, type=int, help="keep the first K distinct triples per image (default: all)")
     parser.add_argument("--predict_descending", action="store_true",
                         help="highest critic score first (default: ascending, the order of the evaluation)")
+    parser.add_argument("--decode", default="samples", choices=kbestmod.DECODES,
+                        help="how --predict_dir / --metrics_out draw an image's candidate triples: samples = the argmax triple of each "
+                             "noise sample, ranked by critic score (the default); kbest = the K most probable triples of each sample's "
+                             "three softmaxes, merged and ranked by the generator's log-probability, no critic pass (--predict_samples "
+                             "then defaults to the test batch size; not with --predict_descending)")
     parser.add_argument("--metrics_out", default=None,
                         help="load the checkpoint in --checkpoints_dir, write R@K, mR@K and zsR@K of the test images (distinct "
                              "predictions, denominators |GT|) as JSON to this file and exit; no training")
@@ -1023,8 +1094,19 @@ def build_parser():
     return parser
 
 
+def parse_args(argv=None):
+    """The command line, with the combinations no single option can reject."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    try:
+        kbestmod.check_decode(args.decode, args.predict_descending)
+    except ValueError as e:
+        parser.error(str(e))
+    return args
+
+
 if __name__ == "__main__":
-    args = build_parser().parse_args()
+    args = parse_args()
     params = vars(args)
 
     if "LOCAL_RANK" not in os.environ:
@@ -1051,14 +1133,15 @@ if __name__ == "__main__":
                   file=sys.stderr)
             sys.exit(2)
         gan.write_predictions(params["predict_dir"], max_images=params["max_test_images"], n_samples=params["predict_samples"],
-                              top_k=params["top_k"], descending=params["predict_descending"])
+                              top_k=params["top_k"], descending=params["predict_descending"], decode=params["decode"])
     elif params["metrics_out"]:
         if not gan.load_checkpoint():
             print("--metrics_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
                   file=sys.stderr)
             sys.exit(2)
         m = gan.evaluate(max_images=params["max_test_images"], ks=tuple(int(k) for k in params["metrics_k"].split(",") if k.strip()),
-                         n_samples=params["predict_samples"], descending=params["predict_descending"], out_path=params["metrics_out"])
+                         n_samples=params["predict_samples"], descending=params["predict_descending"], out_path=params["metrics_out"],
+                         decode=params["decode"])
         if gan.rank == 0:
             print({k: v for k, v in m.items() if k != "predicates" and k != "definition"})
     elif params["test_only"]:
