@@ -8,6 +8,8 @@ Same import path, constructor and method signatures as the reference (generator_
 Added (evaluation): Generator.sample(images, num_samples, noise=None) -> logits [N, B, 3, vocab] on one encoder pass.
 Added (input gradients): Generator.image_gradient(images, d_logits, noise=None) -> [B, S, S, 3], the vector-Jacobian product of
 build_generator with respect to the images (what tf.gradients(fake_inputs, images, d_logits) gives in the reference graph).
+Added (likelihood): Generator.log_prob(images, triples, counts, num_samples, noise=None) -> the log-probability of given triples
+under the mixture of num_samples noise draws (the product of the three softmaxes per draw).
 In the reference these methods add TensorFlow ops to a graph; here they run eagerly on the GPU: every arithmetic
 op is a hand-written HIP kernel behind the C ABI of libsgg_hip.so (include/sgg_hip.h).  Repeated builds share one
 set of weights, as `reuse=tf.AUTO_REUSE` does (train.py:86).  `is_training` is accepted and ignored, as in the
@@ -64,6 +66,21 @@ class Generator(NetworkHandle):
         net.head.forward(st, ctx, noise.contiguous().view(N * B, 512))
         self._publish(ctx, st)
         return st.OUT[0].view(N, B, 3, self.vocab_size)
+
+    def log_prob(self, images, triples, counts, num_samples, noise=None):
+        """The log-probability the generator assigns to given triples: images [B, S, S, 3] (standardised), triples int64 [B, M, 3],
+        counts int32 [B] (rows m >= counts[b] are padding), num_samples noise draws per image (`noise` [N, B, 512], torch.randn if
+        None).  Returns (mix [B, M], mean [B, M], slot [B, M, 3], status int32 [B, M]): the log-probability under the mixture of
+        the N draws, the mean over the draws of the per-draw log-probability, that mean per slot, and 0 / -3 (padding) / -4 (a
+        token outside the vocabulary; the floats of such rows are NaN).  sample(), then the log-sum-exp of every decoder row
+        (softmax_xent without labels), then triple_logp (csrc/xent.hip).  Touches no weights."""
+        logits = self.sample(images, num_samples, noise)
+        K = self._last.K
+        N, B = int(logits.shape[0]), int(logits.shape[1])
+        lse = torch.empty((N, B, 3), device=logits.device, dtype=logits.dtype)
+        K.softmax_xent(logits, None, lse=lse.view(-1))
+        res = K.triple_logp(logits, lse, triples.contiguous(), counts.contiguous())
+        return res["mix"], res["mean"], res["slot"], res["status"]
 
     def image_gradient(self, images, d_logits, noise=None):
         """d <d_logits, build_generator(images, noise)> / d images: images [B, S, S, 3] (standardised), d_logits [B, 3, vocab] ->

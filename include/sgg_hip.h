@@ -449,6 +449,35 @@ int sgg_kbest_merge(const long long* lists, const float* logits, long long ld, c
                     long long* triples, float* scores, int* best_sample, float* best_logp, int* counts, int* n_distinct,
                     void* stream);
 
+/* ---- generator likelihood: softmax cross-entropy and the log-probability of given triples (csrc/xent.hip) -------------------
+ * The likelihood K-best decoding ranks by (above), as a training objective and as a held-out measurement.  Finite logits are a
+ * precondition of all three entry points; none uses a workspace or a float atomic, and two calls give the same bits.
+ * sgg_softmax_xent: row-wise log-softmax cross-entropy, forward and gradient in one launch.
+ *   Row r is logits[r * ld .. r * ld + V), ld >= V, any 4-byte alignment.  lse[r] = max + log(sum_j exp(x_j - max)), fixed summation
+ *   order.  labels int64 [R].  For a label in [0, V): nll[r] = lse[r] - x[label]; hit[r] = 1 if label is the row's tf.argmax (the
+ *   first index of the maximum, as sgg_argmax_rows), else 0; dlogits[r][j] = scale * (exp(x_j - lse[r]) - [j == label]), rows ldd >= V
+ *   apart, stored (accumulate = 0) or added to what is there (accumulate = 1).  A label outside [0, V) SKIPS the row: nll = 0,
+ *   hit = -1, its dlogits row zero-filled (accumulate = 0) or untouched (accumulate = 1); lse is written all the same.
+ *   dlogits, nll, lse and hit may each be NULL (not all).  labels = NULL: the lse-only mode, dlogits = nll = hit = NULL.
+ *   R >= 1, 1 <= V <= 2^21; element offsets are 64-bit.  V <= 1024: one wave per row, the row in registers; above: one workgroup
+ *   per row, an online max / sum pass and a gradient pass that re-reads the row.
+ * sgg_xent_summary: the numbers of a log line from nll / hit of R = 3 B rows, three consecutive rows per triple; one workgroup.
+ *   Valid rows: hit >= 0.  out4 fp32 = { mean nll per valid row (nats per token; summed in fp64), share of valid rows with hit = 1,
+ *   share of the all-valid triples whose three rows all hit, number of valid rows }; a share over nothing is 0.
+ * sgg_triple_logp: the log-probability of given triples under the mixture of an image's N noise samples; one workgroup per image.
+ *   logits fp32 [N * nb][3][V], rows ld >= 3 V apart, sample k of image j is row k * nb + j; lse fp32 [N][nb][3] (sgg_softmax_xent's
+ *   lse-only mode on the R = N * nb * 3 slot rows, or sgg_kbest_triples').  gt int64 [nb][M][3], gt_count int32 [nb] as
+ *   sgg_match_triples takes them (gt_count clamped to [0, M] on the device).  For a valid row (s, p, o): a_t(x) = logits[t][x] - lse[t],
+ *   lp_k = (a_0(s) + a_1(p)) + a_2(o), m = max_k lp_k, mix = m + (log(sum_k exp(lp_k - m)) - log N), summed in sample order in fp32 -
+ *   the arithmetic of sgg_kbest_merge's score, bit for bit.  mean fp32 [nb][M] = mean_k lp_k; slot fp32 [nb][M][3] = mean_k a_t.
+ *   status int32 [nb][M]: 0 valid, -3 padding (m >= gt_count[j]), -4 a token outside [0, V); the float outputs of a row that is
+ *   not valid hold NaN.  Duplicated rows are each scored.  1 <= N <= 4096, 1 <= M <= 4096, nb >= 1, 1 <= V <= 2^21. */
+int sgg_softmax_xent(const float* logits, long long ld, int R, int V, const long long* labels, float scale, int accumulate,
+                     float* dlogits, long long ldd, float* nll, float* lse, int* hit, void* stream);
+int sgg_xent_summary(const float* nll, const int* hit, int R, float* out4, void* stream);
+int sgg_triple_logp(const float* logits, long long ld, const float* lse, int N, int nb, int V, const long long* gt,
+                    const int* gt_count, int M, float* mix, float* mean, float* slot, int* status, void* stream);
+
 /* ---- training diagnostics: per-tensor norms and non-finite counts of a network's arenas (csrc/stats.hip) ----------------------
  * One read-only streaming pass over params, grads, m and v: fp32 arenas of ONE layout, every tensor 16-byte aligned and rounded up
  * to 4 elements (the arena ends on such a boundary), as sgg_adam_tf_multi takes them.

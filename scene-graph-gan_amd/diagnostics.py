@@ -141,6 +141,8 @@ def raise_if_nonfinite(diag, itr=None):
     """NonFiniteError for the first network ("G", then "D") of a GanStep.diagnostics() record whose summary counts a non-finite
     gradient, parameter or update."""
     for net in ("G", "D"):
+        if net not in diag:                 # (the G-only record of the pretraining phase)
+            continue
         first = diag[net]["first_nonfinite"]
         if first is not None:
             raise NonFiniteError(net, first["tensor"], first["which"], itr)

@@ -91,6 +91,9 @@ SIGNATURES = {
     "sgg_match_triples": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "sgg_kbest_triples": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sgg_kbest_merge": (_i, [_vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgg_softmax_xent": (_i, [_vp, _ll, _i, _i, _vp, _f, _i, _vp, _ll, _vp, _vp, _vp, _vp]),
+    "sgg_xent_summary": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "sgg_triple_logp": (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sgg_arena_stats_chunk": (_i, []),
     "sgg_arena_stats_nstat": (_i, []),
     "sgg_arena_stats_workspace_bytes": (_sz, [_i]),
@@ -1099,6 +1102,71 @@ class HipKernels:
         self._check(self.lib.sgg_kbest_merge(_p(triples), _p(x), ld, _p(lse), N, nb, Kc, V, K, _p(res["triples"]), _p(res["scores"]),
                                              _p(res["best_sample"]), _p(res["best_logp"]), _p(res["counts"]), _p(res["n_distinct"]),
                                              self._stream()), "sgg_kbest_merge")
+        return res
+
+    # -- generator likelihood (csrc/xent.hip) ---------------------------------------------------------------
+    @staticmethod
+    def _xent_rows(t, what):
+        """[..., V] tensor whose rows are ONE fixed stride apart (a contiguous tensor, or a column slice of a wider 2-D buffer) ->
+        ([R, V] view, row stride)."""
+        assert t.dtype == torch.float32 and t.dim() >= 2, what
+        V = int(t.shape[-1])
+        x = t if t.dim() == 2 else t.view(-1, V)       # (raises where the rows are not one stride apart)
+        assert x.stride(1) == 1 or V == 1, "%s: the last dimension must be contiguous" % what
+        return x, int(_ld(x))
+
+    def softmax_xent(self, logits, labels=None, scale=1.0, accumulate=False, dlogits=None, nll=None, lse=None, hit=None):
+        """Row-wise log-softmax cross-entropy, forward and gradient in one launch (csrc/xent.hip; include/sgg_hip.h): logits fp32
+        [..., V] (R rows one stride apart), labels int64 with R elements.  Outputs, each optional: dlogits (shape of logits, its own
+        row stride) = scale * (softmax - onehot), stored or - accumulate - added; nll fp32 [R]; lse fp32 [R]; hit int32 [R] (1: the
+        label is the row's argmax, 0: not, -1: the label is outside [0, V) and the row was skipped).  labels=None: lse only."""
+        self._dev(logits, labels, dlogits, nll, lse, hit)
+        x, ld = self._xent_rows(logits, "logits")
+        R, V = int(x.shape[0]), int(x.shape[1])
+        ldd = 0
+        if dlogits is not None:
+            d, ldd = self._xent_rows(dlogits, "dlogits")
+            assert tuple(d.shape) == (R, V), "dlogits must have the logits' rows"
+        if labels is not None:
+            assert labels.dtype == torch.int64 and labels.numel() == R and labels.is_contiguous()
+        for t, dt in ((nll, torch.float32), (lse, torch.float32), (hit, torch.int32)):
+            assert t is None or (t.dtype == dt and t.numel() == R and t.is_contiguous())
+        nb = 4.0 * R * V * (1 + (0 if dlogits is None else (2 if accumulate else 1)))
+        self._check(self._timed("xent_rows_resident_kernel" if V <= 1024 else "xent_rows_stream_kernel", 0.0,
+                                lambda: self.lib.sgg_softmax_xent(_p(x), ld, R, V, _p(labels), float(scale), int(bool(accumulate)),
+                                                                  _p(dlogits), ldd, _p(nll), _p(lse), _p(hit), self._stream()), nb),
+                    "sgg_softmax_xent")
+
+    def xent_summary(self, nll, hit, out=None):
+        """out fp32 [4] = (mean nll per valid row, token accuracy, triple accuracy, valid rows) of softmax_xent's nll / hit over
+        R = 3 B rows, three consecutive rows per triple (include/sgg_hip.h); one workgroup, fixed order."""
+        self._dev(nll, hit, out)
+        R = nll.numel()
+        assert nll.dtype == torch.float32 and hit.dtype == torch.int32 and hit.numel() == R and nll.is_contiguous() and hit.is_contiguous()
+        if out is None:
+            out = torch.empty(4, dtype=torch.float32, device=nll.device)
+        assert out.dtype == torch.float32 and out.numel() == 4 and out.is_contiguous()
+        self._check(self.lib.sgg_xent_summary(_p(nll), _p(hit), R, _p(out), self._stream()), "sgg_xent_summary")
+        return out
+
+    def triple_logp(self, logits, lse, gt, gt_count, out=None):
+        """The log-probability of given triples under the mixture of an image's N samples (csrc/xent.hip): logits fp32
+        [N, nb, 3, V], lse fp32 [N, nb, 3], gt int64 [nb, M, 3], gt_count int32 [nb] -> dict of device tensors: mix [nb, M], mean
+        [nb, M], slot [nb, M, 3], status int32 [nb, M] (0 valid, -3 padding, -4 token outside [0, V); NaN in the floats of a row that
+        is not valid).  out: optional dict of preallocated contiguous tensors under those names."""
+        self._dev(logits, lse, gt, gt_count)
+        assert logits.dim() == 4 and logits.shape[2] == 3, "logits must be [N, nb, 3, V]"
+        N, nb = int(logits.shape[0]), int(logits.shape[1])
+        x, ld = self._logit_rows(logits)
+        V = int(x.shape[2])
+        assert lse.dtype == torch.float32 and lse.numel() == N * nb * 3 and lse.is_contiguous(), "lse must be contiguous [N, nb, 3]"
+        assert gt.dtype == torch.int64 and gt.dim() == 3 and gt.shape[0] == nb and gt.shape[2] == 3 and gt.is_contiguous()
+        M = int(gt.shape[1])
+        assert gt_count.dtype == torch.int32 and tuple(gt_count.shape) == (nb,) and gt_count.is_contiguous()
+        res = self._out_tensors({"mix": ((nb, M), torch.float32), "mean": ((nb, M), torch.float32), "slot": ((nb, M, 3), torch.float32),
+                                 "status": ((nb, M), torch.int32)}, out, logits.device)
+        self._check(self.lib.sgg_triple_logp(_p(x), ld, _p(lse), N, nb, V, _p(gt), _p(gt_count), M, _p(res["mix"]), _p(res["mean"]),
+                                             _p(res["slot"]), _p(res["status"]), self._stream()), "sgg_triple_logp")
         return res
 
     def fill(self, t, value):

@@ -365,7 +365,11 @@ class GanStep:
         # default because concurrent kernels make per-kernel durations (the roofline measurement) meaningless.
         self._g_reuse, self._g_reuse_armed = None, False       # (images, ctx) of G's encoder within one train_iteration
         self._g_reuse_slots = {}                 # accumulation: micro-batch k -> (images, copy of ctx, guard) (generator_forward)
-        self._loss_acc, self._loss_n = {}, {"d": 1, "g": 1}    # sums of the four loss numbers over the micro-batches of an update
+        self._loss_acc, self._loss_n = {}, {"d": 1, "g": 1, "m": 1}    # sums of the four loss numbers over the micro-batches of an update
+        # generator likelihood (pretrain_step, generator_step(mle_weight > 0), generator_nll): (nll per token, token accuracy, triple
+        # accuracy, valid rows) of the last cross-entropy; the per-row buffers behind it are allocated at the first use (_xent_rows)
+        self.mle_losses = z(4)
+        self._xent_buf = None
         # (option side_priority: priority of the side streams - everything on them is off the critical chain of the main stream)
         prio = int(option(K, "side_priority"))
         self.side = torch.cuda.Stream(device=dev, priority=prio) if (overlap_streams and dev.type == "cuda") else None
@@ -584,10 +588,20 @@ class GanStep:
         K.wgan_losses(st.OUT[0].view(3 * B, T_STEPS), self.pen, self.lam, B, T_STEPS, True, out)
         return out
 
-    def generator_step(self, images, noise, micro=None):
-        """One gen_train_op (train.py:368). Returns self.g_losses; g_losses[3] = mean D(fake) = -gen_cost.  micro: as critic_step."""
+    def generator_step(self, images, noise, micro=None, labels=None, mle_weight=0.0):
+        """One gen_train_op (train.py:368). Returns self.g_losses; g_losses[3] = mean D(fake) = -gen_cost.  micro: as critic_step.
+        mle_weight = w > 0 (with labels int64 [B,3]): the auxiliary likelihood term, gen_cost' = -mean D(G(x)) + w * xent with xent
+        the loss of pretrain_step - one softmax_xent launch that ADDS w / B * (softmax - onehot) to the critic's gradient of the fake
+        logits, and the summary into self.mle_losses.  w = 0 (default): nothing of it is launched."""
         K, B, G, D = self.K, self.B, self.G, self.D
         mk, mN = micro if micro is not None else (0, 1)
+        mle_weight = float(mle_weight)
+        if not (mle_weight >= 0.0 and math.isfinite(mle_weight)):
+            raise ValueError("mle_weight must be a finite number >= 0 (got %r)" % mle_weight)
+        if mle_weight > 0.0:
+            if labels is None:
+                raise ValueError("generator_step: mle_weight > 0 needs the labels of the minibatch")
+            self._need_xent("generator_step(mle_weight > 0)")
         if mN > 1:
             G._acc_flat()
         G.finish_update()
@@ -611,6 +625,9 @@ class GanStep:
         ind = D.head.in_dim
         for t in range(T_STEPS):
             K.gemm_nt(st.dXH[t][0][:, FEAT_C:ind], D.head.W_emb, gst.dOUT[0][:, t, :])
+        if mle_weight > 0.0:
+            self._xent(fake, labels, mle_weight / B, gst.dOUT[0], accumulate=True, out=self.mle_losses)
+            self._sum_losses("m", self.mle_losses, mk, mN)
         G.head.backward(gst, gctx, None, R_w=B)
         dctx = G.head.finish_backward(gctx)
         G.trunk.backward(dctx)
@@ -618,6 +635,69 @@ class GanStep:
         self._sum_losses("g", self.g_losses, mk, mN)
         G.end_micro_batch(mk, mN, self.reducer)
         return self.g_losses
+
+    # ---- generator likelihood (csrc/xent.hip) -------------------------------------------------------------
+    def _need_xent(self, what):
+        missing = [n for n in ("softmax_xent", "xent_summary") if not hasattr(self.K, n)]
+        if missing:
+            raise RuntimeError("%s needs the softmax_xent and xent_summary kernels; the %r kernel set lacks %s"
+                               % (what, getattr(self.K, "name", self.K), ", ".join(missing)))
+
+    def _xent(self, logits, labels, scale, dlogits, accumulate, out):
+        """softmax_xent of the B * 3 decoder rows `logits` [B,3,V] against labels int64 [B,3] (gradient into dlogits unless None),
+        then its summary into `out` (4 floats)."""
+        if self._xent_buf is None:
+            dev, R = self.mle_losses.device, self.B * T_STEPS
+            self._xent_buf = (torch.zeros(R, dtype=self.mle_losses.dtype, device=dev), torch.zeros(R, dtype=torch.int32, device=dev))
+        nll, hit = self._xent_buf
+        assert tuple(labels.shape) == (self.B, T_STEPS) and labels.dtype == torch.int64
+        self.K.softmax_xent(logits, labels.reshape(-1), scale=scale, accumulate=accumulate, dlogits=dlogits, nll=nll, hit=hit)
+        return self.K.xent_summary(nll, hit, out=out)
+
+    def pretrain_step(self, images, labels, noise, micro=None):
+        """One maximum-likelihood update of G: loss = (1/B) * sum_b sum_t -log softmax(logits[b,t])[labels[b,t]] - the likelihood
+        K-best decoding ranks by, as a supervised objective.  G's forward as in generator_step, the cross-entropy and its gradient
+        (scale 1/B) in one launch into the head's dOUT, then G's backward and end_micro_batch: accumulation (micro), the data-parallel
+        all-reduce, the guard, the weight average and the diagnostics apply as to any update of G; its Adam moments and step count
+        are those of the GAN phase.  D is never touched.  Returns self.mle_losses = (nll per token, token accuracy, triple accuracy,
+        valid rows) as a device tensor."""
+        B, G = self.B, self.G
+        if self._g_reuse_armed or self._g_reuse is not None:
+            raise RuntimeError("pretrain_step inside an iteration with G-encoder reuse: the step updates G, the kept encoder output "
+                               "would be stale")
+        self._need_xent("pretrain_step")
+        mk, mN = micro if micro is not None else (0, 1)
+        if mN > 1:
+            G._acc_flat()
+        # G's weights change here without a critic update in front: an early encoder forward (_g_early_stream) must not start from an
+        # event recorded before this step (its guard on (arena.version, adam_t) refuses it as well)
+        self._ev_g_free = self._ev_g_images = None
+        G.finish_update()
+        G.zero_grads()
+        gst, gctx = self.generator_forward(images, noise, micro=micro)
+        self._xent(gst.OUT[0], labels, 1.0 / B, gst.dOUT[0], accumulate=False, out=self.mle_losses)
+        G.head.backward(gst, gctx, None, R_w=B)
+        dctx = G.head.finish_backward(gctx)
+        G.trunk.backward(dctx)
+        G.head.join()
+        self._sum_losses("m", self.mle_losses, mk, mN)
+        G.end_micro_batch(mk, mN, self.reducer)
+        return self.mle_losses
+
+    def generator_nll(self, images, labels, noise, out=None):
+        """The four numbers of pretrain_step for a minibatch WITHOUT an update (the forward-only counterpart of critic_loss): the
+        held-out negative log-likelihood of the ground-truth tokens under G(images, noise).  Returns them in `out` (default: a buffer
+        of its own)."""
+        assert self._g_reuse is None and not self._g_reuse_armed, "generator_nll inside an iteration with G-encoder reuse"
+        self._need_xent("generator_nll")
+        if out is None:
+            if getattr(self, "val_nll", None) is None:
+                self.val_nll = torch.zeros_like(self.mle_losses)
+            out = self.val_nll
+        self.flush()
+        self._ev_g_free = self._ev_g_images = None      # (G's encoder buffers are rewritten on this stream)
+        gst, _ = self.generator_forward(images, noise, for_backward=False)
+        return self._xent(gst.OUT[0], labels, 1.0, None, accumulate=False, out=out)
 
     # ---- loss numbers of an update over N micro-batches --------------------------------------------------
     def _sum_losses(self, which, losses, k, N):
@@ -639,6 +719,8 @@ class GanStep:
     # micro-batches; without accumulation d_losses / g_losses themselves
     d_losses_mean = property(lambda self: self._losses_mean("d", self.d_losses))
     g_losses_mean = property(lambda self: self._losses_mean("g", self.g_losses))
+    # (nll per token, token accuracy, triple accuracy, valid rows) of the last cross-entropy of a training step, the same way
+    mle_losses_mean = property(lambda self: self._losses_mean("m", self.mle_losses))
 
     def flush(self):
         """Apply any deferred optimiser update (before reading weights / at the end of the timed region)."""
@@ -674,15 +756,26 @@ class GanStep:
         return {n: guardmod.report(host[i * guardmod.NREC:(i + 1) * guardmod.NREC], net.opt["guard"]["max_norm"],
                                    net.opt["guard"]["skip_nonfinite"]) for i, (n, net) in enumerate(nets)}
 
-    def diagnostics(self):
+    def diagnostics(self, generator_only=False):
         """The statistics of each network's LAST optimiser step while armed, and of the critic's per-row slopes
         ||d sum(D(x_hat)) / d x_hat|| that the last critic update's gradient penalty left on the device:
             {"G": summary, "D": summary,                            diagnostics.summarise
              "gp_slope": {min, mean, max, share_above_1, nonfinite},
              "tensors": {"G": {name: row}, "D": {name: row}}}       diagnostics.tensor_rows (short TF names)
         Applies any deferred optimiser step first (data parallel: the step just taken is the one reported; gradients are identical
-        across ranks after the all-reduce, so every rank sees the same network rows).  One device-to-host copy."""
+        across ranks after the all-reduce, so every rank sees the same network rows).  One device-to-host copy.
+        generator_only=True: the report of the pretraining phase, where only G takes optimiser steps - {"G": summary,
+        "tensors": {"G": ...}} (and "guard" with G's record where G is guarded); the critic is not read."""
         self.flush()
+        if generator_only:
+            gd = self.G.opt.get("diag")
+            if gd is None or gd["last"] is None:
+                raise RuntimeError("diagnostics(generator_only=True): no optimiser step of G has run while armed (arm_diagnostics first)")
+            host = gd["rows"].view(-1).cpu().numpy()
+            out = {"G": diagnostics.summarise(host, gd["names"], gd["numels"]), "tensors": {"G": diagnostics.tensor_rows(host, gd["names"])}}
+            if self.G.has_guard:
+                out["guard"] = {"G": self.G.guard_report()}
+            return out
         gd, dd = self.G.opt.get("diag"), self.D.opt.get("diag")
         if gd is None or dd is None or gd["last"] is None or dd["last"] is None:
             raise RuntimeError("diagnostics(): no optimiser step of both networks has run while armed (arm_diagnostics first)")
@@ -703,15 +796,17 @@ class GanStep:
             out["guard"] = self.guard_reports()
         return out
 
-    def train_iteration(self, images, labels, noises, alphas, critic_iters=1, reuse_g_encoder=False):
+    def train_iteration(self, images, labels, noises, alphas, critic_iters=1, reuse_g_encoder=False, mle_weight=0.0):
         """Loop body of train.py:362-368: critic_iters critic updates then one generator update on one minibatch,
-        fresh noise / alpha per update.  reuse_g_encoder: G's encoder forward once per iteration (generator_forward)."""
+        fresh noise / alpha per update.  reuse_g_encoder: G's encoder forward once per iteration (generator_forward).
+        mle_weight > 0: the generator update carries the auxiliary likelihood term on `labels` (generator_step)."""
+        mle = {"labels": labels, "mle_weight": mle_weight} if mle_weight > 0.0 else {}
         with self.iteration(reuse_g_encoder):
             for i in range(critic_iters):
                 self.critic_step(images, labels, noises[i], alphas[i])
-            self.generator_step(images, noises[critic_iters])
+            self.generator_step(images, noises[critic_iters], **mle)
 
-    def train_iteration_accumulated(self, batches, noises, alphas, critic_iters=1, reuse_g_encoder=False):
+    def train_iteration_accumulated(self, batches, noises, alphas, critic_iters=1, reuse_g_encoder=False, mle_weight=0.0):
         """train_iteration with every update taken from N = len(batches) micro-batches of B rows: the update of the N * B rows.
         batches: [(images, labels)] * N, all resident on the device for the whole iteration (every update reads all of them);
         noises[i][k] / alphas[i][k]: update i (critic updates first, the generator update last), micro-batch k.  Order: per critic
@@ -720,13 +815,14 @@ class GanStep:
         N = len(batches)
         if N == 1:
             return self.train_iteration(batches[0][0], batches[0][1], [n[0] for n in noises], [a[0] for a in alphas],
-                                        critic_iters, reuse_g_encoder)
+                                        critic_iters, reuse_g_encoder, mle_weight)
         with self.iteration(reuse_g_encoder):
             for i in range(critic_iters):
                 for k, (images, labels) in enumerate(batches):
                     self.critic_step(images, labels, noises[i][k], alphas[i][k], micro=(k, N))
-            for k, (images, _) in enumerate(batches):
-                self.generator_step(images, noises[critic_iters][k], micro=(k, N))
+            for k, (images, labels) in enumerate(batches):
+                mle = {"labels": labels, "mle_weight": mle_weight} if mle_weight > 0.0 else {}
+                self.generator_step(images, noises[critic_iters][k], micro=(k, N), **mle)
 
     @contextlib.contextmanager
     def iteration(self, reuse_g_encoder=False):

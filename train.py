@@ -7,6 +7,8 @@
     python train.py --ema_decay 0.999 ...                                  # keep an average of G's weights; evaluation then uses it
     python train.py --batch_size 64 --accumulate 8 ...                     # every update from 8 micro-batches: the batch-512 update
     python train.py --clip_grad_norm 5,50 --skip_nonfinite ...             # clip D / G updates by global norm, drop non-finite ones
+    python train.py --pretrain_iterations 2000 --mle_weight 0.1 --validate_nll ...  # maximum-likelihood warm start of G, held-out NLL
+    python train.py --checkpoints_dir ckpt --likelihood_out nll.json       # NLL of the test split's true triples under G
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -76,7 +78,8 @@ class SceneGraphGAN(object):
     def __init__(self, checkpoints_dir, summaries_dir, path_to_ims_to_triples, path_to_vocab, path_to_word_embeddings,
                  path_to_image_means, path_to_image_stds, critic_iters, batch_size, lambda_, resume,
                  synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True,
-                 ema_decay=0.0, eval_live=False, accumulate=1, clip_grad_norm=0.0, skip_nonfinite=False):
+                 ema_decay=0.0, eval_live=False, accumulate=1, clip_grad_norm=0.0, skip_nonfinite=False,
+                 pretrain_iterations=0, mle_weight=0.0, validate_nll=False):
         # Hyperparameters (train.py:26-32)
         self.CRITIC_ITERS = int(critic_iters)
         self.BATCH_SIZE = int(batch_size)
@@ -113,6 +116,17 @@ class SceneGraphGAN(object):
             raise ValueError("clip_grad_norm takes one number or (critic's, generator's) (got %r)" % (clip_grad_norm,))
         self.skip_nonfinite = bool(skip_nonfinite)
         self.guarded = self.skip_nonfinite or any(x > 0.0 for x in self.clip_norms)
+        # pretrain_iterations = P > 0: iterations itr < P of the run are maximum-likelihood updates of G on the minibatch's true triples
+        # (GanStep.pretrain_step, no critic update); the phase is a function of itr and P, so --resume needs no counter of its own.
+        # mle_weight = w > 0: the same cross-entropy as an auxiliary term of the generator's cost in the GAN phase.  validate_nll:
+        # validation also logs the held-out negative log-likelihood (GanStep.generator_nll).  All off by default: nothing is launched.
+        self.PRETRAIN = int(pretrain_iterations or 0)
+        if self.PRETRAIN < 0:
+            raise ValueError("pretrain_iterations must be >= 0 (got %r)" % (pretrain_iterations,))
+        self.mle_weight = float(mle_weight or 0.0)
+        if not (0.0 <= self.mle_weight < float("inf")):
+            raise ValueError("mle_weight must be a finite number >= 0 (got %r)" % (mle_weight,))
+        self.validate_nll = bool(validate_nll)
         self.shuffle_buffer = bool(shuffle_buffer)      # tf.data shuffle(buffer_size = 10 * batch) on the repeated stream (train.py:176-179)
         self.checkpoints_dir, self.summaries_dir = checkpoints_dir, summaries_dir
         self.rank, self.world, local = dpmod.init_from_env()
@@ -248,16 +262,34 @@ class SceneGraphGAN(object):
         VB = self._val_rows()
         noise = torch.randn((VB, 512), generator=gen).to(self.device)
         alpha = torch.rand((VB,), generator=gen).to(self.device)
-        if self.val_step is None:
-            # the same variables at the validation batch size (train.py:199-203 feeds the validation iterator through the same graph)
-            self.val_step = GanStep(kernels_for(self.device), len(self.vocab), self.image_size, VB, lam=self.LAMBDA,
-                                    G=self.g._ensure(images), D=self.d._ensure(images))
+        self._ensure_val_step(images)
         self.step.flush()           # (a deferred optimiser step of the training networks changes the weights validation reads)
         loss = self.val_step.critic_loss(images, labels, noise, alpha)[0:1].clone()
         if self.world > 1:
             torch.distributed.all_reduce(loss)
             loss /= self.world
         return float(loss.item())
+
+    def _ensure_val_step(self, images):
+        if self.val_step is None:
+            # the same variables at the validation batch size (train.py:199-203 feeds the validation iterator through the same graph)
+            self.val_step = GanStep(kernels_for(self.device), len(self.vocab), self.image_size, self._val_rows(), lam=self.LAMBDA,
+                                    G=self.g._ensure(images), D=self.d._ensure(images))
+
+    def validation_nll(self, k, gen):
+        """The held-out negative log-likelihood of validation batch k's true tokens under the generator (GanStep.generator_nll, no
+        update): {"val_nll_token" (nats per token), "val_token_acc", "val_triple_acc"}, averaged over the data-parallel ranks as
+        validation_loss is.  `gen` is a noise generator of its own, so that validation_loss draws what it draws without this."""
+        images, labels = self._val_batch(k)
+        noise = torch.randn((self._val_rows(), 512), generator=gen).to(self.device)
+        self._ensure_val_step(images)
+        self.step.flush()
+        out = self.val_step.generator_nll(images, labels, noise)[0:3].clone()
+        if self.world > 1:
+            torch.distributed.all_reduce(out)
+            out /= self.world
+        v = out.cpu().tolist()
+        return {"val_nll_token": v[0], "val_token_acc": v[1], "val_triple_acc": v[2]}
 
     def _prefetcher(self, start, stop, workers=16):
         """tf.contrib.data.map_and_batch + prefetch (train.py:181-187) as decode threads + a pinned double buffer whose
@@ -284,15 +316,18 @@ class SceneGraphGAN(object):
                           "history": list(getattr(self, "val_history", []))}}
             if self.ACCUMULATE > 1:         # (only a run that accumulates writes the key)
                 ck["accumulate"] = self.ACCUMULATE
+            if self.PRETRAIN > 0:           # (only a run with a pretraining phase writes the key)
+                ck["pretrain_iterations"] = self.PRETRAIN
             if self.step.D.has_guard or self.step.G.has_guard:      # (only a guarded run writes the key: the clipped / skipped counts)
                 ck["guard"] = {n: net.guard_state() for n, net in (("D", self.step.D), ("G", self.step.G)) if net.has_guard}
             if self.step.G.has_average:     # (only a run that averages writes these keys: without it the checkpoint is what it was)
                 ck["G_ema"] = self.step.G.average_state()
-                # ... and where its noise stream stands, so that a resumed run continues the stream and its average is the one of
-                # the uninterrupted run (single process: every rank draws from a stream of its own, rank 0 writes)
-                gen = getattr(self, "_noise_gen", None)
-                if gen is not None and self.world == 1:
-                    ck["noise_rng"] = gen.get_state()
+            # ... and where the noise stream stands, so that a resumed run continues the stream: its average is the one of the
+            # uninterrupted run, and a run with a pretraining phase, stopped and resumed, ends on the same weights (single process
+            # only: every rank draws from a stream of its own, rank 0 writes)
+            gen = getattr(self, "_noise_gen", None)
+            if (self.step.G.has_average or self.PRETRAIN > 0) and gen is not None and self.world == 1:
+                ck["noise_rng"] = gen.get_state()
             torch.save(ck, self._ckpt_path())
 
     def _loadModel(self, for_training=False):
@@ -326,8 +361,11 @@ class SceneGraphGAN(object):
         if for_training and int(ck.get("accumulate", 1)) != self.ACCUMULATE and self.rank == 0:
             print("resuming with --accumulate %d a run saved with %d: the data stream continues at micro-batch itr * %d = %d"
                   % (self.ACCUMULATE, int(ck.get("accumulate", 1)), self.ACCUMULATE, self.itr * self.ACCUMULATE))
+        if for_training and int(ck.get("pretrain_iterations", 0)) != self.PRETRAIN and self.rank == 0:
+            print("resuming with --pretrain_iterations %d a run saved with %d: iterations below %d are pretraining iterations from "
+                  "here on (the run stands at iteration %d)" % (self.PRETRAIN, int(ck.get("pretrain_iterations", 0)), self.PRETRAIN, self.itr))
         self._resumed_val = ck.get("val")
-        self._resumed_rng = ck.get("noise_rng") if (for_training and self.ema_decay > 0.0 and self.world == 1) else None
+        self._resumed_rng = ck.get("noise_rng") if (for_training and (self.ema_decay > 0.0 or self.PRETRAIN > 0) and self.world == 1) else None
 
     @property
     def evaluates_average(self):
@@ -380,7 +418,8 @@ class SceneGraphGAN(object):
                 noises[i].append(torch.randn((B, 512), generator=gen).to(self.device))
                 if i < C:
                     alphas[i].append(torch.rand((B,), generator=gen).to(self.device))
-        self.step.train_iteration_accumulated(batches, noises, alphas[:C], critic_iters=C, reuse_g_encoder=self.reuse_g_encoder)
+        mle = {"mle_weight": self.mle_weight} if self.mle_weight > 0.0 else {}
+        self.step.train_iteration_accumulated(batches, noises, alphas[:C], critic_iters=C, reuse_g_encoder=self.reuse_g_encoder, **mle)
 
     def load_checkpoint(self):
         """Build both networks and load the checkpoint in checkpoints_dir (weights, Adam state, iteration) as --resume does;
@@ -420,6 +459,7 @@ class SceneGraphGAN(object):
             gen.set_state(self._resumed_rng)
             self._resumed_rng = None
         vgen = torch.Generator().manual_seed(self.seed + 70007 + self.rank)
+        ngen = None                 # noise of the held-out likelihood (validation_nll): seed + 90009 + rank, made at its first use
         log = open(os.path.join(self.summaries_dir, "losses.jsonl"), "a") if self.rank == 0 else None
         B, t0, itr0, N = self.BATCH_SIZE, time.time(), self.itr, self.ACCUMULATE
         loader = self._prefetcher(self.itr * N, n_it * N) if self.dataset is not None else None
@@ -442,7 +482,12 @@ class SceneGraphGAN(object):
                     self.step.arm_diagnostics(report)
                 # every update of an iteration sees the same minibatch (train.py:175-190) and G's weights change only at its end: G's
                 # encoder runs once per iteration (exact; 10 of 11 encoder forwards of G saved at CRITIC_ITERS = 10)
-                if N > 1:
+                pre = self.itr < self.PRETRAIN          # a pretraining iteration: one maximum-likelihood update of G, no critic update
+                if pre:
+                    for k, (im, lb) in enumerate(batches if N > 1 else [(images, labels)]):
+                        noise = torch.randn((B, 512), generator=gen).to(self.device)    # one fresh draw per micro-batch
+                        self.step.pretrain_step(im, lb, noise, micro=(k, N) if N > 1 else None)
+                elif N > 1:
                     self._accumulated_iteration(batches, gen)
                 else:
                     with self.step.iteration(reuse_g_encoder=self.reuse_g_encoder):
@@ -451,17 +496,29 @@ class SceneGraphGAN(object):
                             alpha = torch.rand((B,), generator=gen).to(self.device)
                             self.step.critic_step(images, labels, noise, alpha)
                         noise = torch.randn((B, 512), generator=gen).to(self.device)
-                        self.step.generator_step(images, noise)                         # train.py:368
+                        if self.mle_weight > 0.0:
+                            self.step.generator_step(images, noise, labels=labels, mle_weight=self.mle_weight)
+                        else:
+                            self.step.generator_step(images, noise)                     # train.py:368
                 itr = self.itr                                                          # the reference's 0-based loop variable
                 self.itr += 1
-                diag = self.step.diagnostics() if report else None
+                diag = self.step.diagnostics(generator_only=pre) if report else None
                 tensors = diag.pop("tensors") if diag is not None else None
-                if diag is not None and N > 1:
+                if diag is not None and N > 1 and not pre:
                     diag["gp_slope_rows"] = B       # the slopes are those of the last micro-batch of the last critic update
                 if log is not None and self.itr % log_every == 0:
-                    d, g = self.step.d_losses_mean.cpu().tolist(), self.step.g_losses_mean.cpu().tolist()   # (N = 1: d_losses / g_losses)
                     rate = B * N * self.world * (self.itr - itr0) / (time.time() - t0)  # of this run (a resumed run starts at itr0 > 0)
-                    rec = {"itr": self.itr, "disc_loss": d[0], "gen_loss": -g[3], "gp": d[2], "triples_per_s": rate}
+                    if pre or self.mle_weight > 0.0:
+                        m = self.step.mle_losses_mean.cpu().tolist()
+                        mle = {"mle_nll_token": m[0], "mle_nll_triple": 3.0 * m[0], "mle_token_acc": m[1], "mle_triple_acc": m[2]}
+                    if pre:
+                        rec = dict({"itr": self.itr, "phase": "pretrain"}, **mle)
+                        rec["triples_per_s"] = rate
+                    else:
+                        d, g = self.step.d_losses_mean.cpu().tolist(), self.step.g_losses_mean.cpu().tolist()   # (N = 1: d_losses / g_losses)
+                        rec = {"itr": self.itr, "disc_loss": d[0], "gen_loss": -g[3], "gp": d[2], "triples_per_s": rate}
+                        if self.mle_weight > 0.0:
+                            rec.update(mle)
                     if N > 1:
                         rec["accumulate"] = N
                     if self.guarded:        # the records of each network's last update and the clipped / skipped counts so far
@@ -480,7 +537,21 @@ class SceneGraphGAN(object):
                     raise_if_nonfinite(diag, self.itr)
                 if save_every and self.itr % save_every == 0:
                     self._saveModel()
-                if validate_every and itr % validate_every == 0:                        # train.py:375-384
+                if validate_every and itr % validate_every == 0 and pre:
+                    # pretraining phase: the held-out likelihood only - the critic is untrained, its cost says nothing yet, and the
+                    # early stop's counters and validation iterator wait for the GAN phase (batch: the validation's ordinal)
+                    if ngen is None:
+                        ngen = torch.Generator().manual_seed(self.seed + 90009 + self.rank)
+                    nll = self.validation_nll(itr // validate_every, ngen)
+                    if log is not None:
+                        log.write(json.dumps(dict({"itr": self.itr}, **nll)) + "\n"); log.flush()
+                elif validate_every and itr % validate_every == 0:                      # train.py:375-384
+                    if self.validate_nll:       # on the batch validation_loss is about to read, noise from a generator of its own
+                        if ngen is None:
+                            ngen = torch.Generator().manual_seed(self.seed + 90009 + self.rank)
+                        nll = self.validation_nll(len(self.val_history), ngen)
+                        if log is not None:
+                            log.write(json.dumps(dict({"itr": self.itr}, **nll)) + "\n"); log.flush()
                     loss = self.validation_loss(len(self.val_history), vgen)
                     self.val_history.append((itr, loss))
                     if log is not None:
@@ -998,6 +1069,77 @@ class SceneGraphGAN(object):
         return res
 
 
+    ############################################################
+    ## Likelihood: held-out NLL of the true triples under the generator's softmaxes (csrc/xent.hip)
+    ############################################################
+    def likelihood(self, items=None, max_images=None, n_samples=None, out_path=None, logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
+        """The negative log-likelihood the generator assigns to the true triples of the test images - threshold-free, and comparable
+        between checkpoints and between live and averaged weights.  Given a noise draw the three decoder softmaxes are independent
+        (sgg_amd/kbest.py), so a triple's probability under the image's n_samples draws (default TEST_BATCH_MULTIPLIER x
+        TEST_BATCH_SIZE) is the mixture of per-draw products.  Per batch of _sample_batches (the passes and the noise stream of
+        predict() / evaluate()): the log-sum-exp of every decoder row (K.softmax_xent without labels), then K.triple_logp on the
+        padded ground truth in the form evaluate() builds; one copy back per batch, sums in fp64 on the host.
+
+        items: as evaluate().  Returns (rank 0 writes it as JSON to out_path): nll_mixture {"micro": mean over all valid true triples
+        of -log p_mixture, "macro": mean over images of the image's mean}, nll_single (the same two means of the per-draw
+        log-probability averaged over the draws: what one noise vector gives, >= nll_mixture by Jensen), nll_slot (its three slots:
+        subject, predicate, object; micro), perplexity_token = exp(nll_single micro / 3), n_images, n_triples (valid ones),
+        n_out_of_vocab (true triples with a token outside the vocabulary: counted, not scored), n_samples, generator_weights."""
+        with self._eval_weights() as weights:
+            items = self._evaluate_items(items, max_images)
+            for key, _, real in items:
+                if len(real) > MAX_GT:
+                    raise ValueError("likelihood: image %s has %d ground-truth triples (at most %d per image)" % (key, len(real), MAX_GT))
+            K, V, TB, N, _ = self._sampling_setup("likelihood", n_samples, None)
+            tot = np.zeros(5, dtype=np.float64)             # sums over valid triples of -mix, -mean, -slot[0..2]
+            per_image, n_valid, n_oov = [], 0, 0
+            if items:
+                nb = images_per_pass(N, V, TB, len(items), logits_budget_bytes)
+                M = max(1, max(len(real) for _, _, real in items))
+                packed, out, views = self._device_pack([("mix", np.float32, (nb, M)), ("mean", np.float32, (nb, M)),
+                                                        ("slot", np.float32, (nb, M, 3)), ("status", np.int32, (nb, M))], self.device)
+                gt_parts = [("gt", np.int64, (nb, M, 3)), ("gt_count", np.int32, (nb,))]
+                gt_host, _, gt_views = self._device_pack(gt_parts, "cpu")
+                gt_h = gt_views(gt_host.numpy())
+                gt_packed, gt_d, _ = self._device_pack(gt_parts, self.device)
+                lse = torch.empty((N, nb, 3), dtype=torch.float32, device=self.device)
+                with contextlib.closing(self._sample_batches([(key, x) for key, x, _ in items], N, nb)) as batches:
+                    for i0, n, images, logits in batches:
+                        gt_h["gt"][:] = 0
+                        gt_h["gt_count"][:] = 0             # (the padded images of the last batch: no ground truth)
+                        for j in range(n):
+                            real = items[i0 + j][2]
+                            gt_h["gt"][j, :len(real)] = np.asarray(real, dtype=np.int64).reshape(-1, 3)
+                            gt_h["gt_count"][j] = len(real)
+                        gt_packed.copy_(gt_host)
+                        K.softmax_xent(logits, None, lse=lse.view(-1))
+                        K.triple_logp(logits, lse, gt_d["gt"], gt_d["gt_count"], out=out)
+                        h = views(packed.cpu().numpy())
+                        for j in range(n):
+                            ok = h["status"][j] == 0
+                            n_oov += int((h["status"][j] == -4).sum())
+                            if not ok.any():
+                                continue
+                            row = np.concatenate([-h["mix"][j][ok].astype(np.float64)[:, None], -h["mean"][j][ok].astype(np.float64)[:, None],
+                                                  -h["slot"][j][ok].astype(np.float64)], axis=1)
+                            tot += row.sum(axis=0)
+                            n_valid += int(ok.sum())
+                            per_image.append(row[:, :2].mean(axis=0))
+            micro = tot / n_valid if n_valid else np.full(5, np.nan)
+            macro = np.mean(per_image, axis=0) if per_image else np.full(2, np.nan)
+            num = lambda x: float(x) if np.isfinite(x) else None
+            res = {"nll_mixture": {"micro": num(micro[0]), "macro": num(macro[0])},
+                   "nll_single": {"micro": num(micro[1]), "macro": num(macro[1])},
+                   "nll_slot": [num(x) for x in micro[2:5]],
+                   "perplexity_token": num(np.exp(micro[1] / 3.0)) if n_valid else None,
+                   "n_images": len(items), "n_triples": n_valid, "n_out_of_vocab": n_oov, "n_samples": N,
+                   "generator_weights": weights}
+            if self.rank == 0 and out_path:
+                with open(out_path, "w") as f:
+                    json.dump(res, f, indent=1)
+            return res
+
+
 def _str2bool(v):
     """--resume of the reference is `type=bool` (train.py:410), which makes every non-empty string - "False" included - true."""
     if isinstance(v, bool):
@@ -1088,6 +1230,24 @@ def build_parser():
                         help="drop an update whose gradient holds an Inf or NaN: parameters, Adam moments and the weight average keep "
                              "every bit (decided on the device; the step count still advances); the counts of clipped and skipped "
                              "updates are logged under \"guard\" in losses.jsonl and saved in the checkpoint")
+    parser.add_argument("--pretrain_iterations", default=0, type=int,
+                        help="P >= 0: the first P iterations of the run (itr < P; --max_iterations is the total) are maximum-likelihood "
+                             "updates of the generator on the minibatch's true triples - softmax cross-entropy over its three decoder "
+                             "outputs, one fresh noise draw per (micro-)batch, no critic update; its Adam state carries over into the "
+                             "GAN phase; the checkpoint then also holds \"pretrain_iterations\" and, in a single-process run, the "
+                             "noise generator's state (\"noise_rng\"), so that a stopped and resumed run ends on the same weights - "
+                             "with several ranks a resumed run restarts its noise streams (default 0: off)")
+    parser.add_argument("--mle_weight", default=0.0, type=float,
+                        help="W >= 0: add W x the same cross-entropy to the generator's cost in the GAN phase; losses.jsonl then also "
+                             "carries mle_nll_token / mle_nll_triple / mle_token_acc / mle_triple_acc (default 0: off, nothing is launched)")
+    parser.add_argument("--validate_nll", action="store_true",
+                        help="whenever validation runs, also log the held-out negative log-likelihood of the validation batch's true "
+                             "tokens under the generator (val_nll_token, val_token_acc, val_triple_acc); its noise comes from a "
+                             "generator of its own, so val_disc_loss keeps its bits")
+    parser.add_argument("--likelihood_out", default=None,
+                        help="load the checkpoint in --checkpoints_dir, write the negative log-likelihood of the test images' true "
+                             "triples under the generator (mixture over --predict_samples noise draws, per draw, per slot; token "
+                             "perplexity) as JSON to this file and exit; no training")
     parser.add_argument("--log_every", default=10, type=int, help="iterations between the loss records of losses.jsonl (default 10)")
     parser.add_argument("--eval_live", action="store_true",
                         help="evaluate the generator's live weights even where an average exists (from --ema_decay or the checkpoint)")
@@ -1102,6 +1262,10 @@ def parse_args(argv=None):
         kbestmod.check_decode(args.decode, args.predict_descending)
     except ValueError as e:
         parser.error(str(e))
+    if args.pretrain_iterations < 0:
+        parser.error("--pretrain_iterations must be >= 0")
+    if not (0.0 <= args.mle_weight < float("inf")):
+        parser.error("--mle_weight must be a finite number >= 0")
     return args
 
 
@@ -1120,8 +1284,18 @@ if __name__ == "__main__":
                         resume=params["resume"], synthetic=synthetic, two_streams=not params["single_stream"],
                         reuse_g_encoder=not params["recompute_generator_encoder"], shuffle_buffer=not params["no_shuffle_buffer"],
                         ema_decay=params["ema_decay"], eval_live=params["eval_live"], accumulate=params["accumulate"],
-                        clip_grad_norm=params["clip_grad_norm"], skip_nonfinite=params["skip_nonfinite"])
-    if params["saliency_dir"]:
+                        clip_grad_norm=params["clip_grad_norm"], skip_nonfinite=params["skip_nonfinite"],
+                        pretrain_iterations=params["pretrain_iterations"], mle_weight=params["mle_weight"],
+                        validate_nll=params["validate_nll"])
+    if params["likelihood_out"]:
+        if not gan.load_checkpoint():
+            print("--likelihood_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
+                  file=sys.stderr)
+            sys.exit(2)
+        res = gan.likelihood(max_images=params["max_test_images"], n_samples=params["predict_samples"], out_path=params["likelihood_out"])
+        if gan.rank == 0:
+            print(res)
+    elif params["saliency_dir"]:
         if not gan.load_checkpoint():
             print("--saliency_dir: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
                   file=sys.stderr)
