@@ -329,7 +329,7 @@ int sgg_resize_bilinear_tf1(const unsigned char* src, const long long* offsets, 
 int sgg_adam_tf_multi(float* params, const float* grads, float* m, float* v, long long n, float lr_t, float beta1,
                       float beta2, float eps, float grad_scale, void* stream);
 
-/* ---- tf.train.ExponentialMovingAverage of the trained variables (csrc/ema.hip) --------------------------------------------
+/* ---- tf.train.ExponentialMovingAverage of the trained variables (csrc/optim.hip) ------------------------------------------
  * The reference never averages its weights; its framework ships the op, and evaluating a WGAN-GP generator on the average of its
  * iterates is the usual remedy for the noise of the last one.
  * sgg_adam_tf_multi_ema: sgg_adam_tf_multi and, in the same pass, the shadow update of the average on the new parameter value:
@@ -343,14 +343,14 @@ int sgg_adam_tf_multi_ema(float* params, const float* grads, float* m, float* v,
                           float beta2, float eps, float grad_scale, float one_minus_decay, void* stream);
 int sgg_swap_f32(float* a, float* b, long long n, void* stream);
 
-/* ---- gradient accumulation over micro-batches (csrc/ema.hip) -----------------------------------------------------------------
+/* ---- gradient accumulation over micro-batches (csrc/optim.hip) ---------------------------------------------------------------
  * The reference takes every update from one minibatch; every loss term is a mean over rows and no op couples samples, so the mean
  * of the gradients of N equal micro-batches is the gradient of their union (sgg_amd/step.py: Network.end_micro_batch).
  * acc[i] = g[i] (first != 0; a bit copy) or acc[i] = acc[i] + g[i] (one fp32 addition per element; no atomics: the result is a pure
  * function of the inputs).  Both 16-byte aligned, n > 0, the ranges must not overlap (argument error, nothing is launched). */
 int sgg_grad_accumulate(float* acc, const float* g, long long n, int first, void* stream);
 
-/* ---- guarded updates: global-norm clipping and the non-finite skip, decided on the device (csrc/guard.hip) ---------------------
+/* ---- guarded updates: global-norm clipping and the non-finite skip, decided on the device (csrc/guard.hip, csrc/optim.hip) -----
  * The reference clips nothing and checks nothing; a trainer of its kind is expected to bound an outlier update by the gradient's
  * global norm and to drop an update whose gradient is not finite.  Both decisions need a reduction over the whole gradient arena;
  * it is taken on the device and consumed by the Adam pass from device memory - no host read-back.

@@ -2,16 +2,15 @@
 // loads, wave shuffles for the fp64 sums, no atomics, no LDS beyond the cross-wave hand-over.
 //   grad_guard_chunk_kernel   workgroups walk the flat gradient range grid-stride in chunks of sgg_arena_stats_chunk() elements.  Per
 //                             element x = g * grad_scale (fp32, as adam_kernel forms it): a finite x adds (double)x * (double)x to the
-//                             chunk's sum of squares, a non-finite one is only counted (the test of stats_finite, csrc/stats.hip).
+//                             chunk's sum of squares, a non-finite one is only counted (sgg_finite, as csrc/stats.hip tests it).
 //                             Each chunk's row (ss, count) goes to the workspace with plain stores.
 //   grad_guard_final_kernel   ONE workgroup: thread t sums rows t, t + 256, ... in that order, a fixed shuffle tree, the four waves in
 //                             order; thread 0 then forms the record of eight doubles (include/sgg_hip.h) and read-modify-writes its
 //                             two cumulative counters.
 //                             A chunk's row depends on its elements only, the record on the rows in a fixed order: bit-identical from
 //                             call to call and for every grid.
-//   adam_guarded_kernel       adam_kernel (csrc/misc.hip) and adam_ema_kernel (csrc/ema.hip), expression for expression, with the
-//   adam_ema_guarded_kernel   gradient scale read from the record ((float)record[4]) instead of a kernel argument; record[5] == 0
-//                             (the update is dropped): the kernel returns before its first load, nothing is written.
+// The record's readers are adam_guarded_kernel and adam_ema_guarded_kernel (csrc/optim.hip): (float)record[4] is their gradient
+// scale, record[5] == 0 drops the update.
 // coef is EXACTLY 1 while the norm does not exceed the threshold (TF's clip_norm * min(1 / norm, 1 / clip_norm) is within an ulp of
 // it): a run whose threshold is never reached is bit-identical to an unguarded one.
 #include "sgg_common.h"
@@ -22,24 +21,11 @@
 
 extern "C" int sgg_arena_stats_chunk(void);
 
-__device__ __forceinline__ bool guard_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-__device__ __forceinline__ double guard_shfl_xor(double v, int o) {
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __shfl_xor((int)(b & 0xffffffffll), o, 64), hi = __shfl_xor((int)(b >> 32), o, 64);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
-}
-__device__ __forceinline__ double guard_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += guard_shfl_xor(v, o);
-  return v;
-}
-
 // the four waves' (ss, count) summed in wave order by thread 0; every thread must call it (barriers)
 __device__ __forceinline__ void guard_block_sum(double& ss, double& bad, double (*red)[SGG_GUARD_NROW]) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  ss = guard_wave_sum(ss);
-  bad = guard_wave_sum(bad);
+  ss = wave_sum(ss);
+  bad = wave_sum(bad);
   __syncthreads();                                    // (the previous round's reader of `red` is done)
   if (lane == 0) {
     red[wave][0] = ss;
@@ -84,7 +70,7 @@ __global__ __launch_bounds__(SGG_GUARD_THREADS) void grad_guard_chunk_kernel(con
       for (int q = 0; q < 4; ++q) {
         if (q < live) {
           const float x = gv[q];
-          if (guard_finite(x)) ss += (double)x * (double)x; else bad += 1.0;
+          if (sgg_finite(x)) ss += (double)x * (double)x; else bad += 1.0;
         }
       }
     }
@@ -123,83 +109,7 @@ __global__ __launch_bounds__(SGG_GUARD_THREADS) void grad_guard_final_kernel(con
   }
 }
 
-// adam_kernel of csrc/misc.hip behind the record's decision
-__global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                    long long n, float lr_t, float b1, float b2, float eps, const double* __restrict__ rec) {
-  if (rec[5] == 0.0) return;
-  const float gscale = (float)rec[4];
-  const long long n4 = n >> 2;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i] * gscale;
-    f32x4 mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i], pv = reinterpret_cast<f32x4*>(p)[i];
-    mv = mv * b1 + gv * (1.f - b1);
-    vv = vv * b2 + gv * gv * (1.f - b2);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) pv[q] -= lr_t * mv[q] / (sqrtf(vv[q]) + eps);
-    reinterpret_cast<f32x4*>(m)[i] = mv;
-    reinterpret_cast<f32x4*>(v)[i] = vv;
-    reinterpret_cast<f32x4*>(p)[i] = pv;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long long i = (n4 << 2) + threadIdx.x;
-    const float gv = g[i] * gscale;
-    const float mv = m[i] * b1 + gv * (1.f - b1);
-    const float vv = v[i] * b2 + gv * gv * (1.f - b2);
-    m[i] = mv; v[i] = vv;
-    p[i] -= lr_t * mv / (sqrtf(vv) + eps);
-  }
-}
-
-// adam_ema_kernel of csrc/ema.hip behind the record's decision
-__global__ void adam_ema_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                        float* __restrict__ v, float* __restrict__ e, long long n, float lr_t, float b1, float b2,
-                                        float eps, const double* __restrict__ rec, float omd) {
-  if (rec[5] == 0.0) return;
-  const float gscale = (float)rec[4];
-  const long long n4 = n >> 2;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i] * gscale;
-    f32x4 mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i], pv = reinterpret_cast<f32x4*>(p)[i];
-    f32x4 ev = reinterpret_cast<f32x4*>(e)[i];
-    mv = mv * b1 + gv * (1.f - b1);
-    vv = vv * b2 + gv * gv * (1.f - b2);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) pv[q] -= lr_t * mv[q] / (sqrtf(vv[q]) + eps);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ev[q] -= (ev[q] - pv[q]) * omd;
-    reinterpret_cast<f32x4*>(m)[i] = mv;
-    reinterpret_cast<f32x4*>(v)[i] = vv;
-    reinterpret_cast<f32x4*>(p)[i] = pv;
-    reinterpret_cast<f32x4*>(e)[i] = ev;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long long i = (n4 << 2) + threadIdx.x;
-    const float gv = g[i] * gscale;
-    const float mv = m[i] * b1 + gv * (1.f - b1);
-    const float vv = v[i] * b2 + gv * gv * (1.f - b2);
-    m[i] = mv; v[i] = vv;
-    float pv = p[i];
-    pv -= lr_t * mv / (sqrtf(vv) + eps);
-    p[i] = pv;
-    const float ev = e[i];
-    e[i] = ev - (ev - pv) * omd;
-  }
-}
-
 // ---- C ABI ------------------------------------------------------------------------------------------
-static inline int grid_for(long long n, int block) {
-  long long g = (n + block - 1) / block;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-// [a, a + n) and [b, b + n) floats share a byte
-static inline bool ranges_overlap(const float* a, const float* b, long long n) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
-  return x < y + len && y < x + len;
-}
-
 static inline long long guard_chunks(long long n) {
   const long long chunk = sgg_arena_stats_chunk();
   return n > 0 ? (n + chunk - 1) / chunk : 0;
@@ -233,35 +143,5 @@ extern "C" int sgg_grad_guard(const float* grads, long long n, float grad_scale,
   hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(SGG_GUARD_THREADS), 0, (hipStream_t)stream, (const double*)workspace,
                      n_chunks, grad_scale, max_norm, skip_nonfinite, record);
   SGG_LAUNCH_CHECK("sgg_grad_guard (record)");
-  return SGG_OK;
-}
-
-extern "C" int sgg_adam_tf_multi_guarded(float* params, const float* grads, float* m, float* v, long long n, float lr_t, float beta1,
-                                         float beta2, float eps, const double* record, void* stream) {
-  SGG_CHECK_ARG(params && grads && m && v && record && n > 0, "sgg_adam_tf_multi_guarded: bad argument");
-  SGG_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
-                "sgg_adam_tf_multi_guarded: pointers must be 16-byte aligned");
-  SGG_CHECK_ARG(((uintptr_t)record & 7) == 0, "sgg_adam_tf_multi_guarded: record must be 8-byte aligned");
-  hipLaunchKernelGGL(adam_guarded_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, n,
-                     lr_t, beta1, beta2, eps, record);
-  SGG_LAUNCH_CHECK("sgg_adam_tf_multi_guarded");
-  return SGG_OK;
-}
-
-extern "C" int sgg_adam_tf_multi_ema_guarded(float* params, const float* grads, float* m, float* v, float* ema, long long n,
-                                             float lr_t, float beta1, float beta2, float eps, const double* record,
-                                             float one_minus_decay, void* stream) {
-  SGG_CHECK_ARG(params && grads && m && v && ema && record && n > 0, "sgg_adam_tf_multi_ema_guarded: bad argument");
-  SGG_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0,
-                "sgg_adam_tf_multi_ema_guarded: pointers must be 16-byte aligned");
-  SGG_CHECK_ARG(((uintptr_t)record & 7) == 0, "sgg_adam_tf_multi_ema_guarded: record must be 8-byte aligned");
-  SGG_CHECK_ARG(!ranges_overlap(ema, params, n) && !ranges_overlap(ema, grads, n) && !ranges_overlap(ema, m, n) &&
-                    !ranges_overlap(ema, v, n),
-                "sgg_adam_tf_multi_ema_guarded: ema overlaps another operand");
-  SGG_CHECK_ARG(one_minus_decay >= 0.f && one_minus_decay <= 1.f,
-                "sgg_adam_tf_multi_ema_guarded: one_minus_decay %g is outside [0, 1]", (double)one_minus_decay);
-  hipLaunchKernelGGL(adam_ema_guarded_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, params, grads, m, v,
-                     ema, n, lr_t, beta1, beta2, eps, record, one_minus_decay);
-  SGG_LAUNCH_CHECK("sgg_adam_tf_multi_ema_guarded");
   return SGG_OK;
 }

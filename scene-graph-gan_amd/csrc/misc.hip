@@ -1,8 +1,6 @@
-// Loss, optimiser and utility kernels of the WGAN-GP step (gfx950).
+// Loss and utility kernels of the WGAN-GP step (gfx950); the optimiser's passes are in csrc/optim.hip.
 //   wgan_gp_loss_{fwd,bwd}  tfgan wasserstein_gradient_penalty(one_sided=True, epsilon=1e-10), train.py:249-250 (Appendix A.7)
 //   wgan_losses             wasserstein_{generator,discriminator}_loss, train.py:247-248 (Appendix A.6)
-//   adam_tf_multi           tf.train.AdamOptimizer(1e-4, beta1=0.5, beta2=0.9), train.py:258-259 (Appendix A.8):
-//                           theta -= lr_t * m / (sqrt(v) + eps), eps OUTSIDE the bias correction
 //   argmax_rows             tf.argmax(x, -1), train.py:270-271: int64, first index on ties
 #include "sgg_common.h"
 #include <stdarg.h>
@@ -113,30 +111,6 @@ __global__ __launch_bounds__(256) void wgan_losses_kernel(const float* __restric
   }
 }
 
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            long long n, float lr_t, float b1, float b2, float eps, float gscale) {
-  const long long n4 = n >> 2;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i] * gscale;
-    f32x4 mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i], pv = reinterpret_cast<f32x4*>(p)[i];
-    mv = mv * b1 + gv * (1.f - b1);
-    vv = vv * b2 + gv * gv * (1.f - b2);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) pv[q] -= lr_t * mv[q] / (sqrtf(vv[q]) + eps);
-    reinterpret_cast<f32x4*>(m)[i] = mv;
-    reinterpret_cast<f32x4*>(v)[i] = vv;
-    reinterpret_cast<f32x4*>(p)[i] = pv;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long long i = (n4 << 2) + threadIdx.x;
-    const float gv = g[i] * gscale;
-    const float mv = m[i] * b1 + gv * (1.f - b1);
-    const float vv = v[i] * b2 + gv * gv * (1.f - b2);
-    m[i] = mv; v[i] = vv;
-    p[i] -= lr_t * mv / (sqrtf(vv) + eps);
-  }
-}
-
 // one wave per row
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, long long* __restrict__ out, int rows, int V,
                                                           int ld) {
@@ -204,13 +178,6 @@ __global__ void embed_gather_bwd_kernel(const long long* __restrict__ labels, in
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------
-static inline int grid_for(long long n, int block) {
-  long long g = (n + block - 1) / block;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 extern "C" int sgg_absmax(const float* x, long long n, float* amax, void* stream) {
   SGG_CHECK_ARG(x && amax && n > 0 && (((uintptr_t)x) & 15) == 0, "sgg_absmax: bad argument");
   hipLaunchKernelGGL(absmax_kernel, dim3(grid_for(n / 4 + 1, 256) > 1024 ? 1024 : grid_for(n / 4 + 1, 256)), dim3(256), 0,
@@ -335,19 +302,6 @@ extern "C" int sgg_wgan_losses(const float* d_out, const float* pen, float lam, 
   SGG_CHECK_ARG(d_out && out4 && B > 0 && T > 0, "sgg_wgan_losses: bad argument");
   hipLaunchKernelGGL(wgan_losses_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, d_out, pen, lam, B, T, has_real, out4);
   SGG_LAUNCH_CHECK("sgg_wgan_losses");
-  return SGG_OK;
-}
-
-// "multi-tensor": every trainable tensor of a network lives in one arena, so one flat range covers them all.
-// grad_scale multiplies the gradient first (1/world_size after a sum all-reduce).
-extern "C" int sgg_adam_tf_multi(float* params, const float* grads, float* m, float* v, long long n, float lr_t, float beta1,
-                                 float beta2, float eps, float grad_scale, void* stream) {
-  SGG_CHECK_ARG(params && grads && m && v && n > 0, "sgg_adam_tf_multi: bad argument");
-  SGG_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
-                "sgg_adam_tf_multi: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, n, lr_t,
-                     beta1, beta2, eps, grad_scale);
-  SGG_LAUNCH_CHECK("sgg_adam_tf_multi");
   return SGG_OK;
 }
 

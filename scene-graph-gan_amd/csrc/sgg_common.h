@@ -38,7 +38,24 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline int sgg_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// workgroups of `block` threads for a grid-stride loop over n items: at least 1, at most 4096
+static inline int grid_for(long long n, int block) {
+  long long g = (n + block - 1) / block;
+  if (g > 4096) g = 4096;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+// [a, a + n) and [b, b + n) floats share a byte
+static inline bool ranges_overlap(const float* a, const float* b, long long n) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+  return x < y + len && y < x + len;
+}
+
 #ifdef __HIPCC__
+// neither Inf nor NaN (the statistics and guard passes count such elements instead of summing them)
+__device__ __forceinline__ bool sgg_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
 // ---- wave (64 lanes) reductions through DPP/ds_swizzle-backed shuffles -------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -48,6 +65,27 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// fp64: the same trees, a value exchanged as two 32-bit halves
+__device__ __forceinline__ double shfl_xor(double v, int o) {
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = __shfl_xor((int)(b & 0xffffffffll), o, 64), hi = __shfl_xor((int)(b >> 32), o, 64);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, shfl_xor(v, o));
   return v;
 }
 

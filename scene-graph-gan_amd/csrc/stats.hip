@@ -19,14 +19,12 @@
 #define SGG_STATS_THREADS 256
 #define SGG_VSTATS_N 5             // min, max, sum, count above the threshold, non-finite count
 
-__device__ __forceinline__ bool stats_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
 struct StatAcc {
   double ss;
   float mx;
   int bad;
   __device__ __forceinline__ void add(float x) {
-    if (stats_finite(x)) {
+    if (sgg_finite(x)) {
       ss += (double)x * (double)x;
       mx = fmaxf(mx, fabsf(x));
     } else {
@@ -34,27 +32,6 @@ struct StatAcc {
     }
   }
 };
-
-__device__ __forceinline__ double stats_shfl_xor(double v, int o) {
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __shfl_xor((int)(b & 0xffffffffll), o, 64), hi = __shfl_xor((int)(b >> 32), o, 64);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
-}
-__device__ __forceinline__ double stats_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += stats_shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double stats_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, stats_shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ double stats_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, stats_shfl_xor(v, o));
-  return v;
-}
 
 // table: n_chunks x (tensor, first arena element, count) as int64
 __global__ __launch_bounds__(SGG_STATS_THREADS) void arena_stats_chunk_kernel(
@@ -86,7 +63,7 @@ __global__ __launch_bounds__(SGG_STATS_THREADS) void arena_stats_chunk_kernel(
     double row[SGG_STATS_NSTAT] = {ag.ss, (double)ag.mx, (double)ag.bad, ap.ss, (double)ap.mx, (double)ap.bad,
                                    au.ss, (double)au.mx, (double)au.bad};
 #pragma unroll
-    for (int s = 0; s < SGG_STATS_NSTAT; ++s) row[s] = (s % 3 == 1) ? stats_wave_max(row[s]) : stats_wave_sum(row[s]);
+    for (int s = 0; s < SGG_STATS_NSTAT; ++s) row[s] = (s % 3 == 1) ? wave_max(row[s]) : wave_sum(row[s]);
     __syncthreads();                                  // (the previous chunk's readers of `red` are done)
     if (lane == 0) {
 #pragma unroll
@@ -129,7 +106,7 @@ __global__ __launch_bounds__(64) void arena_stats_tensor_kernel(const long long*
     }
   }
 #pragma unroll
-  for (int s = 0; s < SGG_STATS_NSTAT; ++s) row[s] = (s % 3 == 1) ? stats_wave_max(row[s]) : stats_wave_sum(row[s]);
+  for (int s = 0; s < SGG_STATS_NSTAT; ++s) row[s] = (s % 3 == 1) ? wave_max(row[s]) : wave_sum(row[s]);
   if (lane == 0) {
 #pragma unroll
     for (int s = 0; s < SGG_STATS_NSTAT; ++s) out[(size_t)t * SGG_STATS_NSTAT + s] = row[s];
@@ -143,7 +120,7 @@ __global__ __launch_bounds__(SGG_STATS_THREADS) void vector_stats_kernel(const f
   double mn = INFINITY, mx = -INFINITY, sum = 0.0, above = 0.0, bad = 0.0;
   for (int i = tid; i < n; i += SGG_STATS_THREADS) {
     const float a = x[i];
-    if (stats_finite(a)) {
+    if (sgg_finite(a)) {
       mn = fmin(mn, (double)a);
       mx = fmax(mx, (double)a);
       sum += (double)a;
@@ -152,11 +129,11 @@ __global__ __launch_bounds__(SGG_STATS_THREADS) void vector_stats_kernel(const f
       bad += 1.0;
     }
   }
-  mn = stats_wave_min(mn);
-  mx = stats_wave_max(mx);
-  sum = stats_wave_sum(sum);
-  above = stats_wave_sum(above);
-  bad = stats_wave_sum(bad);
+  mn = wave_min(mn);
+  mx = wave_max(mx);
+  sum = wave_sum(sum);
+  above = wave_sum(above);
+  bad = wave_sum(bad);
   if (lane == 0) {
     red[wave][0] = mn; red[wave][1] = mx; red[wave][2] = sum; red[wave][3] = above; red[wave][4] = bad;
   }

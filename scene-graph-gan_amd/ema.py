@@ -6,7 +6,7 @@ tf.train.ExponentialMovingAverage(decay, num_updates) keeps for every variable a
 
 after every optimiser step.  The warm-up of the schedule lets the first updates follow the variable closely (the first one with
 decay 0.1) so that the initial weights, which the shadow starts from, fade out quickly; it is always on here.  The device applies
-the update inside the optimiser pass (csrc/ema.hip, HipKernels.adam_ema); step.Network holds the buffer and the update count.
+the update inside the optimiser pass (csrc/optim.hip, HipKernels.adam_ema); step.Network holds the buffer and the update count.
 """
 from __future__ import annotations
 

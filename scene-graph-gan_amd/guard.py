@@ -7,8 +7,8 @@ Two controls of an update, both decided from one reduction over the whole gradie
                                   weight average keep every bit.
 
 The device takes the decision (csrc/guard.hip, HipKernels.grad_guard) and leaves it in a record of eight doubles that the guarded
-Adam pass reads from device memory (HipKernels.adam_guarded / adam_ema_guarded); step.Network holds the record.  The host never reads
-it on the training path.
+Adam pass (csrc/optim.hip) reads from device memory (HipKernels.adam_guarded / adam_ema_guarded); step.Network holds the record.
+The host never reads it on the training path.
 
     [0] ss      sum over the finite elements of ((double)x)^2, x = g * grad_scale formed in fp32 as the Adam pass forms it
     [1] bad     number of non-finite x (they enter no sum)

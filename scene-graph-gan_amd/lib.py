@@ -874,24 +874,45 @@ class HipKernels:
         self._check(self.lib.sgg_wgan_losses(_p(d_out), _p(pen), float(lam), B, T, int(has_real), _p(out4), self._stream()),
                     "sgg_wgan_losses")
 
+    # -- the optimiser's whole-arena passes (csrc/optim.hip) --------------------------------------------
+    def _adam(self, suffix, params, grads, m, v, ema, hyper, scale, one_minus_decay=None):
+        """The four Adam entry points sgg_adam_tf_multi<suffix> (one kernel body, csrc/optim.hip).  scale: the gradient scale, or the
+        fp64 record [8] of grad_guard that holds it (the guarded forms); ema with one_minus_decay: the forms that keep the average.
+        28 n bytes, 36 n with the average."""
+        arenas = (params, grads, m, v) if ema is None else (params, grads, m, v, ema)
+        guarded = torch.is_tensor(scale)
+        self._dev(*arenas, scale if guarded else None)
+        n = params.numel()
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in arenas)
+        assert not guarded or (scale.dtype == torch.float64 and tuple(scale.shape) == (8,) and scale.is_contiguous())
+        args = [_p(t) for t in arenas] + [n] + [float(x) for x in hyper] + [_p(scale) if guarded else float(scale)]
+        if ema is not None:
+            args.append(float(one_minus_decay))
+        fn = getattr(self.lib, "sgg_adam_tf_multi" + suffix)
+        self._check(self._timed("adam%s_kernel" % suffix, 0.0, lambda: fn(*args, self._stream()), (28.0 if ema is None else 36.0) * n),
+                    "sgg_adam_tf_multi" + suffix)
+
     def adam(self, params, grads, m, v, lr_t, b1, b2, eps, grad_scale=1.0):
-        self._dev(params, grads, m, v)
-        self._check(self._timed("adam_kernel", 0.0, lambda: self.lib.sgg_adam_tf_multi(
-            _p(params), _p(grads), _p(m), _p(v), params.numel(), float(lr_t), float(b1), float(b2), float(eps), float(grad_scale),
-            self._stream()), 28.0 * params.numel()), "sgg_adam_tf_multi")
+        self._adam("", params, grads, m, v, None, (lr_t, b1, b2, eps), grad_scale)
 
     def adam_ema(self, params, grads, m, v, ema, lr_t, b1, b2, eps, grad_scale=1.0, one_minus_decay=0.0):
-        """adam() and, in the same pass, ema -= (ema - params_new) * one_minus_decay (csrc/ema.hip; include/sgg_hip.h): params, m and
-        v bit-identical to adam().  ema: fp32, as long as params, overlapping none of the other operands."""
-        self._dev(params, grads, m, v, ema)
-        n = params.numel()
-        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (params, grads, m, v, ema))
-        self._check(self._timed("adam_ema_kernel", 0.0, lambda: self.lib.sgg_adam_tf_multi_ema(
-            _p(params), _p(grads), _p(m), _p(v), _p(ema), n, float(lr_t), float(b1), float(b2), float(eps), float(grad_scale),
-            float(one_minus_decay), self._stream()), 36.0 * n), "sgg_adam_tf_multi_ema")
+        """adam() and, in the same pass, ema -= (ema - params_new) * one_minus_decay (include/sgg_hip.h): params, m and v
+        bit-identical to adam().  ema: fp32, as long as params, overlapping none of the other operands."""
+        self._adam("_ema", params, grads, m, v, ema, (lr_t, b1, b2, eps), grad_scale, one_minus_decay)
+
+    def adam_guarded(self, params, grads, m, v, lr_t, b1, b2, eps, record):
+        """adam() with the gradient scale (float)record[4] read on the device, or nothing at all where record[5] == 0 (the record of
+        grad_guard, below)."""
+        assert torch.is_tensor(record)
+        self._adam("_guarded", params, grads, m, v, None, (lr_t, b1, b2, eps), record)
+
+    def adam_ema_guarded(self, params, grads, m, v, ema, lr_t, b1, b2, eps, record, one_minus_decay=0.0):
+        """adam_ema() with the gradient scale (float)record[4] read on the device, or nothing at all where record[5] == 0."""
+        assert torch.is_tensor(record)
+        self._adam("_ema_guarded", params, grads, m, v, ema, (lr_t, b1, b2, eps), record, one_minus_decay)
 
     def swap(self, a, b):
-        """Exchange the contents of two fp32 ranges of equal length bit for bit (csrc/ema.hip)."""
+        """Exchange the contents of two fp32 ranges of equal length bit for bit."""
         self._dev(a, b)
         n = a.numel()
         assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (a, b))
@@ -899,14 +920,14 @@ class HipKernels:
                     "sgg_swap_f32")
 
     def grad_accumulate(self, acc, g, first=False):
-        """acc = g (first) or acc += g, one fp32 addition per element (csrc/ema.hip): the pass of gradient accumulation."""
+        """acc = g (first) or acc += g, one fp32 addition per element: the pass of gradient accumulation."""
         self._dev(acc, g)
         n = acc.numel()
         assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (acc, g))
         self._check(self._timed("grad_accumulate_kernel", 0.0, lambda: self.lib.sgg_grad_accumulate(
             _p(acc), _p(g), n, int(bool(first)), self._stream()), (8.0 if first else 12.0) * n), "sgg_grad_accumulate")
 
-    # -- guarded updates (csrc/guard.hip, sgg_amd/guard.py) ---------------------------------------------
+    # -- guarded updates: the decision (csrc/guard.hip, sgg_amd/guard.py); adam_guarded / adam_ema_guarded above read it ----------
     def grad_guard_workspace_bytes(self, n):
         return int(self.lib.sgg_grad_guard_workspace_bytes(int(n)))
 
@@ -925,26 +946,6 @@ class HipKernels:
             _p(grads), n, float(grad_scale), float(max_norm), int(bool(skip_nonfinite)), int(grid), _p(ws),
             ws.numel() * ws.element_size(), _p(record), self._stream()), 4.0 * n), "sgg_grad_guard")
         return record
-
-    def adam_guarded(self, params, grads, m, v, lr_t, b1, b2, eps, record):
-        """adam() with the gradient scale (float)record[4] read on the device, or nothing at all where record[5] == 0."""
-        self._dev(params, grads, m, v, record)
-        n = params.numel()
-        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (params, grads, m, v))
-        assert record.dtype == torch.float64 and tuple(record.shape) == (8,) and record.is_contiguous()
-        self._check(self._timed("adam_guarded_kernel", 0.0, lambda: self.lib.sgg_adam_tf_multi_guarded(
-            _p(params), _p(grads), _p(m), _p(v), n, float(lr_t), float(b1), float(b2), float(eps), _p(record), self._stream()),
-            28.0 * n), "sgg_adam_tf_multi_guarded")
-
-    def adam_ema_guarded(self, params, grads, m, v, ema, lr_t, b1, b2, eps, record, one_minus_decay=0.0):
-        """adam_ema() with the gradient scale (float)record[4] read on the device, or nothing at all where record[5] == 0."""
-        self._dev(params, grads, m, v, ema, record)
-        n = params.numel()
-        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n for t in (params, grads, m, v, ema))
-        assert record.dtype == torch.float64 and tuple(record.shape) == (8,) and record.is_contiguous()
-        self._check(self._timed("adam_ema_guarded_kernel", 0.0, lambda: self.lib.sgg_adam_tf_multi_ema_guarded(
-            _p(params), _p(grads), _p(m), _p(v), _p(ema), n, float(lr_t), float(b1), float(b2), float(eps), _p(record),
-            float(one_minus_decay), self._stream()), 36.0 * n), "sgg_adam_tf_multi_ema_guarded")
 
     # -- training diagnostics (csrc/stats.hip) ---------------------------------------------------------
     def arena_stats_chunk(self):

@@ -34,6 +34,15 @@ def tf_adam_lr_t(t, lr=ADAM_LR, b1=ADAM_B1, b2=ADAM_B2):
     return lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
 
 
+def need_kernels(K, what, *kernels):
+    """`what` needs these methods of the kernel set K.  A set without one of them (the CPU reference kernels, a stub in a test) is
+    refused by name: an error before anything is launched, never a fall-back."""
+    missing = [n for n in kernels if not hasattr(K, n)]
+    if missing:
+        raise RuntimeError("%s needs the kernels %s; the %r kernel set lacks %s"
+                           % (what, ", ".join(kernels), getattr(K, "name", K), ", ".join(missing)))
+
+
 class Network:
     """Parameters (+ gradient / Adam arenas), encoder and head of one network for ONE batch size.
 
@@ -87,14 +96,12 @@ class Network:
             extra = self.opt.pop("pending_scale", None)
             self.adam_step(scale if extra is None else scale * extra)
 
-    # ---- gradient accumulation (csrc/ema.hip: grad_accumulate_kernel) ------------------------------------
+    # ---- gradient accumulation (csrc/optim.hip: grad_accumulate_kernel) ----------------------------------
     def _acc_flat(self):
         """The second gradient arena: allocated the first time an update spans more than one micro-batch, state of the ARENA."""
         acc = self.opt.get("acc")
         if acc is None:
-            if not hasattr(self.K, "grad_accumulate"):
-                raise RuntimeError("gradient accumulation needs the grad_accumulate kernel; the %r kernel set has none"
-                                   % getattr(self.K, "name", self.K))
+            need_kernels(self.K, "gradient accumulation", "grad_accumulate")
             acc = self.opt["acc"] = self.arena.like()[0]
         return acc
 
@@ -120,16 +127,19 @@ class Network:
         self.adam_t += 1
         a = self.arena
         lr_t = tf_adam_lr_t(self.adam_t)
-        avg = self.opt.get("ema")
-        if self.opt.get("guard") is not None:   # the decision on the device, then the Adam pass that reads it (csrc/guard.hip)
-            self._guarded_adam(lr_t, grad_scale, avg)
-        elif avg is None:
-            self.K.adam(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat),
-                        lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale)
-        else:                                # the same step with the shadow update of the average in the same pass (csrc/ema.hip)
-            self.K.adam_ema(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat), a.live(avg["flat"]),
-                            lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale, ema.one_minus_decay(avg["decay"], avg["updates"]))
-            avg["updates"] += 1
+        # One Adam pass (csrc/optim.hip), K.adam[_ema][_guarded]: the same arithmetic with two optional operands.
+        avg, gd = self.opt.get("ema"), self.opt.get("guard")
+        arenas, scale, tail = [a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat)], grad_scale, []
+        if avg is not None:                  # the shadow update of the average in the same pass
+            arenas.append(a.live(avg["flat"]))
+            tail = [ema.one_minus_decay(avg["decay"], avg["updates"])]
+        if gd is not None:                   # the decision on the device (csrc/guard.hip), then the pass reads its scale from the record
+            self.K.grad_guard(a.live(self.grad_flat), gd["record"], grad_scale, gd["max_norm"], gd["skip_nonfinite"], ws=gd["ws"])
+            scale = gd["record"]
+        kernel = getattr(self.K, "adam" + ("_ema" if avg is not None else "") + ("_guarded" if gd is not None else ""))
+        kernel(*arenas, lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, scale, *tail)
+        if avg is not None:
+            avg["updates"] += 1              # (also for a step the guard dropped: the host does not know)
         if self.opt.get("armed"):            # diagnostics: one read-only pass directly behind the step, on its stream
             self.arena_stats(lr_t, grad_scale)
         a.version += 1                       # (encoders of other batch sizes on this arena re-derive their operand formats lazily)
@@ -151,10 +161,7 @@ class Network:
         max_norm, skip_nonfinite = guardmod.check_settings(max_norm, skip_nonfinite)
         gd = self.opt.get("guard")
         if gd is None:
-            missing = [n for n in ("grad_guard", "adam_guarded", "adam_ema_guarded") if not hasattr(self.K, n)]
-            if missing:
-                raise RuntimeError("guarded updates need the grad_guard, adam_guarded and adam_ema_guarded kernels; the %r kernel "
-                                   "set lacks %s" % (getattr(self.K, "name", self.K), ", ".join(missing)))
+            need_kernels(self.K, "a guarded update", "grad_guard", "adam_guarded", "adam_ema_guarded")
             dev = self.arena.flat.device
             nbytes = self.K.grad_guard_workspace_bytes(self.arena.live_numel) if hasattr(self.K, "grad_guard_workspace_bytes") else 0
             gd = self.opt["guard"] = {"record": torch.zeros(guardmod.NREC, dtype=torch.float64, device=dev),
@@ -171,17 +178,6 @@ class Network:
         if gd is None:
             raise RuntimeError("%s: this network's updates are not guarded (enable_guard first)" % what)
         return gd
-
-    def _guarded_adam(self, lr_t, grad_scale, avg):
-        a, gd = self.arena, self.opt["guard"]
-        self.K.grad_guard(a.live(self.grad_flat), gd["record"], grad_scale, gd["max_norm"], gd["skip_nonfinite"], ws=gd["ws"])
-        if avg is None:
-            self.K.adam_guarded(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat),
-                                lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, gd["record"])
-        else:
-            self.K.adam_ema_guarded(a.live(), a.live(self.grad_flat), a.live(self.m_flat), a.live(self.v_flat), a.live(avg["flat"]),
-                                    lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, gd["record"], ema.one_minus_decay(avg["decay"], avg["updates"]))
-            avg["updates"] += 1              # (also for a dropped step: the host does not know)
 
     def guard_report(self):
         """The record of the LAST guarded step as a dict (guard.report: norm, coef, s_eff, nonfinite, apply, and the cumulative
@@ -201,7 +197,7 @@ class Network:
         self.finish_update()
         gd["record"][6:8] = torch.tensor([float(int(clipped)), float(int(skipped))], dtype=torch.float64)
 
-    # ---- weight averaging (sgg_amd/ema.py, csrc/ema.hip) -------------------------------------------------
+    # ---- weight averaging (sgg_amd/ema.py, csrc/optim.hip) -----------------------------------------------
     # opt["ema"] = {"flat": buffer of the arena's layout, "decay", "updates": shadow updates applied, "swapped"}: state of the ARENA,
     # like t / pending / diag - every Network on it sees the same average.
     has_average = property(lambda self: self.opt.get("ema") is not None)
@@ -220,9 +216,7 @@ class Network:
         if avg is not None:
             avg["decay"] = float(decay)
             return
-        if not (hasattr(self.K, "adam_ema") and hasattr(self.K, "swap")):
-            raise RuntimeError("weight averaging needs the adam_ema and swap kernels; the %r kernel set has none"
-                               % getattr(self.K, "name", self.K))
+        need_kernels(self.K, "weight averaging", "adam_ema", "swap")
         self.finish_update()
         self.opt["ema"] = {"flat": self.arena.flat.clone(), "decay": float(decay), "updates": 0, "swapped": False}
 
@@ -306,8 +300,7 @@ class Network:
         """Chunk table, workspace and stats buffer of this ARENA: built once, kept in `opt` (every Network on the arena sees them)."""
         st = self.opt.get("diag")
         if st is None:
-            if not hasattr(self.K, "arena_stats"):
-                raise RuntimeError("diagnostics need the arena_stats kernel; the %r kernel set has none" % getattr(self.K, "name", self.K))
+            need_kernels(self.K, "the diagnostics pass", "arena_stats")
             chunk = self.K.arena_stats_chunk()
             names, offsets, numels = diagnostics.live_layout(self.arena)
             table = diagnostics.chunk_table(offsets, numels, chunk)
@@ -638,10 +631,7 @@ class GanStep:
 
     # ---- generator likelihood (csrc/xent.hip) -------------------------------------------------------------
     def _need_xent(self, what):
-        missing = [n for n in ("softmax_xent", "xent_summary") if not hasattr(self.K, n)]
-        if missing:
-            raise RuntimeError("%s needs the softmax_xent and xent_summary kernels; the %r kernel set lacks %s"
-                               % (what, getattr(self.K, "name", self.K), ", ".join(missing)))
+        need_kernels(self.K, what, "softmax_xent", "xent_summary")
 
     def _xent(self, logits, labels, scale, dlogits, accumulate, out):
         """softmax_xent of the B * 3 decoder rows `logits` [B,3,V] against labels int64 [B,3] (gradient into dlogits unless None),

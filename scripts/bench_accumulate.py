@@ -1,4 +1,4 @@
-"""bench_accumulate.py - what gradient accumulation costs (csrc/ema.hip: grad_accumulate_kernel; step.Network.end_micro_batch,
+"""bench_accumulate.py - what gradient accumulation costs (csrc/optim.hip: grad_accumulate_kernel; step.Network.end_micro_batch,
 GanStep.train_iteration_accumulated):
 
   kernels     on G's live arena for vocab 1000 and vocab 70 000 at 224 x 224, in one run, the legs alternating:

@@ -1,4 +1,4 @@
-"""bench_ema.py - what averaging the generator's weights costs (csrc/ema.hip, sgg_amd/ema.py, step.Network.enable_averaging):
+"""bench_ema.py - what averaging the generator's weights costs (csrc/optim.hip, sgg_amd/ema.py, step.Network.enable_averaging):
 
   kernels     on G's live arena for vocab 1000 and vocab 70 000 at 224 x 224, in one run, the legs alternating:
                 adam           HipKernels.adam (adam_kernel)                                  7 n words

@@ -1,4 +1,4 @@
-"""bench_guard.py - what guarding the updates costs (csrc/guard.hip, sgg_amd/guard.py, step.Network.enable_guard):
+"""bench_guard.py - what guarding the updates costs (csrc/guard.hip, csrc/optim.hip, sgg_amd/guard.py, step.Network.enable_guard):
 
   kernels     on G's live arena for vocab 1000 at 224 x 224, in one run, the legs alternating:
                 adam               HipKernels.adam (adam_kernel)                                    7 n words

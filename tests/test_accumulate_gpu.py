@@ -1,4 +1,4 @@
-"""-m gpu: gradient accumulation on the device - the accumulate kernel (csrc/ema.hip) against NumPy fp32, an update from N micro-batches
+"""-m gpu: gradient accumulation on the device - the accumulate kernel (csrc/optim.hip) against NumPy fp32, an update from N micro-batches
 against the CPU oracle on all N * B rows, the plumbing bit for bit, the two-stream schedule, G-encoder reuse per micro-batch,
 diagnostics, weight averaging and train.py --accumulate.
 
@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 PAD, SENTINEL = 64, -777.0
-# the launcher of csrc/ema.hip (grid_for): blocks of BLOCK threads, VEC floats per thread and trip, at most GRID_CAP blocks
+# the launcher of csrc/optim.hip (grid_for): blocks of BLOCK threads, VEC floats per thread and trip, at most GRID_CAP blocks
 GRID_CAP, BLOCK, VEC = 4096, 256, 4
 ONE_PASS = GRID_CAP * BLOCK * VEC                       # elements one trip of the capped grid covers
 SIZES = [1, 2, 3, 4, 5, 7, 1027, ONE_PASS + 3, ONE_PASS + VEC * BLOCK + 2]      # (the last: a second trip of the loop AND a tail)

@@ -33,7 +33,7 @@ def ema_bound(e, p):
 
 
 class EmaRefKernels(RefKernels):
-    """The kernel-level reference with the two entry points of csrc/ema.hip: its own adam followed by ema.reference_update, and an
+    """The kernel-level reference with adam_ema and swap of csrc/optim.hip: its own adam followed by ema.reference_update, and an
     exchange through a copy."""
 
     def adam_ema(self, params, grads, m, v, avg, lr_t, b1, b2, eps, grad_scale=1.0, one_minus_decay=0.0):

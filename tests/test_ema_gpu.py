@@ -1,4 +1,4 @@
-"""-m gpu: weight averaging on the device - the fused Adam + average kernel and the swap (csrc/ema.hip) against HipKernels.adam and
+"""-m gpu: weight averaging on the device - the fused Adam + average kernel and the swap (csrc/optim.hip) against HipKernels.adam and
 sgg_amd.ema.reference_update, step.Network with averaging on the two-stream schedule, averaged() (other batch sizes included) and
 train.py --ema_decay / --eval_live.
 

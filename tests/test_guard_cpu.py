@@ -33,9 +33,9 @@ NEW = ("grad_guard", "adam_guarded", "adam_ema_guarded")
 
 
 class GuardRefKernels(RefKernels):
-    """The kernel-level reference with torch versions of the three entry points of csrc/guard.hip in the arithmetic of its tensors
-    (fp64 here: s_eff is NOT rounded to fp32), next to those of csrc/ema.hip that the step needs; every call of a new entry point
-    is recorded."""
+    """The kernel-level reference with torch versions of the guard's three entry points (csrc/guard.hip, csrc/optim.hip) in the
+    arithmetic of its tensors (fp64 here: s_eff is NOT rounded to fp32), next to the others of csrc/optim.hip that the step needs;
+    every call of a new entry point is recorded."""
 
     def __init__(self):
         super().__init__()

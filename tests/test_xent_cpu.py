@@ -31,7 +31,7 @@ NEW = ("softmax_xent", "xent_summary", "triple_logp")
 
 
 class XentRefKernels(GuardRefKernels):
-    """The kernel-level reference (with the entry points of csrc/ema.hip and csrc/guard.hip that the step needs) carrying torch
+    """The kernel-level reference (with the entry points of csrc/optim.hip and csrc/guard.hip that the step needs) carrying torch
     versions of the three entry points of csrc/xent.hip in the arithmetic of their tensors; every call of them is recorded."""
 
     def softmax_xent(self, logits, labels=None, scale=1.0, accumulate=False, dlogits=None, nll=None, lse=None, hit=None):
