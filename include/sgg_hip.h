@@ -261,6 +261,13 @@ int sgg_gemm_skinny_dgrad(int M, int N, int K, const float* A, int lda, const fl
                           int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 int sgg_gemm_skinny_wgrad(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                           int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* The kernels the launch with these scalars starts (mode 0 = fwd, 1 = dgrad, 2 = wgrad), in launch order and separated by ';',
+ * spelled as rocprofv3 prints them with spaces removed and every template argument written out, for instance
+ * "gemm_wk_kernel<2,false,4>" or "gemm_kernel<false,true>;gemm_slab_reduce_wide_kernel".  *nsplit (may be NULL) = the K ranges
+ * the slab kernels split into (1: no slabs).  A pure host function: the launch's own validation and route, no GPU.  The route
+ * does not depend on pointers or leading dimensions (those only choose between vector and scalar loads inside a kernel).
+ * buf_len >= 96. */
+int sgg_gemm_skinny_symbol(int mode, int M, int N, int K, int* nsplit, char* buf, int buf_len);
 /* the step-invariant part of the attention perceptron, ctx_flat[B, L*C] x W_ctx[L*C, L] (same kernels, named
  * for the call site generator_with_attention.py:15) */
 int sgg_attn_ctx_gemm_fwd(int B, int L, int LC, const float* ctx_flat, const float* w_ctx, const float* bias, float* P,
@@ -290,6 +297,11 @@ int sgg_attn_step_fwd(const float* P, const float* ec, const float* ec_dual, int
 int sgg_attn_step_bwd(const float* ctx, const float* alpha, const float* alpha_dual, const float* dz,
                       const float* dz_dual, int lddz, float* de, float* de_dual, float* dP, float* dctx, int R, int B,
                       int L, int C, int accumulate, void* stream);
+/* The kernels those two launches start for these scalars (dual != 0: the *_dual pointers are given), in the spelling of
+ * sgg_gemm_skinny_symbol, for instance "attn_step_bwd_ctx_kernel<Dual>;attn_step_bwd_softmax_kernel<Dual>".  Pure host
+ * functions; they refuse what the launches refuse, with the same sgg_last_error text.  buf_len >= 96. */
+int sgg_attn_step_fwd_symbol(int R, int B, int L, int C, int dual, char* buf, int buf_len);
+int sgg_attn_step_bwd_symbol(int R, int B, int L, int C, int dual, char* buf, int buf_len);
 
 /* ---- tf.contrib.rnn.LayerNormBasicLSTMCell(512) pointwise part ---------------------------------------------
  * generator_with_attention.py:79,87 / discriminator_with_attention.py:81,89.  gates = [x,h] @ kernel, [R,2048] in

@@ -10,6 +10,7 @@
 // in a fixed order by a second kernel (deterministic). Arbitrary M, N, K, leading dimensions and alignment
 // (unaligned operands take a scalar load path).
 #include "mma_f32.h"
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -266,8 +267,7 @@ static int gemm_wk_tm(int M, int N) {
   return 1;
 }
 template <bool TB>
-static void gemm_wk_launch(const GemmParams& p, hipStream_t st) {
-  const int tm = gemm_wk_tm(p.M, p.N);
+static void gemm_wk_launch(const GemmParams& p, int tm, hipStream_t st) {
   const dim3 grid(sgg_cdiv(p.M, 16 * tm) * sgg_cdiv(p.N, 16));
   if (tm == 6) hipLaunchKernelGGL((gemm_wk_kernel<6, TB, 2>), grid, dim3(64 * WK_WAVES), 0, st, p);
   else if (tm == 4) hipLaunchKernelGGL((gemm_wk_kernel<4, TB, 2>), grid, dim3(64 * WK_WAVES), 0, st, p);
@@ -319,11 +319,34 @@ extern "C" size_t sgg_gemm_workspace_bytes(int M, int N, int K) {
   return ns > 1 ? (size_t)ns * M * N * sizeof(float) : 0;
 }
 
+// ---- one decision per GEMM entry point: gemm_run launches this route, sgg_gemm_skinny_symbol prints it ------------------------
+// wk: one gemm_wk_kernel<tm, mode == 1, pd>.  Otherwise gemm_kernel<mode == 2, mode == 1> over nsplit K ranges of kchunk, followed
+// (nsplit > 1) by the slab reduce: the wide one from 16 slabs.
+struct GemmRoute {
+  bool wk;
+  int tm, pd;             // wk: 16 tm rows per tile, pd k groups in flight per wave
+  int nsplit, kchunk;     // the split of gemm_plan (wk: the split the 64 x 64 tiling would have taken; not launched)
+  bool wide_reduce;
+};
+static const char* const GEMM_ENTRY[3] = {"sgg_gemm_skinny_fwd", "sgg_gemm_skinny_dgrad", "sgg_gemm_skinny_wgrad"};
+
+static int gemm_route(int mode, int M, int N, int K, const char* name, GemmRoute* r) {
+  SGG_CHECK_ARG(M > 0 && N > 0 && K > 0, "%s: M, N, K must be positive (got %d, %d, %d)", name, M, N, K);
+  gemm_plan(M, N, K, &r->nsplit, &r->kchunk);
+  r->wk = gemm_wk_applicable(mode, M, N, K, r->nsplit);
+  r->tm = r->wk ? gemm_wk_tm(M, N) : 0;
+  r->pd = r->tm >= 4 ? 2 : 4;
+  r->wide_reduce = !r->wk && r->nsplit >= 16;
+  return SGG_OK;
+}
+
 // mode: 0 = NN (fwd), 1 = NT (dgrad), 2 = TN (wgrad)
 static int gemm_run(int mode, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                     const float* bias, int accumulate, void* workspace, size_t workspace_bytes, void* stream, const char* name) {
   SGG_CHECK_ARG(A && B && C, "%s: null pointer", name);
-  SGG_CHECK_ARG(M > 0 && N > 0 && K > 0, "%s: M, N, K must be positive (got %d, %d, %d)", name, M, N, K);
+  GemmRoute r;
+  int rc = gemm_route(mode, M, N, K, name, &r);
+  if (rc) return rc;
   const int a_cols = (mode == 2) ? M : K, b_cols = (mode == 1) ? K : N;
   SGG_CHECK_ARG(lda >= a_cols && ldb >= b_cols && ldc >= N, "%s: leading dimension too small", name);
   GemmParams p;
@@ -331,50 +354,67 @@ static int gemm_run(int mode, int M, int N, int K, const float* A, int lda, cons
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.accumulate = accumulate;
   p.avec = (lda % 4 == 0) && (((uintptr_t)A & 15) == 0);
   p.bvec = (ldb % 4 == 0) && (((uintptr_t)B & 15) == 0);
-  gemm_plan(M, N, K, &p.nsplit, &p.kchunk);
+  p.nsplit = r.nsplit; p.kchunk = r.kchunk;
   hipStream_t st = (hipStream_t)stream;
-  if (gemm_wk_applicable(mode, M, N, K, p.nsplit)) {
-    if (mode == 0) gemm_wk_launch<false>(p, st);
-    else gemm_wk_launch<true>(p, st);
+  if (r.wk) {
+    if (mode == 0) gemm_wk_launch<false>(p, r.tm, st);
+    else gemm_wk_launch<true>(p, r.tm, st);
     SGG_LAUNCH_CHECK(name);
     return SGG_OK;
   }
-  if (p.nsplit > 1) {
-    const size_t need = (size_t)p.nsplit * M * N * sizeof(float);
+  if (r.nsplit > 1) {
+    const size_t need = (size_t)r.nsplit * M * N * sizeof(float);
     if (!workspace || workspace_bytes < need) {
       sgg_set_error("%s: workspace too small (%zu < %zu)", name, workspace_bytes, need);
       return SGG_ERR_WORKSPACE;
     }
   }
-  dim3 grid(sgg_cdiv(M, 64) * sgg_cdiv(N, 64), 1, p.nsplit);
+  dim3 grid(sgg_cdiv(M, 64) * sgg_cdiv(N, 64), 1, r.nsplit);
   if (mode == 0) hipLaunchKernelGGL((gemm_kernel<false, false>), grid, dim3(256), 0, st, p);
   else if (mode == 1) hipLaunchKernelGGL((gemm_kernel<false, true>), grid, dim3(256), 0, st, p);
   else hipLaunchKernelGGL((gemm_kernel<true, false>), grid, dim3(256), 0, st, p);
   SGG_LAUNCH_CHECK(name);
-  if (p.nsplit > 1) {
+  if (r.nsplit > 1) {
     const long long n = (long long)M * N;
-    if (p.nsplit >= 16)
+    if (r.wide_reduce)
       hipLaunchKernelGGL(gemm_slab_reduce_wide_kernel, dim3(sgg_cdiv(n, 32)), dim3(256), 0, st, (const float*)workspace, C, bias, M,
-                         N, ldc, p.nsplit, accumulate);
+                         N, ldc, r.nsplit, accumulate);
     else
       hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3(sgg_cdiv(n, 256)), dim3(256), 0, st, (const float*)workspace, C, bias, M,
-                         N, ldc, p.nsplit, accumulate);
+                         N, ldc, r.nsplit, accumulate);
     SGG_LAUNCH_CHECK(name);
   }
   return SGG_OK;
 }
 
+// The kernels sgg_gemm_skinny_{fwd,dgrad,wgrad}(M, N, K) launch, in launch order, separated by ';' (rocprofv3's spelling with
+// spaces removed); *nsplit (may be NULL) = the K ranges of the slab kernels, 1 for a single-kernel route.
+extern "C" int sgg_gemm_skinny_symbol(int mode, int M, int N, int K, int* nsplit, char* buf, int buf_len) {
+  SGG_CHECK_ARG(mode >= 0 && mode <= 2, "sgg_gemm_skinny_symbol: mode must be 0 (fwd), 1 (dgrad) or 2 (wgrad), got %d", mode);
+  SGG_CHECK_ARG(buf && buf_len >= 96, "sgg_gemm_skinny_symbol: the buffer must hold at least 96 bytes");
+  GemmRoute r;
+  int rc = gemm_route(mode, M, N, K, GEMM_ENTRY[mode], &r);
+  if (rc) return rc;
+  if (nsplit) *nsplit = r.wk ? 1 : r.nsplit;
+  if (r.wk)
+    snprintf(buf, (size_t)buf_len, "gemm_wk_kernel<%d,%s,%d>", r.tm, mode == 1 ? "true" : "false", r.pd);
+  else
+    snprintf(buf, (size_t)buf_len, "gemm_kernel<%s,%s>%s", mode == 2 ? "true" : "false", mode == 1 ? "true" : "false",
+             r.nsplit <= 1 ? "" : r.wide_reduce ? ";gemm_slab_reduce_wide_kernel" : ";gemm_slab_reduce_kernel");
+  return SGG_OK;
+}
+
 extern "C" int sgg_gemm_skinny_fwd(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                                    const float* bias, int accumulate, void* ws, size_t ws_bytes, void* stream) {
-  return gemm_run(0, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, ws, ws_bytes, stream, "sgg_gemm_skinny_fwd");
+  return gemm_run(0, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, ws, ws_bytes, stream, GEMM_ENTRY[0]);
 }
 extern "C" int sgg_gemm_skinny_dgrad(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                                      int accumulate, void* ws, size_t ws_bytes, void* stream) {
-  return gemm_run(1, M, N, K, A, lda, B, ldb, C, ldc, nullptr, accumulate, ws, ws_bytes, stream, "sgg_gemm_skinny_dgrad");
+  return gemm_run(1, M, N, K, A, lda, B, ldb, C, ldc, nullptr, accumulate, ws, ws_bytes, stream, GEMM_ENTRY[1]);
 }
 extern "C" int sgg_gemm_skinny_wgrad(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                                      int accumulate, void* ws, size_t ws_bytes, void* stream) {
-  return gemm_run(2, M, N, K, A, lda, B, ldb, C, ldc, nullptr, accumulate, ws, ws_bytes, stream, "sgg_gemm_skinny_wgrad");
+  return gemm_run(2, M, N, K, A, lda, B, ldb, C, ldc, nullptr, accumulate, ws, ws_bytes, stream, GEMM_ENTRY[2]);
 }
 
 // Step-invariant part of the attention perceptron (generator_with_attention.py:15): P = ctx_flat * W_ctx + b.

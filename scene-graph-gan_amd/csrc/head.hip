@@ -13,6 +13,7 @@
 // dual plane = cotangent of the primal (dual.h).
 #include "dual.h"
 #include "mma_f32.h"
+#include <stdio.h>
 #include <stdlib.h>
 
 #define HEAD_LN_EPS 1e-12f
@@ -631,36 +632,99 @@ static int attn_check(const char* name, int R, int B, int L, int C) {
   return SGG_OK;
 }
 
+// ---- one decision per attention entry point: the launch switches on the route, sgg_attn_step_{fwd,bwd}_symbol print it --------
+#define ATTN_DYN_LDS_DEFAULT (64 * 1024)  // dynamic LDS a launch gets without hipFuncAttributeMaxDynamicSharedMemorySize
+#define ATTN_DYN_LDS_MAX (150 * 1024)
+
+struct AttnFwdRoute {
+  bool rows;              // attn_step_fwd_rows_kernel<tr> (many float rows per image), else attn_step_fwd_kernel<float | Dual>
+  bool dual;
+  int tr;                 // rows: rows per tile
+  int cs;                 // per-row kernel: workgroups per row (C / cs channels each)
+  size_t lds;             // dynamic LDS bytes
+};
+// many float rows per image (evaluation: N samples of each image): one read of the feature map per tile of rows.  64-row tiles
+// while alpha fits beside the staging buffers with room to spare, 32-row tiles up to the LDS size, the per-row kernel beyond.
+static int attn_fwd_route(int R, int B, int L, int C, bool dual, AttnFwdRoute* r) {
+  int rc = attn_check("sgg_attn_step_fwd", R, B, L, C);
+  if (rc) return rc;
+  const int N = R / B, tr = attn_rows_lds_bytes(64, L) <= 112 * 1024 ? 64 : 32;
+  r->dual = dual;
+  r->rows = !dual && N >= ATTN_ROWS_MIN_RATIO && attn_rows_lds_bytes(tr, L) <= ATTN_ROWS_MAX_LDS;
+  if (r->rows) {
+    r->tr = tr;
+    r->cs = 0;
+    r->lds = attn_rows_lds_bytes(tr, L);
+    return SGG_OK;
+  }
+  r->tr = 0;
+  r->cs = (R < 256 && C % 512 == 0) ? 2 : 1;      // two workgroups per row (256 channels each) while the rows do not fill the chip
+  r->lds = (size_t)(L + 1024) * (dual ? sizeof(Dual) : sizeof(float));
+  SGG_CHECK_ARG(r->lds <= ATTN_DYN_LDS_MAX, "sgg_attn_step_fwd: L too large for LDS (%zu bytes)", r->lds);
+  return SGG_OK;
+}
+
+struct AttnBwdRoute {
+  bool dual;
+  int ls;                 // > 1: attn_step_bwd_ctx_kernel on (B, ls) workgroups + attn_step_bwd_softmax_kernel; 1: the fused kernel
+  size_t lds;             // dynamic LDS bytes of the first kernel
+};
+static int attn_bwd_route(int R, int B, int L, int C, bool dual, AttnBwdRoute* r) {
+  int rc = attn_check("sgg_attn_step_bwd", R, B, L, C);
+  if (rc) return rc;
+  const int npass = R / B;
+  SGG_CHECK_ARG(npass <= ATTN_MAX_PASS, "sgg_attn_step_bwd: at most %d rows per image (got %d)", ATTN_MAX_PASS, npass);
+  const size_t elem = dual ? sizeof(Dual) : sizeof(float);
+  r->dual = dual;
+  // full-size feature maps: split the locations of an image over several workgroups (see attn_step_bwd_ctx_kernel)
+  r->ls = (B < 256 && L >= 64 && L <= 2048) ? (512 / B < L / 8 ? 512 / B : L / 8) : 1;
+  if (r->ls > 1) {
+    r->lds = (size_t)npass * C * elem;
+  } else {
+    r->lds = (size_t)npass * (C + 2 * L) * elem;
+    SGG_CHECK_ARG(r->lds <= ATTN_DYN_LDS_MAX, "sgg_attn_step_bwd: L too large for LDS (%zu bytes)", r->lds);
+  }
+  return SGG_OK;
+}
+
+// a kernel that asks for more dynamic LDS than the default limit has to be told so before the launch
+template <typename F>
+static int attn_allow_lds(F kernel, size_t lds, const char* name) {
+  if (lds <= ATTN_DYN_LDS_DEFAULT) return SGG_OK;
+  const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  SGG_CHECK_ARG(e == hipSuccess, "%s: %zu bytes of LDS refused: %s", name, lds, hipGetErrorString(e));
+  return SGG_OK;
+}
+
 extern "C" int sgg_attn_step_fwd(const float* P, const float* ec, const float* ec_dual, int ldec, const float* ctx, float* alpha,
                                  float* alpha_dual, float* z, float* z_dual, int ldz, int R, int B, int L, int C, void* stream) {
   SGG_CHECK_ARG(P && ec && ctx && alpha && z, "sgg_attn_step_fwd: null pointer");
-  int rc = attn_check("sgg_attn_step_fwd", R, B, L, C);
+  AttnFwdRoute r;
+  int rc = attn_fwd_route(R, B, L, C, ec_dual != nullptr, &r);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // many float rows per image (evaluation: N samples of each image): one read of the feature map per tile of rows.  64-row tiles
-  // while alpha fits beside the staging buffers with room to spare, 32-row tiles up to the LDS size, the per-row kernel beyond.
-  const int N = R / B, tr = attn_rows_lds_bytes(64, L) <= 112 * 1024 ? 64 : 32;
-  if (!ec_dual && N >= ATTN_ROWS_MIN_RATIO && attn_rows_lds_bytes(tr, L) <= ATTN_ROWS_MAX_LDS) {
-    const size_t smb = attn_rows_lds_bytes(tr, L);
-    const dim3 grid(B, sgg_cdiv(N, tr), C / ATTN_ROWS_CS);
-    if (tr == 64) {
-      (void)hipFuncSetAttribute((const void*)attn_step_fwd_rows_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smb);
-      hipLaunchKernelGGL(attn_step_fwd_rows_kernel<64>, grid, dim3(256), smb, st, P, ec, ldec, ctx, alpha, z, ldz, B, N, L, C);
+  if (r.rows) {
+    const int N = R / B;
+    const dim3 grid(B, sgg_cdiv(N, r.tr), C / ATTN_ROWS_CS);
+    if (r.tr == 64) {
+      (void)hipFuncSetAttribute((const void*)attn_step_fwd_rows_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+      hipLaunchKernelGGL(attn_step_fwd_rows_kernel<64>, grid, dim3(256), r.lds, st, P, ec, ldec, ctx, alpha, z, ldz, B, N, L, C);
     } else {
-      (void)hipFuncSetAttribute((const void*)attn_step_fwd_rows_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smb);
-      hipLaunchKernelGGL(attn_step_fwd_rows_kernel<32>, grid, dim3(256), smb, st, P, ec, ldec, ctx, alpha, z, ldz, B, N, L, C);
+      (void)hipFuncSetAttribute((const void*)attn_step_fwd_rows_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+      hipLaunchKernelGGL(attn_step_fwd_rows_kernel<32>, grid, dim3(256), r.lds, st, P, ec, ldec, ctx, alpha, z, ldz, B, N, L, C);
     }
     SGG_LAUNCH_CHECK("sgg_attn_step_fwd");
     return SGG_OK;
   }
-  const int cs = (R < 256 && C % 512 == 0) ? 2 : 1;      // two workgroups per row (256 channels each) while the rows do not fill the chip
-  if (ec_dual) {
+  if (r.dual) {
     SGG_CHECK_ARG(alpha_dual && z_dual, "sgg_attn_step_fwd: dual outputs missing");
-    hipLaunchKernelGGL(attn_step_fwd_kernel<Dual>, dim3(R, cs), dim3(256), (size_t)(L + 1024) * sizeof(Dual), st, P, ec, ec_dual, ldec,
-                       ctx, alpha, alpha_dual, z, z_dual, ldz, B, L, C);
+    if ((rc = attn_allow_lds(attn_step_fwd_kernel<Dual>, r.lds, "sgg_attn_step_fwd"))) return rc;
+    hipLaunchKernelGGL(attn_step_fwd_kernel<Dual>, dim3(R, r.cs), dim3(256), r.lds, st, P, ec, ec_dual, ldec, ctx, alpha, alpha_dual, z,
+                       z_dual, ldz, B, L, C);
   } else {
-    hipLaunchKernelGGL(attn_step_fwd_kernel<float>, dim3(R, cs), dim3(256), (size_t)(L + 1024) * sizeof(float), st, P, ec, nullptr, ldec,
-                       ctx, alpha, nullptr, z, nullptr, ldz, B, L, C);
+    if ((rc = attn_allow_lds(attn_step_fwd_kernel<float>, r.lds, "sgg_attn_step_fwd"))) return rc;
+    hipLaunchKernelGGL(attn_step_fwd_kernel<float>, dim3(R, r.cs), dim3(256), r.lds, st, P, ec, nullptr, ldec, ctx, alpha, nullptr, z,
+                       nullptr, ldz, B, L, C);
   }
   SGG_LAUNCH_CHECK("sgg_attn_step_fwd");
   return SGG_OK;
@@ -671,41 +735,58 @@ extern "C" int sgg_attn_step_bwd(const float* ctx, const float* alpha, const flo
                                  const float* dz_dual, int lddz, float* de, float* de_dual, float* dP, float* dctx, int R, int B,
                                  int L, int C, int accumulate, void* stream) {
   SGG_CHECK_ARG(ctx && alpha && dz && de && dP && dctx, "sgg_attn_step_bwd: null pointer");
-  int rc = attn_check("sgg_attn_step_bwd", R, B, L, C);
+  AttnBwdRoute r;
+  int rc = attn_bwd_route(R, B, L, C, alpha_dual != nullptr, &r);
   if (rc) return rc;
-  const int npass = R / B;
-  SGG_CHECK_ARG(npass <= ATTN_MAX_PASS, "sgg_attn_step_bwd: at most %d rows per image (got %d)", ATTN_MAX_PASS, npass);
+  if (r.dual) SGG_CHECK_ARG(dz_dual && de_dual, "sgg_attn_step_bwd: dual pointers missing");
   hipStream_t st = (hipStream_t)stream;
-  // full-size feature maps: split the locations of an image over several workgroups (see attn_step_bwd_ctx_kernel)
-  const int ls = (B < 256 && L >= 64 && L <= 2048) ? (512 / B < L / 8 ? 512 / B : L / 8) : 1;
-  if (ls > 1) {
-    if (alpha_dual) {
-      SGG_CHECK_ARG(dz_dual && de_dual, "sgg_attn_step_bwd: dual pointers missing");
-      hipLaunchKernelGGL(attn_step_bwd_ctx_kernel<Dual>, dim3(B, ls), dim3(256), (size_t)npass * C * sizeof(Dual), st, ctx, alpha,
-                         alpha_dual, dz, dz_dual, lddz, de, de_dual, dctx, R, B, L, C, accumulate);
+  if (r.ls > 1) {
+    if (r.dual) {
+      hipLaunchKernelGGL(attn_step_bwd_ctx_kernel<Dual>, dim3(B, r.ls), dim3(256), r.lds, st, ctx, alpha, alpha_dual, dz, dz_dual, lddz,
+                         de, de_dual, dctx, R, B, L, C, accumulate);
       hipLaunchKernelGGL(attn_step_bwd_softmax_kernel<Dual>, dim3(B), dim3(256), 0, st, alpha, alpha_dual, de, de_dual, dP, R, B, L,
                          accumulate);
     } else {
-      hipLaunchKernelGGL(attn_step_bwd_ctx_kernel<float>, dim3(B, ls), dim3(256), (size_t)npass * C * sizeof(float), st, ctx, alpha,
-                         nullptr, dz, nullptr, lddz, de, nullptr, dctx, R, B, L, C, accumulate);
+      hipLaunchKernelGGL(attn_step_bwd_ctx_kernel<float>, dim3(B, r.ls), dim3(256), r.lds, st, ctx, alpha, nullptr, dz, nullptr, lddz,
+                         de, nullptr, dctx, R, B, L, C, accumulate);
       hipLaunchKernelGGL(attn_step_bwd_softmax_kernel<float>, dim3(B), dim3(256), 0, st, alpha, nullptr, de, nullptr, dP, R, B, L,
                          accumulate);
     }
     SGG_LAUNCH_CHECK("sgg_attn_step_bwd");
     return SGG_OK;
   }
-  if (alpha_dual) {
-    SGG_CHECK_ARG(dz_dual && de_dual, "sgg_attn_step_bwd: dual pointers missing");
-    const size_t smb = (size_t)npass * (C + 2 * L) * sizeof(Dual);
-    SGG_CHECK_ARG(smb <= 150 * 1024, "sgg_attn_step_bwd: L too large for LDS (%zu bytes)", smb);
-    hipLaunchKernelGGL(attn_step_bwd_kernel<Dual>, dim3(B), dim3(256), smb, st, ctx, alpha, alpha_dual, dz, dz_dual, lddz, de,
-                       de_dual, dP, dctx, R, B, L, C, accumulate);
+  if (r.dual) {
+    if ((rc = attn_allow_lds(attn_step_bwd_kernel<Dual>, r.lds, "sgg_attn_step_bwd"))) return rc;
+    hipLaunchKernelGGL(attn_step_bwd_kernel<Dual>, dim3(B), dim3(256), r.lds, st, ctx, alpha, alpha_dual, dz, dz_dual, lddz, de, de_dual,
+                       dP, dctx, R, B, L, C, accumulate);
   } else {
-    const size_t smb = (size_t)npass * (C + 2 * L) * sizeof(float);
-    hipLaunchKernelGGL(attn_step_bwd_kernel<float>, dim3(B), dim3(256), smb, st, ctx, alpha, nullptr, dz, nullptr, lddz, de,
-                       nullptr, dP, dctx, R, B, L, C, accumulate);
+    if ((rc = attn_allow_lds(attn_step_bwd_kernel<float>, r.lds, "sgg_attn_step_bwd"))) return rc;
+    hipLaunchKernelGGL(attn_step_bwd_kernel<float>, dim3(B), dim3(256), r.lds, st, ctx, alpha, nullptr, dz, nullptr, lddz, de, nullptr,
+                       dP, dctx, R, B, L, C, accumulate);
   }
   SGG_LAUNCH_CHECK("sgg_attn_step_bwd");
+  return SGG_OK;
+}
+
+// The kernels sgg_attn_step_fwd / _bwd launch for these scalars (dual: the *_dual pointers are given), in launch order, separated
+// by ';' (rocprofv3's spelling with spaces removed).  Same validation, same refusals as the launch.
+extern "C" int sgg_attn_step_fwd_symbol(int R, int B, int L, int C, int dual, char* buf, int buf_len) {
+  SGG_CHECK_ARG(buf && buf_len >= 96, "sgg_attn_step_fwd_symbol: the buffer must hold at least 96 bytes");
+  AttnFwdRoute r;
+  int rc = attn_fwd_route(R, B, L, C, dual != 0, &r);
+  if (rc) return rc;
+  if (r.rows) snprintf(buf, (size_t)buf_len, "attn_step_fwd_rows_kernel<%d>", r.tr);
+  else snprintf(buf, (size_t)buf_len, "attn_step_fwd_kernel<%s>", r.dual ? "Dual" : "float");
+  return SGG_OK;
+}
+extern "C" int sgg_attn_step_bwd_symbol(int R, int B, int L, int C, int dual, char* buf, int buf_len) {
+  SGG_CHECK_ARG(buf && buf_len >= 96, "sgg_attn_step_bwd_symbol: the buffer must hold at least 96 bytes");
+  AttnBwdRoute r;
+  int rc = attn_bwd_route(R, B, L, C, dual != 0, &r);
+  if (rc) return rc;
+  const char* t = r.dual ? "Dual" : "float";
+  if (r.ls > 1) snprintf(buf, (size_t)buf_len, "attn_step_bwd_ctx_kernel<%s>;attn_step_bwd_softmax_kernel<%s>", t, t);
+  else snprintf(buf, (size_t)buf_len, "attn_step_bwd_kernel<%s>", t);
   return SGG_OK;
 }
 

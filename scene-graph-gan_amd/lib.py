@@ -57,6 +57,9 @@ SIGNATURES = {
     "sgg_gemm_skinny_fwd": (_i, [_i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "sgg_gemm_skinny_dgrad": (_i, [_i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
     "sgg_gemm_skinny_wgrad": (_i, [_i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "sgg_gemm_skinny_symbol": (_i, [_i, _i, _i, _i, _vp, c_char_p, _i]),
+    "sgg_attn_step_fwd_symbol": (_i, [_i, _i, _i, _i, _i, c_char_p, _i]),
+    "sgg_attn_step_bwd_symbol": (_i, [_i, _i, _i, _i, _i, c_char_p, _i]),
     "sgg_layernorm_hwc_elu_bwd_sums": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "sgg_conv2d_nhwc_wgrad_c3_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "sgg_conv2d_nhwc_dgrad_c3": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -686,6 +689,24 @@ class HipKernels:
             rc = fn(M, N, K, _p(A), _ld(A), _p(Bm), _ld(Bm), _p(C), _ld(C), int(accumulate), _p(ws), ws.numel(),
                     self._stream())
         self._check(rc, ("sgg_gemm_skinny_fwd", "sgg_gemm_skinny_dgrad", "sgg_gemm_skinny_wgrad")[mode])
+
+    def _head_symbol(self, query, *args):
+        """The kernels of a head launch, in launch order and separated by ';', as the library's own routing reports them
+        (sgg_gemm_skinny_symbol / sgg_attn_step_fwd_symbol / _bwd_symbol: the launch's validation and route, scalars only)."""
+        buf = ctypes.create_string_buffer(96)
+        self._check(getattr(self.lib, query)(*args, buf, len(buf)), query)
+        return buf.value.decode()
+
+    def gemm_symbol(self, mode, M, N, K):
+        """(kernels, nsplit) of sgg_gemm_skinny_{fwd, dgrad, wgrad}[mode](M, N, K)."""
+        ns = c_int(0)
+        return self._head_symbol("sgg_gemm_skinny_symbol", mode, M, N, K, ctypes.addressof(ns)), ns.value
+
+    def attn_step_fwd_symbol(self, R, B, L, C, dual):
+        return self._head_symbol("sgg_attn_step_fwd_symbol", R, B, L, C, int(dual))
+
+    def attn_step_bwd_symbol(self, R, B, L, C, dual):
+        return self._head_symbol("sgg_attn_step_bwd_symbol", R, B, L, C, int(dual))
 
     def gemm_nn(self, A, Bm, C, bias=None, accumulate=False):
         """C[M,N] (+)= A[M,K] @ B[K,N] (+ bias)"""
