@@ -23,6 +23,7 @@ if _ROOT not in sys.path:
 import sgg_amd  # noqa: E402,F401
 from sgg_amd import grad  # noqa: E402
 from sgg_amd.api import NetworkHandle  # noqa: E402
+from sgg_amd.step import need_kernels  # noqa: E402
 
 
 class Discriminator(NetworkHandle):
@@ -44,18 +45,25 @@ class Discriminator(NetworkHandle):
         self._publish(ctx, st)
         return st.OUT[0]
 
-    def score_samples(self, input_triples, images):
+    def score_samples(self, input_triples, images, relax_tau=None):
         """Critic outputs of N triples per image on ONE encoder pass: input_triples [N, B, 3, vocab] (one-hots or generator
         logits, e.g. Generator.sample's output), images [B, S, S, 3] -> [N, B, 3, 1].  Row k*B + b reads image b; the returned
-        tensor is a view of the head's rows (the next call overwrites it)."""
+        tensor is a view of the head's rows (the next call overwrites it).
+        relax_tau = tau > 0: the critic of a run with a relaxed generator output - input_triples are logits and are replaced IN PLACE
+        by softmax(logits / tau) before the critic reads them (one launch, csrc/relax.hip; a contiguous input_triples is the
+        caller's own tensor: take its argmax first)."""
         net = self._ensure(images)
         B = int(images.shape[0])
         N = int(input_triples.shape[0])
         assert tuple(input_triples.shape) == (N, B, 3, self.vocab_size), input_triples.shape
+        rows = input_triples.contiguous().view(N * B, 3, self.vocab_size)
+        if relax_tau is not None:
+            need_kernels(net.K, "score_samples(relax_tau)", "relax_rows")
+            net.K.relax_rows(rows, float(relax_tau))
         ctx = net.trunk.forward(images.contiguous(), for_backward=False)
         net.head.precompute(ctx)
         st = net.head.sample_state(N * B)
-        net.head.forward(st, ctx, [input_triples.contiguous().view(N * B, 3, self.vocab_size)])
+        net.head.forward(st, ctx, [rows])
         self._publish(ctx, st)
         return st.OUT[0].view(N, B, 3, 1)
 

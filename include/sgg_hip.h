@@ -490,6 +490,25 @@ int sgg_xent_summary(const float* nll, const int* hit, int R, float* out4, void*
 int sgg_triple_logp(const float* logits, long long ld, const float* lse, int N, int nb, int V, const long long* gt,
                     const int* gt_count, int M, float* mix, float* mean, float* slot, int* status, void* stream);
 
+/* ---- relaxed generator output: softmax / Gumbel-softmax rows for the critic, and their gradient (csrc/relax.hip) ---------------
+ * The critic's fake rows as points of the probability simplex instead of raw decoder logits.  Neither entry point uses a workspace
+ * or a float atomic, and two calls give the same bits.  Rows are any 4-byte alignment; element offsets are 64-bit.  R >= 1,
+ * 1 <= V <= 2^21, tau finite and > 0; anything else is refused without a launch.
+ * sgg_relax_rows: y[r][j] = exp(z_j - max z) / sum_k exp(z_k - max z) with z = (x[r] + g) / tau; x rows ldx >= V apart, y rows
+ *   ldy >= V apart.  y may BE x (same pointer, then ldy == ldx): the row is relaxed in place.  gumbel = 0: g = 0.  gumbel = 1: g is
+ *   drawn in the kernel, a pure function of (seed, draw, r, j): Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ *   (j >> 2, r, draw & 0xffffffff, draw >> 32); element j takes output word w = out[j & 3]; u = ((w >> 9) + 0.5) * 2^-23, exact in
+ *   fp32 and strictly inside (0, 1); g = -log(-log u).  u_out (optional, gumbel = 1 only, rows ldu >= V apart, a buffer of its own)
+ *   receives u.  Finite x is a precondition.
+ * sgg_relax_rows_bwd: dx[r][j] = (scale / tau) * y_j * (dy_j - sum_k y_k dy_k) - the gradient of scale * <dy, y> by x for y of
+ *   sgg_relax_rows, with either value of gumbel; it needs neither x nor the noise.  dx may BE dy (then lddx == lddy), not y.
+ * V <= 1024: one wave per row, the row in registers; above: one workgroup per row, a reduction pass and a pass that re-reads the
+ * row and writes it. */
+int sgg_relax_rows(const float* x, long long ldx, int R, int V, float tau, int gumbel, unsigned long long seed, unsigned long long draw,
+                   float* y, long long ldy, float* u_out, long long ldu, void* stream);
+int sgg_relax_rows_bwd(const float* y, long long ldy, const float* dy, long long lddy, int R, int V, float tau, float scale, float* dx,
+                       long long lddx, void* stream);
+
 /* ---- training diagnostics: per-tensor norms and non-finite counts of a network's arenas (csrc/stats.hip) ----------------------
  * One read-only streaming pass over params, grads, m and v: fp32 arenas of ONE layout, every tensor 16-byte aligned and rounded up
  * to 4 elements (the arena ends on such a boundary), as sgg_adam_tf_multi takes them.

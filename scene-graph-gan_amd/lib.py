@@ -13,14 +13,14 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_ulonglong, c_void_p
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsgg_hip.so")
 
-_vp, _i, _f, _sz, _ll = c_void_p, c_int, c_float, c_size_t, c_longlong
+_vp, _i, _f, _sz, _ll, _ull = c_void_p, c_int, c_float, c_size_t, c_longlong, c_ulonglong
 
 # name -> (restype, argtypes); must list every symbol declared in include/sgg_hip.h
 SIGNATURES = {
@@ -97,6 +97,8 @@ SIGNATURES = {
     "sgg_softmax_xent": (_i, [_vp, _ll, _i, _i, _vp, _f, _i, _vp, _ll, _vp, _vp, _vp, _vp]),
     "sgg_xent_summary": (_i, [_vp, _vp, _i, _vp, _vp]),
     "sgg_triple_logp": (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sgg_relax_rows": (_i, [_vp, _ll, _i, _i, _f, _i, _ull, _ull, _vp, _ll, _vp, _ll, _vp]),
+    "sgg_relax_rows_bwd": (_i, [_vp, _ll, _vp, _ll, _i, _i, _f, _f, _vp, _ll, _vp]),
     "sgg_arena_stats_chunk": (_i, []),
     "sgg_arena_stats_nstat": (_i, []),
     "sgg_arena_stats_workspace_bytes": (_sz, [_i]),
@@ -1190,6 +1192,44 @@ class HipKernels:
         self._check(self.lib.sgg_triple_logp(_p(x), ld, _p(lse), N, nb, V, _p(gt), _p(gt_count), M, _p(res["mix"]), _p(res["mean"]),
                                              _p(res["slot"]), _p(res["status"]), self._stream()), "sgg_triple_logp")
         return res
+
+    # -- relaxed generator output (csrc/relax.hip) ---------------------------------------------------------------
+    def relax_rows(self, x, tau, y=None, gumbel=False, seed=0, draw=0, u_out=None):
+        """y = softmax((x + g) / tau) row by row (csrc/relax.hip; include/sgg_hip.h): x fp32 [..., V] (R rows one stride apart), y of
+        the same rows with its own stride (default: x itself, relaxed in place).  gumbel: g = -log(-log u) drawn in the kernel from
+        Philox4x32-10 keyed by the 64-bit `seed`, counter (j >> 2, row, draw): a pure function of (seed, draw, row, j); else g = 0.
+        u_out (gumbel only): receives u.  Returns y."""
+        if y is None:
+            y = x
+        self._dev(x, y, u_out)
+        xv, ldx = self._xent_rows(x, "x")
+        yv, ldy = self._xent_rows(y, "y")
+        R, V = int(xv.shape[0]), int(xv.shape[1])
+        assert tuple(yv.shape) == (R, V), "y must have x's rows"
+        uv, ldu = None, 0
+        if u_out is not None:
+            uv, ldu = self._xent_rows(u_out, "u_out")
+            assert tuple(uv.shape) == (R, V), "u_out must have x's rows"
+        sym = "relax_rows_%s_kernel<%s>" % ("resident" if V <= 1024 else "stream", "true" if gumbel else "false")
+        self._check(self._timed(sym, 0.0, lambda: self.lib.sgg_relax_rows(
+            _p(xv), ldx, R, V, float(tau), int(bool(gumbel)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, _p(yv), ldy,
+            _p(uv), ldu, self._stream()), 4.0 * R * V * 2), "sgg_relax_rows")
+        return y
+
+    def relax_rows_bwd(self, y, dy, tau, scale=1.0, dx=None):
+        """dx = (scale / tau) * y * (dy - sum_k y_k dy_k) row by row: the gradient of scale * <dy, y> by the x of relax_rows (either
+        mode; needs neither x nor the noise).  y, dy, dx fp32 [..., V], each with its own row stride; default dx: dy, in place."""
+        if dx is None:
+            dx = dy
+        self._dev(y, dy, dx)
+        yv, ldy = self._xent_rows(y, "y")
+        gv, lddy = self._xent_rows(dy, "dy")
+        dv, lddx = self._xent_rows(dx, "dx")
+        R, V = int(yv.shape[0]), int(yv.shape[1])
+        assert tuple(gv.shape) == (R, V) and tuple(dv.shape) == (R, V), "dy and dx must have y's rows"
+        self._check(self._timed("relax_bwd_%s_kernel" % ("resident" if V <= 1024 else "stream"), 0.0, lambda: self.lib.sgg_relax_rows_bwd(
+            _p(yv), ldy, _p(gv), lddy, R, V, float(tau), float(scale), _p(dv), lddx, self._stream()), 4.0 * R * V * 3), "sgg_relax_rows_bwd")
+        return dx
 
     def fill(self, t, value):
         self._dev(t)

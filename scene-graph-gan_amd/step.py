@@ -363,6 +363,8 @@ class GanStep:
         # accuracy, valid rows) of the last cross-entropy; the per-row buffers behind it are allocated at the first use (_xent_rows)
         self.mle_losses = z(4)
         self._xent_buf = None
+        # relaxed generator output (set_relaxation; csrc/relax.hip): None = the critic sees the raw decoder logits
+        self._relax, self._relax_buf = None, None
         # (option side_priority: priority of the side streams - everything on them is off the critical chain of the main stream)
         prio = int(option(K, "side_priority"))
         self.side = torch.cuda.Stream(device=dev, priority=prio) if (overlap_streams and dev.type == "cuda") else None
@@ -491,10 +493,42 @@ class GanStep:
         if self.side is not None:
             torch.cuda.current_stream().wait_stream(self.side)
 
-    def critic_step(self, images, labels, noise, alpha, micro=None):
+    # ---- relaxed generator output (csrc/relax.hip) --------------------------------------------------------
+    RELAX_MODES = ("logits", "softmax", "gumbel")
+
+    def set_relaxation(self, mode, tau=1.0, seed=0):
+        """What the critic sees of G's decoder rows x: "logits" (default) = x itself, nothing launched; "softmax" = y = softmax(x / tau);
+        "gumbel" = y = softmax((x + g) / tau) with g drawn on the device from (seed, draw, row, column) - `draw` is the 64-bit number
+        each step takes.  The generator's update differentiates through y (one launch in front of D, one behind the critic's gradient
+        of its input); the critic's update treats y as a constant, as it treats the logits.  tau may be changed between steps by
+        another call (a schedule); the [B, 3, V] buffer of the generator update is allocated the first time a mode is on."""
+        if mode not in self.RELAX_MODES:
+            raise ValueError("generator_output must be one of %s (got %r)" % (", ".join(self.RELAX_MODES), mode))
+        if mode == "logits":
+            self._relax = None
+            return
+        tau = float(tau)
+        if not (math.isfinite(tau) and tau > 0.0):
+            raise ValueError("the relaxation's temperature must be a finite number > 0 (got %r)" % tau)
+        need_kernels(self.K, "generator_output=%s" % mode, "relax_rows", "relax_rows_bwd")
+        self._relax = {"mode": mode, "tau": tau, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF}
+        if self._relax_buf is None:
+            self._relax_buf = torch.zeros_like(self.TRI[:self.B])
+
+    relaxation = property(lambda self: None if self._relax is None else dict(self._relax))
+
+    def _relax_fwd(self, logits, out, draw):
+        """out = the relaxed rows of `logits` [B,3,V] in the mode in force (one launch)."""
+        rx = self._relax
+        gumbel = rx["mode"] == "gumbel"
+        self.K.relax_rows(logits, rx["tau"], y=out, gumbel=gumbel, seed=rx["seed"], draw=(int(draw or 0) if gumbel else 0))
+        return out
+
+    def critic_step(self, images, labels, noise, alpha, micro=None, draw=None):
         """One disc_train_op (train.py:365). labels int64 [B,3]; noise [B,512]; alpha [B]. Returns self.d_losses
         = (disc_cost, wasserstein term, gradient penalty, mean D(fake)) as a device tensor.
-        micro = (k, N): this is micro-batch k of an update over N (Network.end_micro_batch); None = (0, 1), the whole update."""
+        micro = (k, N): this is micro-batch k of an update over N (Network.end_micro_batch); None = (0, 1), the whole update.
+        draw: the 64-bit number of this launch's Gumbel noise (set_relaxation; ignored unless the mode is "gumbel")."""
         K, B, V, D = self.K, self.B, self.V, self.D
         mk, mN = micro if micro is not None else (0, 1)
         if mN > 1:
@@ -519,7 +553,10 @@ class GanStep:
             self._ev_g_free.record()
             self._ev_g_images = (images, images._version, (self.G.arena.version, self.G.adam_t), self.G.data_passes)
         self._join_side()
-        fake_rows.copy_(gst.OUT[0])
+        if self._relax is None:
+            fake_rows.copy_(gst.OUT[0])
+        else:
+            self._relax_fwd(gst.OUT[0], fake_rows, draw)      # (the launch writes y where the copy wrote the logits)
         K.onehot(labels, real_rows)
         K.interpolate(real_rows, fake_rows, alpha, hat_rows)
         # ---- first-order pass on the 3B-row super-batch ------------------------------------------------
@@ -551,7 +588,7 @@ class GanStep:
         D.end_micro_batch(mk, mN, self.reducer)
         return self.d_losses
 
-    def critic_loss(self, images, labels, noise, alpha, out=None):
+    def critic_loss(self, images, labels, noise, alpha, out=None, draw=None):
         """disc_cost of a minibatch WITHOUT an update: what `sess.run(self.disc_cost, feed_dict = {handle: val_handle})` evaluates
         for the validation-loss early stop (train.py:375-377).  Same forward as critic_step; the head backward runs only as far as
         g = d sum(D(x_hat)) / d x_hat needs it (no parameter gradient is touched, R_w = 0), no encoder backward, no Adam.
@@ -566,7 +603,10 @@ class GanStep:
         self.flush()
         ctx = self._encode(D, images, False)
         gst, _ = self.generator_forward(images, noise, for_backward=False)
-        fake_rows.copy_(gst.OUT[0])
+        if self._relax is None:
+            fake_rows.copy_(gst.OUT[0])
+        else:
+            self._relax_fwd(gst.OUT[0], fake_rows, draw)
         K.onehot(labels, real_rows)
         K.interpolate(real_rows, fake_rows, alpha, hat_rows)
         st = D.head.state(1, 3 * B)
@@ -581,11 +621,14 @@ class GanStep:
         K.wgan_losses(st.OUT[0].view(3 * B, T_STEPS), self.pen, self.lam, B, T_STEPS, True, out)
         return out
 
-    def generator_step(self, images, noise, micro=None, labels=None, mle_weight=0.0):
+    def generator_step(self, images, noise, micro=None, labels=None, mle_weight=0.0, draw=None):
         """One gen_train_op (train.py:368). Returns self.g_losses; g_losses[3] = mean D(fake) = -gen_cost.  micro: as critic_step.
         mle_weight = w > 0 (with labels int64 [B,3]): the auxiliary likelihood term, gen_cost' = -mean D(G(x)) + w * xent with xent
         the loss of pretrain_step - one softmax_xent launch that ADDS w / B * (softmax - onehot) to the critic's gradient of the fake
-        logits, and the summary into self.mle_losses.  w = 0 (default): nothing of it is launched."""
+        logits, and the summary into self.mle_losses.  w = 0 (default): nothing of it is launched.
+        With a relaxation on (set_relaxation) D's input is y = relax(logits) in a buffer of its own, and the critic's gradient of y is
+        turned into the gradient of the logits in place (relax_rows_bwd) before the likelihood term - a function of the logits - adds
+        to it.  draw: as critic_step."""
         K, B, G, D = self.K, self.B, self.G, self.D
         mk, mN = micro if micro is not None else (0, 1)
         mle_weight = float(mle_weight)
@@ -610,14 +653,17 @@ class GanStep:
             ctx = self._d_encoder_on_side_stream(images, zero_grads=False, for_backward=False)   # only D's head is differentiated here
         fake = gst.OUT[0]
         self._join_side()
+        d_in = fake if self._relax is None else self._relax_fwd(fake, self._relax_buf, draw)
         st = D.head.state(1, B, "g")
-        D.head.forward(st, ctx, [fake])
+        D.head.forward(st, ctx, [d_in])
         K.wgan_losses(st.OUT[0].view(B, T_STEPS), None, 0.0, B, T_STEPS, False, self.g_losses)
         K.fill(st.dOUT[0], -1.0 / (B * T_STEPS))  # gen_cost = -mean(D(G(x)))
-        D.head.backward(st, ctx, [fake], R_w=0)
+        D.head.backward(st, ctx, [d_in], R_w=0)
         ind = D.head.in_dim
         for t in range(T_STEPS):
             K.gemm_nt(st.dXH[t][0][:, FEAT_C:ind], D.head.W_emb, gst.dOUT[0][:, t, :])
+        if self._relax is not None:
+            K.relax_rows_bwd(d_in, gst.dOUT[0], self._relax["tau"])        # d cost / d y -> d cost / d logits, in place
         if mle_weight > 0.0:
             self._xent(fake, labels, mle_weight / B, gst.dOUT[0], accumulate=True, out=self.mle_losses)
             self._sum_losses("m", self.mle_losses, mk, mN)
@@ -786,33 +832,36 @@ class GanStep:
             out["guard"] = self.guard_reports()
         return out
 
-    def train_iteration(self, images, labels, noises, alphas, critic_iters=1, reuse_g_encoder=False, mle_weight=0.0):
+    def train_iteration(self, images, labels, noises, alphas, critic_iters=1, reuse_g_encoder=False, mle_weight=0.0, draws=None):
         """Loop body of train.py:362-368: critic_iters critic updates then one generator update on one minibatch,
         fresh noise / alpha per update.  reuse_g_encoder: G's encoder forward once per iteration (generator_forward).
-        mle_weight > 0: the generator update carries the auxiliary likelihood term on `labels` (generator_step)."""
+        mle_weight > 0: the generator update carries the auxiliary likelihood term on `labels` (generator_step).
+        draws[i]: the Gumbel draw number of update i (critic updates first, the generator update last; set_relaxation)."""
         mle = {"labels": labels, "mle_weight": mle_weight} if mle_weight > 0.0 else {}
+        dr = (lambda i: {}) if draws is None else (lambda i: {"draw": draws[i]})
         with self.iteration(reuse_g_encoder):
             for i in range(critic_iters):
-                self.critic_step(images, labels, noises[i], alphas[i])
-            self.generator_step(images, noises[critic_iters], **mle)
+                self.critic_step(images, labels, noises[i], alphas[i], **dr(i))
+            self.generator_step(images, noises[critic_iters], **mle, **dr(critic_iters))
 
-    def train_iteration_accumulated(self, batches, noises, alphas, critic_iters=1, reuse_g_encoder=False, mle_weight=0.0):
+    def train_iteration_accumulated(self, batches, noises, alphas, critic_iters=1, reuse_g_encoder=False, mle_weight=0.0, draws=None):
         """train_iteration with every update taken from N = len(batches) micro-batches of B rows: the update of the N * B rows.
         batches: [(images, labels)] * N, all resident on the device for the whole iteration (every update reads all of them);
         noises[i][k] / alphas[i][k]: update i (critic updates first, the generator update last), micro-batch k.  Order: per critic
         update all N micro-batches, then ONE optimiser step; then the generator update the same way.  reuse_g_encoder: G's encoder
-        runs 2 N times per iteration instead of N * (critic_iters + 1) (generator_forward).  N = 1 is train_iteration."""
+        runs 2 N times per iteration instead of N * (critic_iters + 1) (generator_forward).  N = 1 is train_iteration.  draws[i][k]: as noises (train_iteration)."""
         N = len(batches)
         if N == 1:
             return self.train_iteration(batches[0][0], batches[0][1], [n[0] for n in noises], [a[0] for a in alphas],
-                                        critic_iters, reuse_g_encoder, mle_weight)
+                                        critic_iters, reuse_g_encoder, mle_weight, None if draws is None else [d[0] for d in draws])
+        dr = (lambda i, k: {}) if draws is None else (lambda i, k: {"draw": draws[i][k]})
         with self.iteration(reuse_g_encoder):
             for i in range(critic_iters):
                 for k, (images, labels) in enumerate(batches):
-                    self.critic_step(images, labels, noises[i][k], alphas[i][k], micro=(k, N))
+                    self.critic_step(images, labels, noises[i][k], alphas[i][k], micro=(k, N), **dr(i, k))
             for k, (images, labels) in enumerate(batches):
                 mle = {"labels": labels, "mle_weight": mle_weight} if mle_weight > 0.0 else {}
-                self.generator_step(images, noises[critic_iters][k], micro=(k, N), **mle)
+                self.generator_step(images, noises[critic_iters][k], micro=(k, N), **mle, **dr(critic_iters, k))
 
     @contextlib.contextmanager
     def iteration(self, reuse_g_encoder=False):

@@ -9,6 +9,7 @@
     python train.py --clip_grad_norm 5,50 --skip_nonfinite ...             # clip D / G updates by global norm, drop non-finite ones
     python train.py --pretrain_iterations 2000 --mle_weight 0.1 --validate_nll ...  # maximum-likelihood warm start of G, held-out NLL
     python train.py --checkpoints_dir ckpt --likelihood_out nll.json       # NLL of the test split's true triples under G
+    python train.py --generator_output gumbel --relax_tau 2,0.5,20000 ...  # the critic sees Gumbel-softmax rows, tau annealed
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -70,6 +71,49 @@ def micro_batch_ids(it, N):
     return range(it * N, (it + 1) * N)
 
 
+RELAX_MODES = GanStep.RELAX_MODES
+
+
+def parse_relax_tau(spec):
+    """--relax_tau: "T" or "T0,T1,N" (or a number, or three of them) -> (T0, T1, N), the temperature schedule
+    tau(it) = T0 * (T1 / T0) ^ (min(it, N) / N); a constant T is (T, T, 0).  T0, T1 finite and > 0, N a whole number >= 0."""
+    parts = [p for p in spec.split(",")] if isinstance(spec, str) else (list(spec) if isinstance(spec, (tuple, list)) else [spec])
+    try:
+        if len(parts) == 1:
+            t0 = t1 = float(parts[0])
+            n = 0
+        elif len(parts) == 3:
+            t0, t1, n = float(parts[0]), float(parts[1]), int(parts[2])
+            if n != float(parts[2]):
+                raise ValueError
+        else:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("relax_tau takes T or T0,T1,N (got %r)" % (spec,))
+    if not (np.isfinite(t0) and np.isfinite(t1) and t0 > 0.0 and t1 > 0.0 and n >= 0) or (n == 0 and t0 != t1):
+        raise ValueError("relax_tau: temperatures must be finite and > 0, N >= 1 for a schedule (got %r)" % (spec,))
+    return (t0, t1, n)
+
+
+def relax_tau_at(spec, it):
+    """tau(it) of the schedule (T0, T1, N), in double on the host."""
+    t0, t1, n = spec
+    if n == 0:
+        return float(t0)
+    return float(t0) * (float(t1) / float(t0)) ** (min(int(it), n) / float(n))
+
+
+def relax_draw(it, update, micro, critic_iters, accumulate):
+    """The 64-bit Gumbel draw number of one relaxation launch of training: a function of the iteration, the update within it (critic
+    updates first, the generator update last) and the micro-batch - a stopped and resumed run repeats its draws with nothing saved."""
+    return ((int(it) * (int(critic_iters) + 1) + int(update)) * int(accumulate) + int(micro)) & 0x7FFFFFFFFFFFFFFF
+
+
+def relax_val_draw(k):
+    """... and of validation number k: the top bit set, so that no training launch shares it."""
+    return (1 << 63) | (int(k) & 0x7FFFFFFFFFFFFFFF)
+
+
 class SceneGraphGAN(object):
 
     ############################################################
@@ -79,7 +123,7 @@ class SceneGraphGAN(object):
                  path_to_image_means, path_to_image_stds, critic_iters, batch_size, lambda_, resume,
                  synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True,
                  ema_decay=0.0, eval_live=False, accumulate=1, clip_grad_norm=0.0, skip_nonfinite=False,
-                 pretrain_iterations=0, mle_weight=0.0, validate_nll=False):
+                 pretrain_iterations=0, mle_weight=0.0, validate_nll=False, generator_output=None, relax_tau=None):
         # Hyperparameters (train.py:26-32)
         self.CRITIC_ITERS = int(critic_iters)
         self.BATCH_SIZE = int(batch_size)
@@ -127,6 +171,16 @@ class SceneGraphGAN(object):
         if not (0.0 <= self.mle_weight < float("inf")):
             raise ValueError("mle_weight must be a finite number >= 0 (got %r)" % (mle_weight,))
         self.validate_nll = bool(validate_nll)
+        # generator_output = "softmax" | "gumbel": the critic sees y = softmax((logits [+ Gumbel noise]) / tau) instead of G's raw
+        # decoder logits, and the generator's update differentiates through y (GanStep.set_relaxation); relax_tau = T or (T0, T1, N),
+        # tau(it) = T0 (T1 / T0)^(min(it, N) / N).  None = not given: a fresh run is "logits" at tau 1 (nothing launched, nothing
+        # written), a resumed run or an evaluation takes both from the checkpoint; a given value that contradicts the checkpoint is
+        # an error (_loadModel).
+        if generator_output is not None and generator_output not in RELAX_MODES:
+            raise ValueError("generator_output must be one of %s (got %r)" % (", ".join(RELAX_MODES), generator_output))
+        self._relax_flags = (generator_output, None if relax_tau is None else parse_relax_tau(relax_tau))
+        self.relax_mode = generator_output or "logits"
+        self.relax_tau = self._relax_flags[1] or (1.0, 1.0, 0)
         self.shuffle_buffer = bool(shuffle_buffer)      # tf.data shuffle(buffer_size = 10 * batch) on the repeated stream (train.py:176-179)
         self.checkpoints_dir, self.summaries_dir = checkpoints_dir, summaries_dir
         self.rank, self.world, local = dpmod.init_from_env()
@@ -264,11 +318,37 @@ class SceneGraphGAN(object):
         alpha = torch.rand((VB,), generator=gen).to(self.device)
         self._ensure_val_step(images)
         self.step.flush()           # (a deferred optimiser step of the training networks changes the weights validation reads)
-        loss = self.val_step.critic_loss(images, labels, noise, alpha)[0:1].clone()
+        relax = {}
+        if self.relaxed:            # the training relaxation at the temperature of the iteration just run, draws keyed on k
+            self._set_relaxation(self.val_step, max(self.itr - 1, 0))
+            relax = {"draw": relax_val_draw(k)}
+        loss = self.val_step.critic_loss(images, labels, noise, alpha, **relax)[0:1].clone()
         if self.world > 1:
             torch.distributed.all_reduce(loss)
             loss /= self.world
         return float(loss.item())
+
+    # ---- relaxed generator output (GanStep.set_relaxation, csrc/relax.hip) ------------------------------------
+    relaxed = property(lambda self: self.relax_mode != "logits")
+
+    def _relax_seed(self):
+        """The 64-bit key of the Gumbel noise: --seed in the high word, the rank in the low one."""
+        return ((int(self.seed) & 0xFFFFFFFF) << 32) | (int(self.rank) & 0xFFFFFFFF)
+
+    def _set_relaxation(self, step, it):
+        """Put `step` into the run's mode at the temperature of iteration `it`; returns that temperature."""
+        tau = relax_tau_at(self.relax_tau, it)
+        step.set_relaxation(self.relax_mode, tau, self._relax_seed())
+        return tau
+
+    def _eval_relax(self):
+        """What the critic is shown at evaluation: None (logits) or the temperature of softmax(logits / tau) at the checkpoint's
+        iteration - in both modes without Gumbel noise (the samples' diversity comes from the noise vector)."""
+        return relax_tau_at(self.relax_tau, self.itr) if self.relaxed else None
+
+    def _relax_label(self):
+        """The "generator_output" entry of an evaluation's JSON output."""
+        return {"mode": self.relax_mode, "tau": relax_tau_at(self.relax_tau, self.itr)}
 
     def _ensure_val_step(self, images):
         if self.val_step is None:
@@ -318,6 +398,8 @@ class SceneGraphGAN(object):
                 ck["accumulate"] = self.ACCUMULATE
             if self.PRETRAIN > 0:           # (only a run with a pretraining phase writes the key)
                 ck["pretrain_iterations"] = self.PRETRAIN
+            if self.relaxed:                # (only a run with a relaxed generator output writes the key)
+                ck["generator_output"] = {"mode": self.relax_mode, "tau": list(self.relax_tau)}
             if self.step.D.has_guard or self.step.G.has_guard:      # (only a guarded run writes the key: the clipped / skipped counts)
                 ck["guard"] = {n: net.guard_state() for n, net in (("D", self.step.D), ("G", self.step.G)) if net.has_guard}
             if self.step.G.has_average:     # (only a run that averages writes these keys: without it the checkpoint is what it was)
@@ -326,12 +408,22 @@ class SceneGraphGAN(object):
             # uninterrupted run, and a run with a pretraining phase, stopped and resumed, ends on the same weights (single process
             # only: every rank draws from a stream of its own, rank 0 writes)
             gen = getattr(self, "_noise_gen", None)
-            if (self.step.G.has_average or self.PRETRAIN > 0) and gen is not None and self.world == 1:
+            if (self.step.G.has_average or self.PRETRAIN > 0 or self.relaxed) and gen is not None and self.world == 1:
                 ck["noise_rng"] = gen.get_state()
             torch.save(ck, self._ckpt_path())
 
     def _loadModel(self, for_training=False):
         ck = torch.load(self._ckpt_path(), map_location="cpu")
+        # the generator output the run was trained with is the checkpoint's: a flag that says otherwise is an error, before anything is loaded
+        saved_relax = ck.get("generator_output") or {"mode": "logits", "tau": [1.0, 1.0, 0]}
+        saved_mode, saved_tau = saved_relax["mode"], (float(saved_relax["tau"][0]), float(saved_relax["tau"][1]), int(saved_relax["tau"][2]))
+        flag_mode, flag_tau = self._relax_flags
+        if flag_mode is not None and flag_mode != saved_mode:
+            raise ValueError("--generator_output %s contradicts the checkpoint, which was trained with %s" % (flag_mode, saved_mode))
+        if flag_tau is not None and saved_mode != "logits" and flag_tau != saved_tau:
+            raise ValueError("--relax_tau %s contradicts the checkpoint's %s" % (",".join(str(x) for x in flag_tau),
+                                                                                 ",".join(str(x) for x in saved_tau)))
+        self.relax_mode, self.relax_tau = saved_mode, saved_tau
         self.g.load_state_dict(ck["G"])
         self.d.load_state_dict(ck["D"])
         for net, key in ((self.step.G, "G_adam"), (self.step.D, "D_adam")):
@@ -365,7 +457,8 @@ class SceneGraphGAN(object):
             print("resuming with --pretrain_iterations %d a run saved with %d: iterations below %d are pretraining iterations from "
                   "here on (the run stands at iteration %d)" % (self.PRETRAIN, int(ck.get("pretrain_iterations", 0)), self.PRETRAIN, self.itr))
         self._resumed_val = ck.get("val")
-        self._resumed_rng = ck.get("noise_rng") if (for_training and (self.ema_decay > 0.0 or self.PRETRAIN > 0) and self.world == 1) else None
+        self._resumed_rng = ck.get("noise_rng") if (for_training and (self.ema_decay > 0.0 or self.PRETRAIN > 0 or self.relaxed)
+                                                    and self.world == 1) else None
 
     @property
     def evaluates_average(self):
@@ -419,6 +512,8 @@ class SceneGraphGAN(object):
                 if i < C:
                     alphas[i].append(torch.rand((B,), generator=gen).to(self.device))
         mle = {"mle_weight": self.mle_weight} if self.mle_weight > 0.0 else {}
+        if self.relax_mode == "gumbel":
+            mle["draws"] = [[relax_draw(self.itr, i, k, C, N) for k in range(N)] for i in range(C + 1)]
         self.step.train_iteration_accumulated(batches, noises, alphas[:C], critic_iters=C, reuse_g_encoder=self.reuse_g_encoder, **mle)
 
     def load_checkpoint(self):
@@ -483,6 +578,10 @@ class SceneGraphGAN(object):
                 # every update of an iteration sees the same minibatch (train.py:175-190) and G's weights change only at its end: G's
                 # encoder runs once per iteration (exact; 10 of 11 encoder forwards of G saved at CRITIC_ITERS = 10)
                 pre = self.itr < self.PRETRAIN          # a pretraining iteration: one maximum-likelihood update of G, no critic update
+                C = self.CRITIC_ITERS
+                # relaxed generator output: this iteration's temperature, and per launch a draw number made of (itr, update, micro-batch)
+                tau = self._set_relaxation(self.step, self.itr) if (self.relaxed and not pre) else None
+                draw = (lambda i: {"draw": relax_draw(self.itr, i, 0, C, 1)}) if self.relax_mode == "gumbel" else (lambda i: {})
                 if pre:
                     for k, (im, lb) in enumerate(batches if N > 1 else [(images, labels)]):
                         noise = torch.randn((B, 512), generator=gen).to(self.device)    # one fresh draw per micro-batch
@@ -491,15 +590,15 @@ class SceneGraphGAN(object):
                     self._accumulated_iteration(batches, gen)
                 else:
                     with self.step.iteration(reuse_g_encoder=self.reuse_g_encoder):
-                        for _ in range(self.CRITIC_ITERS):                              # train.py:364-365
+                        for i in range(C):                                              # train.py:364-365
                             noise = torch.randn((B, 512), generator=gen).to(self.device)
                             alpha = torch.rand((B,), generator=gen).to(self.device)
-                            self.step.critic_step(images, labels, noise, alpha)
+                            self.step.critic_step(images, labels, noise, alpha, **draw(i))
                         noise = torch.randn((B, 512), generator=gen).to(self.device)
                         if self.mle_weight > 0.0:
-                            self.step.generator_step(images, noise, labels=labels, mle_weight=self.mle_weight)
+                            self.step.generator_step(images, noise, labels=labels, mle_weight=self.mle_weight, **draw(C))
                         else:
-                            self.step.generator_step(images, noise)                     # train.py:368
+                            self.step.generator_step(images, noise, **draw(C))          # train.py:368
                 itr = self.itr                                                          # the reference's 0-based loop variable
                 self.itr += 1
                 diag = self.step.diagnostics(generator_only=pre) if report else None
@@ -519,6 +618,8 @@ class SceneGraphGAN(object):
                         rec = {"itr": self.itr, "disc_loss": d[0], "gen_loss": -g[3], "gp": d[2], "triples_per_s": rate}
                         if self.mle_weight > 0.0:
                             rec.update(mle)
+                        if tau is not None:
+                            rec["relax"] = {"mode": self.relax_mode, "tau": tau}
                     if N > 1:
                         rec["accumulate"] = N
                     if self.guarded:        # the records of each network's last update and the clipped / skipped counts so far
@@ -643,6 +744,7 @@ class SceneGraphGAN(object):
 
         gen = torch.Generator().manual_seed(self.seed + 123)
         toks = torch.empty((n_samples, nb, 3), dtype=torch.int64, device=self.device)
+        relax = {"relax_tau": self._eval_relax()} if self.relaxed else {}      # the critic scores what it was trained on
         r50, r100, details = [], [], []
         try:
             pending = fetch(0) if items else None
@@ -657,7 +759,7 @@ class SceneGraphGAN(object):
                         noise[p * TB:(p + 1) * TB, j] = torch.randn((TB, 512), generator=gen)
                 logits = self.g.sample(images, n_samples, noise.to(self.device))
                 K.argmax_rows(logits, toks.view(-1))
-                d = self.d.score_samples(logits, images)
+                d = self.d.score_samples(logits, images, **relax)   # (relaxed: in place on the logits, behind the argmax)
                 tok_h, d_h = toks.cpu().numpy(), d.cpu().numpy()
                 score_h = d_h.mean(axis=2).reshape(n_samples, nb)
                 for j in range(n):
@@ -674,8 +776,13 @@ class SceneGraphGAN(object):
         if self.rank == 0 and out_path:
             with open(out_path, "w") as f:
                 f.write("{}\n{}\n# ordering: {}\n".format(res[0], res[1], ordering))
+                if self.relaxed:
+                    f.write("# generator_output: {}\n".format(json.dumps(self._relax_label())))
         if self.rank == 0:
-            print({"R@50": res[0], "R@100": res[1], "ordering": ordering, "images": len(items), "samples_per_image": n_samples})
+            summary = {"R@50": res[0], "R@100": res[1], "ordering": ordering, "images": len(items), "samples_per_image": n_samples}
+            if self.relaxed:
+                summary["generator_output"] = self._relax_label()
+            print(summary)
         return (res, details) if return_details else res
 
     def sample_triples(self, images, noise=None):
@@ -827,10 +934,11 @@ class SceneGraphGAN(object):
         results."""
         V = len(self.vocab)
         toks = torch.empty((N, nb, 3), dtype=torch.int64, device=self.device)
+        relax = {"relax_tau": self._eval_relax()} if self.relaxed else {}      # the critic scores what it was trained on
         with contextlib.closing(self._sample_batches(items, N, nb)) as batches:
             for i0, n, images, logits in batches:
                 K.argmax_rows(logits, toks.view(-1))
-                d = self.d.score_samples(logits, images)
+                d = self.d.score_samples(logits, images, **relax)   # (relaxed: in place on the logits, behind the argmax)
                 K.rank_triples(toks, d.view(N, nb, 3), top_k, descending=descending, vocab=V, out=out)
                 yield i0, n
 
@@ -944,6 +1052,8 @@ class SceneGraphGAN(object):
             index["generator_weights"] = "ema"
         if decode == "kbest":
             index["decode"] = "kbest"
+        elif self.relaxed:                  # (the critic ranked softmax(logits / tau); K-best decoding does not run it)
+            index["generator_output"] = self._relax_label()
         with open(os.path.join(out_dir, "index.json"), "w") as f:
             json.dump(index, f, indent=1)
         if self.rank == 0:
@@ -1063,6 +1173,8 @@ class SceneGraphGAN(object):
             res["generator_weights"] = "ema"
         if kbest:
             res["decode"] = "kbest"
+        elif self.relaxed:
+            res["generator_output"] = self._relax_label()
         if self.rank == 0 and out_path:
             with open(out_path, "w") as f:
                 json.dump(res, f, indent=1)
@@ -1244,6 +1356,18 @@ def build_parser():
                         help="whenever validation runs, also log the held-out negative log-likelihood of the validation batch's true "
                              "tokens under the generator (val_nll_token, val_token_acc, val_triple_acc); its noise comes from a "
                              "generator of its own, so val_disc_loss keeps its bits")
+    parser.add_argument("--generator_output", default=None, choices=list(RELAX_MODES),
+                        help="what the critic is shown of the generator's decoder rows x: logits = x itself; softmax = "
+                             "y = softmax(x / tau); gumbel = y = softmax((x + g) / tau) with Gumbel noise g drawn on the device from "
+                             "--seed, the rank and (iteration, update, micro-batch).  The generator's update differentiates through y.  "
+                             "The checkpoint records the mode; a resumed run and every evaluation mode take it from there (where "
+                             "the critic scores softmax(x / tau) without noise), and a flag that contradicts it is an error "
+                             "(default: logits for a fresh run)")
+    parser.add_argument("--seed", default=0, type=int,
+                        help="the run's seed: the example stream, the noise streams and the Gumbel noise's key derive from it (default 0)")
+    parser.add_argument("--relax_tau", default=None, metavar="T | T0,T1,N",
+                        help="the relaxation's temperature: a constant T, or the schedule tau(it) = T0 (T1 / T0)^(min(it, N) / N) "
+                             "(default 1)")
     parser.add_argument("--likelihood_out", default=None,
                         help="load the checkpoint in --checkpoints_dir, write the negative log-likelihood of the test images' true "
                              "triples under the generator (mixture over --predict_samples noise draws, per draw, per slot; token "
@@ -1266,6 +1390,11 @@ def parse_args(argv=None):
         parser.error("--pretrain_iterations must be >= 0")
     if not (0.0 <= args.mle_weight < float("inf")):
         parser.error("--mle_weight must be a finite number >= 0")
+    if args.relax_tau is not None:
+        try:
+            args.relax_tau = parse_relax_tau(args.relax_tau)
+        except ValueError as e:
+            parser.error("--" + str(e))
     return args
 
 
@@ -1286,7 +1415,8 @@ if __name__ == "__main__":
                         ema_decay=params["ema_decay"], eval_live=params["eval_live"], accumulate=params["accumulate"],
                         clip_grad_norm=params["clip_grad_norm"], skip_nonfinite=params["skip_nonfinite"],
                         pretrain_iterations=params["pretrain_iterations"], mle_weight=params["mle_weight"],
-                        validate_nll=params["validate_nll"])
+                        validate_nll=params["validate_nll"], generator_output=params["generator_output"],
+                        relax_tau=params["relax_tau"], seed=params["seed"])
     if params["likelihood_out"]:
         if not gan.load_checkpoint():
             print("--likelihood_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
