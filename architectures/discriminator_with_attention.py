@@ -45,19 +45,24 @@ class Discriminator(NetworkHandle):
         self._publish(ctx, st)
         return st.OUT[0]
 
-    def score_samples(self, input_triples, images, relax_tau=None):
+    def score_samples(self, input_triples, images, relax_tau=None, relax_hard=False):
         """Critic outputs of N triples per image on ONE encoder pass: input_triples [N, B, 3, vocab] (one-hots or generator
         logits, e.g. Generator.sample's output), images [B, S, S, 3] -> [N, B, 3, 1].  Row k*B + b reads image b; the returned
         tensor is a view of the head's rows (the next call overwrites it).
         relax_tau = tau > 0: the critic of a run with a relaxed generator output - input_triples are logits and are replaced IN PLACE
         by softmax(logits / tau) before the critic reads them (one launch, csrc/relax.hip; a contiguous input_triples is the
-        caller's own tensor: take its argmax first)."""
+        caller's own tensor: take its argmax first).
+        relax_hard: the critic of a straight-through run - the logits are replaced IN PLACE by onehot(argmax(logits)) instead, without
+        noise and whatever the temperature: the scored row is the token argmax_rows reports."""
         net = self._ensure(images)
         B = int(images.shape[0])
         N = int(input_triples.shape[0])
         assert tuple(input_triples.shape) == (N, B, 3, self.vocab_size), input_triples.shape
         rows = input_triples.contiguous().view(N * B, 3, self.vocab_size)
-        if relax_tau is not None:
+        if relax_hard:
+            need_kernels(net.K, "score_samples(relax_hard)", "relax_rows_hard")
+            net.K.relax_rows_hard(rows)
+        elif relax_tau is not None:
             need_kernels(net.K, "score_samples(relax_tau)", "relax_rows")
             net.K.relax_rows(rows, float(relax_tau))
         ctx = net.trunk.forward(images.contiguous(), for_backward=False)

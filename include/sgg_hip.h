@@ -508,6 +508,20 @@ int sgg_relax_rows(const float* x, long long ldx, int R, int V, float tau, int g
                    float* y, long long ldy, float* u_out, long long ldu, void* stream);
 int sgg_relax_rows_bwd(const float* y, long long ldy, const float* dy, long long lddy, int R, int V, float tau, float scale, float* dx,
                        long long lddx, void* stream);
+/* The straight-through (hard) pair: the critic sees one-hot rows, the generator's update takes the soft row's gradient.
+ * sgg_relax_rows_hard: k_r = the FIRST index that maximises the fp32 s_j = x[r][j] (gumbel = 0) or x[r][j] + g_j (gumbel = 1, g formed
+ *   exactly as sgg_relax_rows forms it: one fp32 add).  No tau: the argmax is taken before any scaling.  y[r][j] = 1.0f at j = k_r,
+ *   +0.0f elsewhere; tok[r] = k_r (int64).  Either output may be null, not both; tok alone with gumbel = 1 is a Gumbel-max sample
+ *   from softmax(x[r]).  y may BE x (then ldy == ldx).  Finite x is a precondition (a row of NaN gives k_r = 0).
+ * sgg_relax_rows_hard_bwd: dx[r][j] = (scale / tau) * y_j * (dy_j - sum_k y_k dy_k) with y = softmax((x + g) / tau) recomputed from x
+ *   and the noise of (seed, draw) as sgg_relax_rows computes it - the input buffer of the critic holds the one-hot row, not y.
+ *   dx may BE dy (then lddx == lddy), not x.
+ * V <= 1024: one wave per row (the backward: x and dy in registers); above: one workgroup per row - the forward reads and draws
+ * the row once and writes it behind the barrier without reading; the backward reads x and dy and draws the noise in both passes. */
+int sgg_relax_rows_hard(const float* x, long long ldx, int R, int V, int gumbel, unsigned long long seed, unsigned long long draw,
+                        float* y, long long ldy, long long* tok, void* stream);
+int sgg_relax_rows_hard_bwd(const float* x, long long ldx, const float* dy, long long lddy, int R, int V, float tau, float scale,
+                            int gumbel, unsigned long long seed, unsigned long long draw, float* dx, long long lddx, void* stream);
 
 /* ---- training diagnostics: per-tensor norms and non-finite counts of a network's arenas (csrc/stats.hip) ----------------------
  * One read-only streaming pass over params, grads, m and v: fp32 arenas of ONE layout, every tensor 16-byte aligned and rounded up

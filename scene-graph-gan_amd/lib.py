@@ -99,6 +99,8 @@ SIGNATURES = {
     "sgg_triple_logp": (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sgg_relax_rows": (_i, [_vp, _ll, _i, _i, _f, _i, _ull, _ull, _vp, _ll, _vp, _ll, _vp]),
     "sgg_relax_rows_bwd": (_i, [_vp, _ll, _vp, _ll, _i, _i, _f, _f, _vp, _ll, _vp]),
+    "sgg_relax_rows_hard": (_i, [_vp, _ll, _i, _i, _i, _ull, _ull, _vp, _ll, _vp, _vp]),
+    "sgg_relax_rows_hard_bwd": (_i, [_vp, _ll, _vp, _ll, _i, _i, _f, _f, _i, _ull, _ull, _vp, _ll, _vp]),
     "sgg_arena_stats_chunk": (_i, []),
     "sgg_arena_stats_nstat": (_i, []),
     "sgg_arena_stats_workspace_bytes": (_sz, [_i]),
@@ -1229,6 +1231,44 @@ class HipKernels:
         assert tuple(gv.shape) == (R, V) and tuple(dv.shape) == (R, V), "dy and dx must have y's rows"
         self._check(self._timed("relax_bwd_%s_kernel" % ("resident" if V <= 1024 else "stream"), 0.0, lambda: self.lib.sgg_relax_rows_bwd(
             _p(yv), ldy, _p(gv), lddy, R, V, float(tau), float(scale), _p(dv), lddx, self._stream()), 4.0 * R * V * 3), "sgg_relax_rows_bwd")
+        return dx
+
+    def relax_rows_hard(self, x, y=None, tok=None, gumbel=False, seed=0, draw=0):
+        """The straight-through forward (csrc/relax.hip; include/sgg_hip.h): k = the first argmax of x + g per row (g as relax_rows
+        draws it, or 0), y = onehot(k) in fp32 (rows of x's shape with their own stride), tok int64 [R] = k.  y=None and tok=None:
+        x itself becomes the one-hot rows; tok alone with gumbel: a Gumbel-max sample from softmax(x).  Returns (y, tok)."""
+        if y is None and tok is None:
+            y = x
+        self._dev(x, y, tok)
+        xv, ldx = self._xent_rows(x, "x")
+        R, V = int(xv.shape[0]), int(xv.shape[1])
+        yv, ldy = None, 0
+        if y is not None:
+            yv, ldy = self._xent_rows(y, "y")
+            assert tuple(yv.shape) == (R, V), "y must have x's rows"
+        assert tok is None or (tok.dtype == torch.int64 and tok.numel() == R and tok.is_contiguous()), "tok: contiguous int64, one per row"
+        sym = "relax_hard_%s_kernel<%s>" % ("resident" if V <= 1024 else "stream", "true" if gumbel else "false")
+        self._check(self._timed(sym, 0.0, lambda: self.lib.sgg_relax_rows_hard(
+            _p(xv), ldx, R, V, int(bool(gumbel)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, _p(yv), ldy, _p(tok),
+            self._stream()), 4.0 * R * V * (1 if y is None else 2)), "sgg_relax_rows_hard")
+        return y, tok
+
+    def relax_rows_hard_bwd(self, x, dy, tau, scale=1.0, gumbel=False, seed=0, draw=0, dx=None):
+        """The straight-through backward: dx = (scale / tau) * y * (dy - sum_k y_k dy_k) with y = softmax((x + g) / tau) rebuilt from
+        the logits x and the noise of (seed, draw) - the launch that made the hard rows left no y behind.  x, dy, dx fp32 [..., V],
+        each with its own row stride; default dx: dy, in place (never x)."""
+        if dx is None:
+            dx = dy
+        self._dev(x, dy, dx)
+        xv, ldx = self._xent_rows(x, "x")
+        gv, lddy = self._xent_rows(dy, "dy")
+        dv, lddx = self._xent_rows(dx, "dx")
+        R, V = int(xv.shape[0]), int(xv.shape[1])
+        assert tuple(gv.shape) == (R, V) and tuple(dv.shape) == (R, V), "dy and dx must have x's rows"
+        sym = "relax_hard_bwd_%s_kernel<%s>" % ("resident" if V <= 1024 else "stream", "true" if gumbel else "false")
+        self._check(self._timed(sym, 0.0, lambda: self.lib.sgg_relax_rows_hard_bwd(
+            _p(xv), ldx, _p(gv), lddy, R, V, float(tau), float(scale), int(bool(gumbel)), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            int(draw) & 0xFFFFFFFFFFFFFFFF, _p(dv), lddx, self._stream()), 4.0 * R * V * 5), "sgg_relax_rows_hard_bwd")
         return dx
 
     def fill(self, t, value):

@@ -496,22 +496,31 @@ class GanStep:
     # ---- relaxed generator output (csrc/relax.hip) --------------------------------------------------------
     RELAX_MODES = ("logits", "softmax", "gumbel")
 
-    def set_relaxation(self, mode, tau=1.0, seed=0):
+    def set_relaxation(self, mode, tau=1.0, seed=0, hard=False):
         """What the critic sees of G's decoder rows x: "logits" (default) = x itself, nothing launched; "softmax" = y = softmax(x / tau);
         "gumbel" = y = softmax((x + g) / tau) with g drawn on the device from (seed, draw, row, column) - `draw` is the 64-bit number
         each step takes.  The generator's update differentiates through y (one launch in front of D, one behind the critic's gradient
         of its input); the critic's update treats y as a constant, as it treats the logits.  tau may be changed between steps by
-        another call (a schedule); the [B, 3, V] buffer of the generator update is allocated the first time a mode is on."""
+        another call (a schedule); the [B, 3, V] buffer of the generator update is allocated the first time a mode is on.
+        hard (straight-through, with "softmax" or "gumbel"): the critic sees onehot(argmax(x + g)) in both updates, and the generator's
+        update takes the gradient of the soft row y, rebuilt from the logits and the same draw behind the critic's input gradient."""
         if mode not in self.RELAX_MODES:
             raise ValueError("generator_output must be one of %s (got %r)" % (", ".join(self.RELAX_MODES), mode))
+        if hard and mode == "logits":
+            raise ValueError("the straight-through (hard) output needs generator_output softmax or gumbel: raw logits have no one-hot form")
         if mode == "logits":
             self._relax = None
             return
         tau = float(tau)
         if not (math.isfinite(tau) and tau > 0.0):
             raise ValueError("the relaxation's temperature must be a finite number > 0 (got %r)" % tau)
-        need_kernels(self.K, "generator_output=%s" % mode, "relax_rows", "relax_rows_bwd")
+        if hard:
+            need_kernels(self.K, "generator_output=%s, hard" % mode, "relax_rows_hard", "relax_rows_hard_bwd")
+        else:
+            need_kernels(self.K, "generator_output=%s" % mode, "relax_rows", "relax_rows_bwd")
         self._relax = {"mode": mode, "tau": tau, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF}
+        if hard:
+            self._relax["hard"] = True
         if self._relax_buf is None:
             self._relax_buf = torch.zeros_like(self.TRI[:self.B])
 
@@ -521,7 +530,11 @@ class GanStep:
         """out = the relaxed rows of `logits` [B,3,V] in the mode in force (one launch)."""
         rx = self._relax
         gumbel = rx["mode"] == "gumbel"
-        self.K.relax_rows(logits, rx["tau"], y=out, gumbel=gumbel, seed=rx["seed"], draw=(int(draw or 0) if gumbel else 0))
+        draw = int(draw or 0) if gumbel else 0
+        if rx.get("hard"):
+            self.K.relax_rows_hard(logits, y=out, gumbel=gumbel, seed=rx["seed"], draw=draw)
+        else:
+            self.K.relax_rows(logits, rx["tau"], y=out, gumbel=gumbel, seed=rx["seed"], draw=draw)
         return out
 
     def critic_step(self, images, labels, noise, alpha, micro=None, draw=None):
@@ -628,7 +641,8 @@ class GanStep:
         logits, and the summary into self.mle_losses.  w = 0 (default): nothing of it is launched.
         With a relaxation on (set_relaxation) D's input is y = relax(logits) in a buffer of its own, and the critic's gradient of y is
         turned into the gradient of the logits in place (relax_rows_bwd) before the likelihood term - a function of the logits - adds
-        to it.  draw: as critic_step."""
+        to it.  With the hard option D's input is the one-hot row and the second launch is relax_rows_hard_bwd on the logits.
+        draw: as critic_step."""
         K, B, G, D = self.K, self.B, self.G, self.D
         mk, mN = micro if micro is not None else (0, 1)
         mle_weight = float(mle_weight)
@@ -662,7 +676,12 @@ class GanStep:
         ind = D.head.in_dim
         for t in range(T_STEPS):
             K.gemm_nt(st.dXH[t][0][:, FEAT_C:ind], D.head.W_emb, gst.dOUT[0][:, t, :])
-        if self._relax is not None:
+        if self._relax is not None and self._relax.get("hard"):
+            # straight-through: d_in holds the one-hot rows; the soft row's gradient from the logits and the forward's draw, in place
+            gumbel = self._relax["mode"] == "gumbel"
+            K.relax_rows_hard_bwd(fake, gst.dOUT[0], self._relax["tau"], gumbel=gumbel, seed=self._relax["seed"],
+                                  draw=(int(draw or 0) if gumbel else 0))
+        elif self._relax is not None:
             K.relax_rows_bwd(d_in, gst.dOUT[0], self._relax["tau"])        # d cost / d y -> d cost / d logits, in place
         if mle_weight > 0.0:
             self._xent(fake, labels, mle_weight / B, gst.dOUT[0], accumulate=True, out=self.mle_losses)

@@ -10,6 +10,7 @@
     python train.py --pretrain_iterations 2000 --mle_weight 0.1 --validate_nll ...  # maximum-likelihood warm start of G, held-out NLL
     python train.py --checkpoints_dir ckpt --likelihood_out nll.json       # NLL of the test split's true triples under G
     python train.py --generator_output gumbel --relax_tau 2,0.5,20000 ...  # the critic sees Gumbel-softmax rows, tau annealed
+    python train.py --generator_output gumbel --relax_tau 1 --relax_hard ...  # straight-through: one-hot rows to the critic, soft gradient
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -123,7 +124,7 @@ class SceneGraphGAN(object):
                  path_to_image_means, path_to_image_stds, critic_iters, batch_size, lambda_, resume,
                  synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True,
                  ema_decay=0.0, eval_live=False, accumulate=1, clip_grad_norm=0.0, skip_nonfinite=False,
-                 pretrain_iterations=0, mle_weight=0.0, validate_nll=False, generator_output=None, relax_tau=None):
+                 pretrain_iterations=0, mle_weight=0.0, validate_nll=False, generator_output=None, relax_tau=None, relax_hard=False):
         # Hyperparameters (train.py:26-32)
         self.CRITIC_ITERS = int(critic_iters)
         self.BATCH_SIZE = int(batch_size)
@@ -180,6 +181,11 @@ class SceneGraphGAN(object):
             raise ValueError("generator_output must be one of %s (got %r)" % (", ".join(RELAX_MODES), generator_output))
         self._relax_flags = (generator_output, None if relax_tau is None else parse_relax_tau(relax_tau))
         self.relax_mode = generator_output or "logits"
+        # relax_hard: the straight-through estimator on top of "softmax" or "gumbel" - the critic sees onehot(argmax(logits [+ noise])),
+        # the generator's update takes the soft row's gradient.  False = not given: taken from the checkpoint like the mode.
+        self.relax_hard = bool(relax_hard)
+        if self.relax_hard and generator_output == "logits":
+            raise ValueError("relax_hard needs generator_output softmax or gumbel (got logits)")
         self.relax_tau = self._relax_flags[1] or (1.0, 1.0, 0)
         self.shuffle_buffer = bool(shuffle_buffer)      # tf.data shuffle(buffer_size = 10 * batch) on the repeated stream (train.py:176-179)
         self.checkpoints_dir, self.summaries_dir = checkpoints_dir, summaries_dir
@@ -338,7 +344,7 @@ class SceneGraphGAN(object):
     def _set_relaxation(self, step, it):
         """Put `step` into the run's mode at the temperature of iteration `it`; returns that temperature."""
         tau = relax_tau_at(self.relax_tau, it)
-        step.set_relaxation(self.relax_mode, tau, self._relax_seed())
+        step.set_relaxation(self.relax_mode, tau, self._relax_seed(), hard=self.relax_hard)
         return tau
 
     def _eval_relax(self):
@@ -346,9 +352,20 @@ class SceneGraphGAN(object):
         iteration - in both modes without Gumbel noise (the samples' diversity comes from the noise vector)."""
         return relax_tau_at(self.relax_tau, self.itr) if self.relaxed else None
 
+    def _eval_relax_kw(self):
+        """score_samples' keywords at evaluation: nothing (logits), the temperature, or - a straight-through run - the hard option:
+        the critic scores onehot(argmax(logits)), the row of the token that is reported."""
+        if not self.relaxed:
+            return {}
+        return dict({"relax_tau": self._eval_relax()}, **({"relax_hard": True} if self.relax_hard else {}))
+
+    def _hard_key(self):
+        """{"hard": True} for a straight-through run, else nothing: a soft run's checkpoint, logs and labels keep their keys."""
+        return {"hard": True} if self.relax_hard else {}
+
     def _relax_label(self):
         """The "generator_output" entry of an evaluation's JSON output."""
-        return {"mode": self.relax_mode, "tau": relax_tau_at(self.relax_tau, self.itr)}
+        return dict({"mode": self.relax_mode, "tau": relax_tau_at(self.relax_tau, self.itr)}, **self._hard_key())
 
     def _ensure_val_step(self, images):
         if self.val_step is None:
@@ -399,7 +416,7 @@ class SceneGraphGAN(object):
             if self.PRETRAIN > 0:           # (only a run with a pretraining phase writes the key)
                 ck["pretrain_iterations"] = self.PRETRAIN
             if self.relaxed:                # (only a run with a relaxed generator output writes the key)
-                ck["generator_output"] = {"mode": self.relax_mode, "tau": list(self.relax_tau)}
+                ck["generator_output"] = dict({"mode": self.relax_mode, "tau": list(self.relax_tau)}, **self._hard_key())
             if self.step.D.has_guard or self.step.G.has_guard:      # (only a guarded run writes the key: the clipped / skipped counts)
                 ck["guard"] = {n: net.guard_state() for n, net in (("D", self.step.D), ("G", self.step.G)) if net.has_guard}
             if self.step.G.has_average:     # (only a run that averages writes these keys: without it the checkpoint is what it was)
@@ -423,7 +440,10 @@ class SceneGraphGAN(object):
         if flag_tau is not None and saved_mode != "logits" and flag_tau != saved_tau:
             raise ValueError("--relax_tau %s contradicts the checkpoint's %s" % (",".join(str(x) for x in flag_tau),
                                                                                  ",".join(str(x) for x in saved_tau)))
-        self.relax_mode, self.relax_tau = saved_mode, saved_tau
+        if self.relax_hard and not saved_relax.get("hard"):
+            raise ValueError("--relax_hard contradicts the checkpoint, which was trained %s"
+                             % ("on the raw logits" if saved_mode == "logits" else "with soft %s rows" % saved_mode))
+        self.relax_mode, self.relax_tau, self.relax_hard = saved_mode, saved_tau, bool(saved_relax.get("hard"))
         self.g.load_state_dict(ck["G"])
         self.d.load_state_dict(ck["D"])
         for net, key in ((self.step.G, "G_adam"), (self.step.D, "D_adam")):
@@ -544,6 +564,8 @@ class SceneGraphGAN(object):
         self._constructOps(images)
         if self.resume and os.path.exists(self._ckpt_path()):
             self._loadModel(for_training=True)
+        if self.relax_hard and not self.relaxed:
+            raise ValueError("relax_hard needs generator_output softmax or gumbel (a fresh run's default is logits)")
         n_it = max_iterations if max_iterations is not None else getattr(self, "max_iterations", 1000)
         if validate_every is None:
             validate_every = getattr(self, "validate_iterations", 0) if self.dataset is not None else 0
@@ -619,7 +641,7 @@ class SceneGraphGAN(object):
                         if self.mle_weight > 0.0:
                             rec.update(mle)
                         if tau is not None:
-                            rec["relax"] = {"mode": self.relax_mode, "tau": tau}
+                            rec["relax"] = dict({"mode": self.relax_mode, "tau": tau}, **self._hard_key())
                     if N > 1:
                         rec["accumulate"] = N
                     if self.guarded:        # the records of each network's last update and the clipped / skipped counts so far
@@ -744,7 +766,7 @@ class SceneGraphGAN(object):
 
         gen = torch.Generator().manual_seed(self.seed + 123)
         toks = torch.empty((n_samples, nb, 3), dtype=torch.int64, device=self.device)
-        relax = {"relax_tau": self._eval_relax()} if self.relaxed else {}      # the critic scores what it was trained on
+        relax = self._eval_relax_kw()       # the critic scores what it was trained on
         r50, r100, details = [], [], []
         try:
             pending = fetch(0) if items else None
@@ -934,7 +956,7 @@ class SceneGraphGAN(object):
         results."""
         V = len(self.vocab)
         toks = torch.empty((N, nb, 3), dtype=torch.int64, device=self.device)
-        relax = {"relax_tau": self._eval_relax()} if self.relaxed else {}      # the critic scores what it was trained on
+        relax = self._eval_relax_kw()       # the critic scores what it was trained on
         with contextlib.closing(self._sample_batches(items, N, nb)) as batches:
             for i0, n, images, logits in batches:
                 K.argmax_rows(logits, toks.view(-1))
@@ -1363,6 +1385,11 @@ def build_parser():
                              "The checkpoint records the mode; a resumed run and every evaluation mode take it from there (where "
                              "the critic scores softmax(x / tau) without noise), and a flag that contradicts it is an error "
                              "(default: logits for a fresh run)")
+    parser.add_argument("--relax_hard", action="store_true",
+                        help="with --generator_output softmax|gumbel: the straight-through estimator - the critic is shown "
+                             "onehot(argmax(x + g)) in both updates and the generator's update takes the gradient of the soft row, rebuilt "
+                             "from the logits and the same noise.  Recorded in the checkpoint and taken from there on --resume and at "
+                             "evaluation, where the critic scores onehot(argmax(x)): the row of the reported token")
     parser.add_argument("--seed", default=0, type=int,
                         help="the run's seed: the example stream, the noise streams and the Gumbel noise's key derive from it (default 0)")
     parser.add_argument("--relax_tau", default=None, metavar="T | T0,T1,N",
@@ -1390,6 +1417,8 @@ def parse_args(argv=None):
         parser.error("--pretrain_iterations must be >= 0")
     if not (0.0 <= args.mle_weight < float("inf")):
         parser.error("--mle_weight must be a finite number >= 0")
+    if args.relax_hard and args.generator_output == "logits":
+        parser.error("--relax_hard needs --generator_output softmax or gumbel")
     if args.relax_tau is not None:
         try:
             args.relax_tau = parse_relax_tau(args.relax_tau)
@@ -1416,7 +1445,7 @@ if __name__ == "__main__":
                         clip_grad_norm=params["clip_grad_norm"], skip_nonfinite=params["skip_nonfinite"],
                         pretrain_iterations=params["pretrain_iterations"], mle_weight=params["mle_weight"],
                         validate_nll=params["validate_nll"], generator_output=params["generator_output"],
-                        relax_tau=params["relax_tau"], seed=params["seed"])
+                        relax_tau=params["relax_tau"], relax_hard=params["relax_hard"], seed=params["seed"])
     if params["likelihood_out"]:
         if not gan.load_checkpoint():
             print("--likelihood_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
