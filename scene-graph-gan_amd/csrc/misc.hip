@@ -120,14 +120,9 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   int bi = 0x7fffffff;
   for (int i = lane; i < V; i += 64) {
     const float v = x[(size_t)row * ld + i];
-    if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+    argmax_merge(best, bi, v, i);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
+  wave_argmax(best, bi);
   if (lane == 0) out[row] = (long long)bi;
 }
 

@@ -67,6 +67,24 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// (value, index) maximum: the larger value wins, on equal values the smaller index (tf.argmax: the first index of the maximum)
+__device__ __forceinline__ void argmax_merge(float& v, int& i, float ov, int oi) {
+  if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+__device__ __forceinline__ void wave_argmax(float& v, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    argmax_merge(v, i, ov, oi);
+  }
+}
+// the same over the n per-wave pairs a workgroup left in LDS (behind its barrier), in a fixed order; every thread gets the pair
+__device__ __forceinline__ void lds_argmax(const float* red_v, const int* red_i, int n, float& v, int& i) {
+  v = red_v[0];
+  i = red_i[0];
+  for (int w = 1; w < n; ++w) argmax_merge(v, i, red_v[w], red_i[w]);
+}
 // fp64: the same trees, a value exchanged as two 32-bit halves
 __device__ __forceinline__ double shfl_xor(double v, int o) {
   const long long b = __builtin_bit_cast(long long, v);

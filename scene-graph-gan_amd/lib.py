@@ -1132,7 +1132,7 @@ class HipKernels:
 
     # -- generator likelihood (csrc/xent.hip) ---------------------------------------------------------------
     @staticmethod
-    def _xent_rows(t, what):
+    def _rows(t, what):
         """[..., V] tensor whose rows are ONE fixed stride apart (a contiguous tensor, or a column slice of a wider 2-D buffer) ->
         ([R, V] view, row stride)."""
         assert t.dtype == torch.float32 and t.dim() >= 2, what
@@ -1141,24 +1141,29 @@ class HipKernels:
         assert x.stride(1) == 1 or V == 1, "%s: the last dimension must be contiguous" % what
         return x, int(_ld(x))
 
+    @staticmethod
+    def _rows_symbol(name, V, gumbel=None):
+        """The row kernel behind an entry point (csrc/softmax_rows.h): resident up to V = 1024, streaming above; <gumbel> where templated."""
+        return "%s_%s_kernel%s" % (name, "resident" if V <= 1024 else "stream", "" if gumbel is None else "<%s>" % ("true" if gumbel else "false"))
+
     def softmax_xent(self, logits, labels=None, scale=1.0, accumulate=False, dlogits=None, nll=None, lse=None, hit=None):
         """Row-wise log-softmax cross-entropy, forward and gradient in one launch (csrc/xent.hip; include/sgg_hip.h): logits fp32
         [..., V] (R rows one stride apart), labels int64 with R elements.  Outputs, each optional: dlogits (shape of logits, its own
         row stride) = scale * (softmax - onehot), stored or - accumulate - added; nll fp32 [R]; lse fp32 [R]; hit int32 [R] (1: the
         label is the row's argmax, 0: not, -1: the label is outside [0, V) and the row was skipped).  labels=None: lse only."""
         self._dev(logits, labels, dlogits, nll, lse, hit)
-        x, ld = self._xent_rows(logits, "logits")
+        x, ld = self._rows(logits, "logits")
         R, V = int(x.shape[0]), int(x.shape[1])
         ldd = 0
         if dlogits is not None:
-            d, ldd = self._xent_rows(dlogits, "dlogits")
+            d, ldd = self._rows(dlogits, "dlogits")
             assert tuple(d.shape) == (R, V), "dlogits must have the logits' rows"
         if labels is not None:
             assert labels.dtype == torch.int64 and labels.numel() == R and labels.is_contiguous()
         for t, dt in ((nll, torch.float32), (lse, torch.float32), (hit, torch.int32)):
             assert t is None or (t.dtype == dt and t.numel() == R and t.is_contiguous())
         nb = 4.0 * R * V * (1 + (0 if dlogits is None else (2 if accumulate else 1)))
-        self._check(self._timed("xent_rows_resident_kernel" if V <= 1024 else "xent_rows_stream_kernel", 0.0,
+        self._check(self._timed(self._rows_symbol("xent_rows", V), 0.0,
                                 lambda: self.lib.sgg_softmax_xent(_p(x), ld, R, V, _p(labels), float(scale), int(bool(accumulate)),
                                                                   _p(dlogits), ldd, _p(nll), _p(lse), _p(hit), self._stream()), nb),
                     "sgg_softmax_xent")
@@ -1204,16 +1209,15 @@ class HipKernels:
         if y is None:
             y = x
         self._dev(x, y, u_out)
-        xv, ldx = self._xent_rows(x, "x")
-        yv, ldy = self._xent_rows(y, "y")
+        xv, ldx = self._rows(x, "x")
+        yv, ldy = self._rows(y, "y")
         R, V = int(xv.shape[0]), int(xv.shape[1])
         assert tuple(yv.shape) == (R, V), "y must have x's rows"
         uv, ldu = None, 0
         if u_out is not None:
-            uv, ldu = self._xent_rows(u_out, "u_out")
+            uv, ldu = self._rows(u_out, "u_out")
             assert tuple(uv.shape) == (R, V), "u_out must have x's rows"
-        sym = "relax_rows_%s_kernel<%s>" % ("resident" if V <= 1024 else "stream", "true" if gumbel else "false")
-        self._check(self._timed(sym, 0.0, lambda: self.lib.sgg_relax_rows(
+        self._check(self._timed(self._rows_symbol("relax_rows", V, gumbel), 0.0, lambda: self.lib.sgg_relax_rows(
             _p(xv), ldx, R, V, float(tau), int(bool(gumbel)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, _p(yv), ldy,
             _p(uv), ldu, self._stream()), 4.0 * R * V * 2), "sgg_relax_rows")
         return y
@@ -1224,12 +1228,12 @@ class HipKernels:
         if dx is None:
             dx = dy
         self._dev(y, dy, dx)
-        yv, ldy = self._xent_rows(y, "y")
-        gv, lddy = self._xent_rows(dy, "dy")
-        dv, lddx = self._xent_rows(dx, "dx")
+        yv, ldy = self._rows(y, "y")
+        gv, lddy = self._rows(dy, "dy")
+        dv, lddx = self._rows(dx, "dx")
         R, V = int(yv.shape[0]), int(yv.shape[1])
         assert tuple(gv.shape) == (R, V) and tuple(dv.shape) == (R, V), "dy and dx must have y's rows"
-        self._check(self._timed("relax_bwd_%s_kernel" % ("resident" if V <= 1024 else "stream"), 0.0, lambda: self.lib.sgg_relax_rows_bwd(
+        self._check(self._timed(self._rows_symbol("relax_bwd", V), 0.0, lambda: self.lib.sgg_relax_rows_bwd(
             _p(yv), ldy, _p(gv), lddy, R, V, float(tau), float(scale), _p(dv), lddx, self._stream()), 4.0 * R * V * 3), "sgg_relax_rows_bwd")
         return dx
 
@@ -1240,15 +1244,14 @@ class HipKernels:
         if y is None and tok is None:
             y = x
         self._dev(x, y, tok)
-        xv, ldx = self._xent_rows(x, "x")
+        xv, ldx = self._rows(x, "x")
         R, V = int(xv.shape[0]), int(xv.shape[1])
         yv, ldy = None, 0
         if y is not None:
-            yv, ldy = self._xent_rows(y, "y")
+            yv, ldy = self._rows(y, "y")
             assert tuple(yv.shape) == (R, V), "y must have x's rows"
         assert tok is None or (tok.dtype == torch.int64 and tok.numel() == R and tok.is_contiguous()), "tok: contiguous int64, one per row"
-        sym = "relax_hard_%s_kernel<%s>" % ("resident" if V <= 1024 else "stream", "true" if gumbel else "false")
-        self._check(self._timed(sym, 0.0, lambda: self.lib.sgg_relax_rows_hard(
+        self._check(self._timed(self._rows_symbol("relax_hard", V, gumbel), 0.0, lambda: self.lib.sgg_relax_rows_hard(
             _p(xv), ldx, R, V, int(bool(gumbel)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, _p(yv), ldy, _p(tok),
             self._stream()), 4.0 * R * V * (1 if y is None else 2)), "sgg_relax_rows_hard")
         return y, tok
@@ -1260,13 +1263,12 @@ class HipKernels:
         if dx is None:
             dx = dy
         self._dev(x, dy, dx)
-        xv, ldx = self._xent_rows(x, "x")
-        gv, lddy = self._xent_rows(dy, "dy")
-        dv, lddx = self._xent_rows(dx, "dx")
+        xv, ldx = self._rows(x, "x")
+        gv, lddy = self._rows(dy, "dy")
+        dv, lddx = self._rows(dx, "dx")
         R, V = int(xv.shape[0]), int(xv.shape[1])
         assert tuple(gv.shape) == (R, V) and tuple(dv.shape) == (R, V), "dy and dx must have x's rows"
-        sym = "relax_hard_bwd_%s_kernel<%s>" % ("resident" if V <= 1024 else "stream", "true" if gumbel else "false")
-        self._check(self._timed(sym, 0.0, lambda: self.lib.sgg_relax_rows_hard_bwd(
+        self._check(self._timed(self._rows_symbol("relax_hard_bwd", V, gumbel), 0.0, lambda: self.lib.sgg_relax_rows_hard_bwd(
             _p(xv), ldx, _p(gv), lddy, R, V, float(tau), float(scale), int(bool(gumbel)), int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(draw) & 0xFFFFFFFFFFFFFFFF, _p(dv), lddx, self._stream()), 4.0 * R * V * 5), "sgg_relax_rows_hard_bwd")
         return dx

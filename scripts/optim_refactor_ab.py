@@ -165,15 +165,24 @@ def timing_leg(libs, names, dev, hyper, V, S, repeats, burst=10):
                 "swap": lambda: lib.call("sgg_swap_f32", t["p"], t["e"], n),
                 "grad_accumulate": lambda: lib.call("sgg_grad_accumulate", t["a"], t["g"], n, 0)}
 
-    fns = [legs(lib) for lib in libs]
+    res = {"vocab": V, "parameters": int(n), "burst": burst, "repeats": repeats,
+           "order": "%s first in even repetitions, %s first in odd ones" % tuple(names),
+           "legs": alternating_bursts([legs(lib) for lib in libs], LEGS, names, repeats, burst)}
+    res["ok"] = all(v["new_median_within_parent_max"] for v in res["legs"].values())
+    return res
+
+
+def alternating_bursts(fns, legs, names, repeats, burst=10):
+    """fns[0] (parent) and fns[1] (new): {leg: a function that enqueues one call}.  Per leg and repetition one burst of each between
+    two device events, parent and new alternating -> {leg: medians, extremes, every time, and the criterion}."""
     for f in fns:
         for fn in f.values():
             for _ in range(3):
                 fn()
     torch.cuda.synchronize()
-    ms = [{k: [] for k in LEGS} for _ in libs]
+    ms = [{k: [] for k in legs} for _ in fns]
     for r in range(repeats):
-        for k in LEGS:
+        for k in legs:
             # the second burst of a pair starts on the cache state (dirty lines of the same arenas) the first one left, the first on
             # that of another leg: which library goes first changes with every repetition
             for which in ((0, 1) if r % 2 == 0 else (1, 0)):
@@ -185,15 +194,13 @@ def timing_leg(libs, names, dev, hyper, V, S, repeats, burst=10):
                 e1.record()
                 e1.synchronize()
                 ms[which][k].append(e0.elapsed_time(e1) / burst)
-    res = {"vocab": V, "parameters": int(n), "burst": burst, "repeats": repeats,
-           "order": "%s first in even repetitions, %s first in odd ones" % tuple(names), "legs": {}}
-    for k in LEGS:
+    res = {}
+    for k in legs:
         par, new = ms[0][k], ms[1][k]
-        res["legs"][k] = {names[0]: {"median": round(float(np.median(par)), 5), "min": round(min(par), 5), "max": round(max(par), 5)},
-                          names[1]: {"median": round(float(np.median(new)), 5), "min": round(min(new), 5), "max": round(max(new), 5)},
-                          "new_median_within_parent_max": bool(np.median(new) <= max(par)),
-                          "ms_all": {names[0]: [round(x, 5) for x in par], names[1]: [round(x, 5) for x in new]}}
-    res["ok"] = all(v["new_median_within_parent_max"] for v in res["legs"].values())
+        res[k] = {names[0]: {"median": round(float(np.median(par)), 5), "min": round(min(par), 5), "max": round(max(par), 5)},
+                  names[1]: {"median": round(float(np.median(new)), 5), "min": round(min(new), 5), "max": round(max(new), 5)},
+                  "new_median_within_parent_max": bool(np.median(new) <= max(par)),
+                  "ms_all": {names[0]: [round(x, 5) for x in par], names[1]: [round(x, 5) for x in new]}}
     return res
 
 

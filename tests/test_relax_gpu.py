@@ -131,6 +131,40 @@ def test_relax_rows_match_fp64_restatement(hip, case, tau, gumbel):
     assert err_f <= RELAX_TOL and err_b <= RELAX_GRAD_TOL
 
 
+DX_APART_CASE = (2, 1027, 1028, 1028, 0, 0)         # both inputs of a backward in rows of 1028 on a 16-byte boundary ...
+DX_APART_SHIFT, DX_APART_TAU = 1, 0.25             # ... and dx in rows of 1028 one element behind one
+
+
+def check_dx_apart(launch, dx64, unit, tol):
+    """launch(dx) of a streaming backward whose inputs sit alike against 16 bytes (pass 1 on 16-byte loads), with dx one element off
+    (pass 2 on 4-byte accesses) and with dx laid out like the inputs: the guard words around dx, the restatement, equal bits."""
+    R, V, ld = DX_APART_CASE[:3]
+    bd, dv = on_device(None, R, V, ld, DX_APART_SHIFT, SENT[F32])
+    bl, dl = on_device(None, R, V, ld, 0, SENT[F32])
+    launch(dv)
+    launch(dl)
+    torch.cuda.synchronize()
+    assert_rows_guard(bd, R, V, ld, DX_APART_SHIFT, "dx")
+    assert_rows_guard(bl, R, V, ld, 0, "dx like the inputs")
+    err = float(np.abs(dv.cpu().numpy() - dx64).max()) / unit
+    print("dx one element off the inputs' alignment: max |dx - dx64| / (max|dy| scale / tau) %.3e" % err)
+    assert err <= tol
+    assert np.array_equal(u32(dv.contiguous()), u32(dl.contiguous())), "dx off the inputs' alignment differs from dx laid out like them"
+
+
+@pytest.mark.parametrize("gumbel", [False, True], ids=["softmax", "gumbel"])
+def test_backward_with_dx_alone_off_the_inputs_alignment(hip, gumbel):
+    R, V, ld = DX_APART_CASE[:3]
+    tau, scale = DX_APART_TAU, 0.37
+    x, dy, _, _ = relax_case(DX_APART_CASE, tau, gumbel)
+    _, xv = on_device(x, R, V, ld, 0, float("nan"))
+    _, yv = on_device(None, R, V, ld, 0, SENT[F32])
+    _, gv = on_device(dy, R, V, ld, 0, float("nan"))
+    hip.relax_rows(xv, tau, y=yv, gumbel=gumbel, seed=SEED, draw=77 + R)
+    check_dx_apart(lambda dx: hip.relax_rows_bwd(yv, gv, tau, scale=scale, dx=dx), RR.relax_rows_bwd(yv.cpu().numpy(), dy, tau, scale),
+                   float(np.abs(dy).max()) * scale / tau, RELAX_GRAD_TOL)
+
+
 @pytest.mark.parametrize("gumbel", [False, True], ids=["softmax", "gumbel"])
 @pytest.mark.parametrize("V,ld,sx", [(11, 11, 0), (1000, 1001, 1), (70001, 70001, 3)])
 def test_rows_of_plus_minus_80_at_tau_0p1_do_not_overflow(hip, V, ld, sx, gumbel):

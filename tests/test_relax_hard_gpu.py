@@ -20,7 +20,8 @@ from sgg_amd.step import GanStep
 from tests import relax_hard_ref as HR
 from tests.relax_hard_ref import HARD_GRAD_TOL, HARD_MARGIN_MIN
 from tests.test_relax_cpu import SEED
-from tests.test_relax_gpu import RELAX_CASES, TAUS, _arenas, _iteration, _setup, on_device, relax_case
+from tests.test_relax_gpu import (DX_APART_CASE, DX_APART_TAU, RELAX_CASES, TAUS, _arenas, _iteration, _setup, check_dx_apart, on_device,
+                                  relax_case)
 from tests.test_relax_hard_cpu import oracle_d_cost_hard, oracle_g_cost_hard
 from tests.test_step_gpu import check_weights_after_adam, tensor_err
 from tests.test_xent_gpu import F32, SENT, assert_rows_guard, u32
@@ -134,6 +135,18 @@ def test_hard_backward_matches_fp64_restatement_and_the_soft_pair(hip, case, tau
     print("relax_rows_hard_bwd R %d V %d tau %g gumbel %d: max |dx - dx64| %.3e   max |dx - soft pair| %.3e   (units of max|dy| scale / tau)"
           % (case[0], case[1], tau, gumbel, err, err_soft))
     assert err <= HARD_GRAD_TOL and err_soft <= 2 * HARD_GRAD_TOL
+
+
+@pytest.mark.parametrize("gumbel", [False, True], ids=["softmax", "gumbel"])
+def test_hard_backward_with_dx_alone_off_the_inputs_alignment(hip, gumbel):
+    R, V, ld = DX_APART_CASE[:3]
+    tau, scale = DX_APART_TAU, 0.37
+    kw = {"gumbel": gumbel, "seed": SEED, "draw": 77 + R}
+    x, dy, _, _ = relax_case(DX_APART_CASE, tau, gumbel)
+    _, xv = on_device(x, R, V, ld, 0, float("nan"))
+    _, gv = on_device(dy, R, V, ld, 0, float("nan"))
+    check_dx_apart(lambda dx: hip.relax_rows_hard_bwd(xv, gv, tau, scale=scale, dx=dx, **kw),
+                   HR.relax_rows_hard_bwd(x, dy, tau, scale, gumbel, SEED, 77 + R), float(np.abs(dy).max()) * scale / tau, HARD_GRAD_TOL)
 
 
 @pytest.mark.parametrize("gumbel", [False, True], ids=["softmax", "gumbel"])
