@@ -523,6 +523,33 @@ int sgg_relax_rows_hard(const float* x, long long ldx, int R, int V, int gumbel,
 int sgg_relax_rows_hard_bwd(const float* x, long long ldx, const float* dy, long long lddy, int R, int V, float tau, float scale,
                             int gumbel, unsigned long long seed, unsigned long long draw, float* dx, long long lddx, void* stream);
 
+/* ---- score-function (REINFORCE) generator update: the policy gradient of sampled triples (csrc/score.hip) ----------------------
+ * The decoder rows x are a policy p = softmax(x); tokens sampled from it (sgg_relax_rows_hard with tok and gumbel = 1) were scored by
+ * the critic, and the generator's gradient needs nothing of the critic but those scores.  None of the three uses a workspace or a
+ * float atomic, and two calls give the same bits; element offsets are 64-bit; anything outside the stated ranges is refused without
+ * a launch.
+ * sgg_score_advantage: one workgroup.  d_out fp32 [B][T], rows ldd >= T apart: the critic's outputs of sample b.
+ *   r_b = (sum_t d_out[b][t]) / T, summed in fp32 in order of t; S = sum_b r_b in fp64 in order of b.  baseline = 0 (none):
+ *   adv[b] = r_b.  baseline = 1 (leave-one-out): adv[b] = (float)(r_b - (S - r_b) / (B - 1)) in fp64, the reward against the mean of
+ *   the OTHER rewards; it needs B >= 2.  out2 (optional) fp32 = { mean_b r_b, mean_b adv[b]^2 }, summed in fp64 in order of b.
+ *   1 <= B <= 2^20, 1 <= T <= 64.
+ * sgg_score_rows: row r is x[r * ldx .. r * ldx + V), ldx >= V, any 4-byte alignment.  lse = max + log(sum_j exp(x_j - max)),
+ *   p_j = exp(x_j - lse), H_r = lse - sum_j p_j x_j (the row's entropy), w_r = coef * adv[r / group] (adv = NULL: w_r = coef; adv has
+ *   ceil(R / group) entries).  tok int64 [R].  For a token a = tok[r] in [0, V):
+ *   dx[r][j] = w_r (p_j - [j == a]) + ent_coef * p_j ((x_j - lse) + H_r) - the gradient of -w_r log p_a - ent_coef H_r by x - rows
+ *   lddx >= V apart, stored (accumulate = 0) or added to what is there (accumulate = 1); logp[r] = x_a - lse; ent[r] = H_r.  A token
+ *   outside [0, V) SKIPS the row as sgg_softmax_xent does: logp = 0, its dx row zero-filled (accumulate = 0) or untouched
+ *   (accumulate = 1); ent is written all the same.  The token is read once per row and addresses no load or store.  dx, logp and ent
+ *   may each be NULL (not all; without dx the row is read once).  dx must not BE x.  R >= 1, 1 <= V <= 2^21, group >= 1, coef and
+ *   ent_coef finite; finite x is a precondition.  V <= 1024: one wave per row, the row in registers; above: one workgroup per row,
+ *   an online pass for (max, sum exp, sum exp * x) and a gradient pass that re-reads the row.
+ * sgg_score_summary: one workgroup.  out2 fp32 = { mean logp, mean ent } over the R rows, summed in fp64 in row order.
+ *   1 <= R <= 2^24. */
+int sgg_score_advantage(const float* d_out, long long ldd, int B, int T, int baseline, float* adv, float* out2, void* stream);
+int sgg_score_rows(const float* x, long long ldx, int R, int V, const long long* tok, const float* adv, int group, float coef,
+                   float ent_coef, int accumulate, float* dx, long long lddx, float* logp, float* ent, void* stream);
+int sgg_score_summary(const float* logp, const float* ent, int R, float* out2, void* stream);
+
 /* ---- training diagnostics: per-tensor norms and non-finite counts of a network's arenas (csrc/stats.hip) ----------------------
  * One read-only streaming pass over params, grads, m and v: fp32 arenas of ONE layout, every tensor 16-byte aligned and rounded up
  * to 4 elements (the arena ends on such a boundary), as sgg_adam_tf_multi takes them.

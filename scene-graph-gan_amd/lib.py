@@ -101,6 +101,9 @@ SIGNATURES = {
     "sgg_relax_rows_bwd": (_i, [_vp, _ll, _vp, _ll, _i, _i, _f, _f, _vp, _ll, _vp]),
     "sgg_relax_rows_hard": (_i, [_vp, _ll, _i, _i, _i, _ull, _ull, _vp, _ll, _vp, _vp]),
     "sgg_relax_rows_hard_bwd": (_i, [_vp, _ll, _vp, _ll, _i, _i, _f, _f, _i, _ull, _ull, _vp, _ll, _vp]),
+    "sgg_score_advantage": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _vp]),
+    "sgg_score_rows": (_i, [_vp, _ll, _i, _i, _vp, _vp, _i, _f, _f, _i, _vp, _ll, _vp, _vp, _vp]),
+    "sgg_score_summary": (_i, [_vp, _vp, _i, _vp, _vp]),
     "sgg_arena_stats_chunk": (_i, []),
     "sgg_arena_stats_nstat": (_i, []),
     "sgg_arena_stats_workspace_bytes": (_sz, [_i]),
@@ -1272,6 +1275,64 @@ class HipKernels:
             _p(xv), ldx, _p(gv), lddy, R, V, float(tau), float(scale), int(bool(gumbel)), int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(draw) & 0xFFFFFFFFFFFFFFFF, _p(dv), lddx, self._stream()), 4.0 * R * V * 5), "sgg_relax_rows_hard_bwd")
         return dx
+
+    # -- score-function generator update (csrc/score.hip) -----------------------------------------------------------
+    SCORE_BASELINES = {"none": 0, "rloo": 1}
+
+    def score_advantage(self, d_out, baseline="rloo", adv=None, out2=None):
+        """Rewards and advantages of B sampled triples (csrc/score.hip; include/sgg_hip.h): d_out fp32 [B, T] (rows one stride apart) =
+        the critic's outputs, r_b = mean_t d_out[b, t]; adv fp32 [B] = r_b ("none") or r_b minus the mean of the other rewards
+        ("rloo": needs B >= 2).  out2 (optional) fp32 [2] = (mean reward, mean advantage^2).  One workgroup.  Returns adv."""
+        if baseline not in self.SCORE_BASELINES:
+            raise ValueError("score_advantage: baseline must be one of %s (got %r)" % (", ".join(sorted(self.SCORE_BASELINES)), baseline))
+        self._dev(d_out, adv, out2)
+        assert d_out.dim() == 2, "d_out must be [B, T]"
+        dv, ldd = self._rows(d_out, "d_out")
+        B, T = int(dv.shape[0]), int(dv.shape[1])
+        if adv is None:
+            adv = torch.empty(B, dtype=torch.float32, device=d_out.device)
+        assert adv.dtype == torch.float32 and adv.numel() == B and adv.is_contiguous(), "adv: contiguous fp32, one per row of d_out"
+        assert out2 is None or (out2.dtype == torch.float32 and out2.numel() == 2 and out2.is_contiguous()), "out2: contiguous fp32 [2]"
+        self._check(self.lib.sgg_score_advantage(_p(dv), ldd, B, T, self.SCORE_BASELINES[baseline], _p(adv), _p(out2), self._stream()),
+                    "sgg_score_advantage")
+        return adv
+
+    def score_rows(self, x, tok, adv=None, group=1, coef=1.0, ent_coef=0.0, accumulate=False, dx=None, logp=None, ent=None):
+        """The policy gradient of sampled tokens, row by row in one launch (csrc/score.hip; include/sgg_hip.h): x fp32 [..., V] (R rows
+        one stride apart), tok int64 with R elements, adv fp32 with at least ceil(R / group) elements (None: every weight is coef).
+        Outputs, each optional (not all absent): dx (x's rows, its own stride; never x itself) = coef * adv[r // group] * (softmax -
+        onehot(tok)) + ent_coef * softmax * (log softmax + H), stored or - accumulate - added; logp fp32 [R] = log softmax(x)[tok];
+        ent fp32 [R] = H, the row's entropy.  A token outside [0, V) skips its row (logp 0, dx zero or untouched)."""
+        self._dev(x, tok, adv, dx, logp, ent)
+        xv, ldx = self._rows(x, "x")
+        R, V = int(xv.shape[0]), int(xv.shape[1])
+        group = int(group)
+        assert tok.dtype == torch.int64 and tok.numel() == R and tok.is_contiguous(), "tok: contiguous int64, one per row"
+        if adv is not None:
+            assert adv.dtype == torch.float32 and adv.is_contiguous(), "adv: contiguous fp32"
+            assert group < 1 or adv.numel() >= -(-R // group), "adv needs ceil(R / group) = %d elements (got %d)" % (-(-R // max(group, 1)), adv.numel())
+        dv, lddx = None, 0
+        if dx is not None:
+            dv, lddx = self._rows(dx, "dx")
+            assert tuple(dv.shape) == (R, V), "dx must have x's rows"
+        for t in (logp, ent):
+            assert t is None or (t.dtype == torch.float32 and t.numel() == R and t.is_contiguous()), "logp, ent: contiguous fp32, one per row"
+        nb = 4.0 * R * V * (1 + (0 if dx is None else (2 if accumulate else 1)))
+        self._check(self._timed(self._rows_symbol("score_rows", V), 0.0, lambda: self.lib.sgg_score_rows(
+            _p(xv), ldx, R, V, _p(tok), _p(adv), group, float(coef), float(ent_coef), int(bool(accumulate)), _p(dv), lddx, _p(logp), _p(ent),
+            self._stream()), nb), "sgg_score_rows")
+        return dx
+
+    def score_summary(self, logp, ent, out2=None):
+        """out2 fp32 [2] = (mean logp, mean ent) of score_rows' per-row outputs over their R rows; one workgroup, fp64, row order."""
+        self._dev(logp, ent, out2)
+        R = logp.numel()
+        assert logp.dtype == torch.float32 and ent.dtype == torch.float32 and ent.numel() == R and logp.is_contiguous() and ent.is_contiguous()
+        if out2 is None:
+            out2 = torch.empty(2, dtype=torch.float32, device=logp.device)
+        assert out2.dtype == torch.float32 and out2.numel() == 2 and out2.is_contiguous()
+        self._check(self.lib.sgg_score_summary(_p(logp), _p(ent), R, _p(out2), self._stream()), "sgg_score_summary")
+        return out2
 
     def fill(self, t, value):
         self._dev(t)

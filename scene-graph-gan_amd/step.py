@@ -358,13 +358,15 @@ class GanStep:
         # default because concurrent kernels make per-kernel durations (the roofline measurement) meaningless.
         self._g_reuse, self._g_reuse_armed = None, False       # (images, ctx) of G's encoder within one train_iteration
         self._g_reuse_slots = {}                 # accumulation: micro-batch k -> (images, copy of ctx, guard) (generator_forward)
-        self._loss_acc, self._loss_n = {}, {"d": 1, "g": 1, "m": 1}    # sums of the four loss numbers over the micro-batches of an update
+        self._loss_acc, self._loss_n = {}, {"d": 1, "g": 1, "m": 1, "s": 1}    # sums of the four loss numbers over the micro-batches of an update
         # generator likelihood (pretrain_step, generator_step(mle_weight > 0), generator_nll): (nll per token, token accuracy, triple
         # accuracy, valid rows) of the last cross-entropy; the per-row buffers behind it are allocated at the first use (_xent_rows)
         self.mle_losses = z(4)
         self._xent_buf = None
         # relaxed generator output (set_relaxation; csrc/relax.hip): None = the critic sees the raw decoder logits
         self._relax, self._relax_buf = None, None
+        # score-function generator update (set_estimator; csrc/score.hip): None = the pathwise update, nothing of it is launched or allocated
+        self._estimator, self._score_bufs = None, None
         # (option side_priority: priority of the side streams - everything on them is off the critical chain of the main stream)
         prio = int(option(K, "side_priority"))
         self.side = torch.cuda.Stream(device=dev, priority=prio) if (overlap_streams and dev.type == "cuda") else None
@@ -537,6 +539,51 @@ class GanStep:
             self.K.relax_rows(logits, rx["tau"], y=out, gumbel=gumbel, seed=rx["seed"], draw=draw)
         return out
 
+    # ---- score-function generator update (csrc/score.hip) ---------------------------------------------------
+    ESTIMATORS = ("pathwise", "score")
+    SCORE_BASELINES = ("rloo", "none")
+
+    def _check_score_relaxation(self):
+        rx = self._relax
+        if rx is None or rx["mode"] != "gumbel" or not rx.get("hard"):
+            have = "logits" if rx is None else "%s, hard=%s" % (rx["mode"], bool(rx.get("hard")))
+            raise ValueError("generator_gradient=score needs generator_output=gumbel with hard=True - the critic must see Gumbel-max "
+                             "samples of softmax(logits) in both updates (the relaxation in force is generator_output=%s)" % have)
+
+    def set_estimator(self, kind="pathwise", baseline="rloo", entropy_weight=0.0):
+        """How the generator's update gets its gradient.  "pathwise" (default): through the critic's gradient of its input, as
+        set_relaxation describes - today's path, nothing new launched.  "score": the score-function (REINFORCE) estimator.  The critic
+        scores the sampled one-hot rows (the relaxation must be "gumbel" with hard=True: tok is then an exact sample of
+        softmax(logits)), its head is NOT differentiated, and the logits receive the gradient of
+            -(1/B) sum_b A_b sum_t log p(a_bt) - (entropy_weight / B) sum_{b,t} H(p_bt)
+        with A_b a constant: the reward r_b = mean_t D(sample b)[t], minus - baseline "rloo" - the mean reward of the OTHER samples of
+        the (micro-)batch, which leaves the estimator unbiased; "none": r_b itself.  entropy_weight >= 0: an entropy bonus on the
+        policy.  Four numbers of the update land in score_losses."""
+        if kind not in self.ESTIMATORS:
+            raise ValueError("generator_gradient must be one of %s (got %r)" % (", ".join(self.ESTIMATORS), kind))
+        if kind == "pathwise":
+            self._estimator = None
+            return
+        if baseline not in self.SCORE_BASELINES:
+            raise ValueError("score_baseline must be one of %s (got %r)" % (", ".join(self.SCORE_BASELINES), baseline))
+        entropy_weight = float(entropy_weight)
+        if not (math.isfinite(entropy_weight) and entropy_weight >= 0.0):
+            raise ValueError("entropy_weight must be a finite number >= 0 (got %r)" % entropy_weight)
+        self._check_score_relaxation()
+        need_kernels(self.K, "generator_gradient=score", "score_advantage", "score_rows", "score_summary", "relax_rows_hard")
+        if baseline == "rloo" and self.B < 2:
+            raise ValueError("score_baseline=rloo compares each sample with the others of its batch: it needs B >= 2 (got B = %d)" % self.B)
+        if self._score_bufs is None:
+            dev, dt, R = self.g_losses.device, self.g_losses.dtype, self.B * T_STEPS
+            self._score_bufs = {"tok": torch.zeros((self.B, T_STEPS), dtype=torch.int64, device=dev), "adv": torch.zeros(self.B, dtype=dt, device=dev),
+                                "logp": torch.zeros(R, dtype=dt, device=dev), "ent": torch.zeros(R, dtype=dt, device=dev)}
+            self.score_losses = torch.zeros(4, dtype=dt, device=dev)
+        self._estimator = {"kind": "score", "baseline": baseline, "entropy_weight": entropy_weight}
+
+    estimator = property(lambda self: {"kind": "pathwise"} if self._estimator is None else dict(self._estimator))
+    _score_tok = property(lambda self: self._score_bufs["tok"])
+    _score_adv = property(lambda self: self._score_bufs["adv"])
+
     def critic_step(self, images, labels, noise, alpha, micro=None, draw=None):
         """One disc_train_op (train.py:365). labels int64 [B,3]; noise [B,512]; alpha [B]. Returns self.d_losses
         = (disc_cost, wasserstein term, gradient penalty, mean D(fake)) as a device tensor.
@@ -642,6 +689,7 @@ class GanStep:
         With a relaxation on (set_relaxation) D's input is y = relax(logits) in a buffer of its own, and the critic's gradient of y is
         turned into the gradient of the logits in place (relax_rows_bwd) before the likelihood term - a function of the logits - adds
         to it.  With the hard option D's input is the one-hot row and the second launch is relax_rows_hard_bwd on the logits.
+        With the score-function estimator (set_estimator) D's head is not differentiated: _score_logits_gradient.
         draw: as critic_step."""
         K, B, G, D = self.K, self.B, self.G, self.D
         mk, mN = micro if micro is not None else (0, 1)
@@ -652,6 +700,9 @@ class GanStep:
             if labels is None:
                 raise ValueError("generator_step: mle_weight > 0 needs the labels of the minibatch")
             self._need_xent("generator_step(mle_weight > 0)")
+        score = self._estimator
+        if score is not None:
+            self._check_score_relaxation()        # (set_relaxation may have been called since set_estimator)
         if mN > 1:
             G._acc_flat()
         G.finish_update()
@@ -667,22 +718,25 @@ class GanStep:
             ctx = self._d_encoder_on_side_stream(images, zero_grads=False, for_backward=False)   # only D's head is differentiated here
         fake = gst.OUT[0]
         self._join_side()
-        d_in = fake if self._relax is None else self._relax_fwd(fake, self._relax_buf, draw)
-        st = D.head.state(1, B, "g")
-        D.head.forward(st, ctx, [d_in])
-        K.wgan_losses(st.OUT[0].view(B, T_STEPS), None, 0.0, B, T_STEPS, False, self.g_losses)
-        K.fill(st.dOUT[0], -1.0 / (B * T_STEPS))  # gen_cost = -mean(D(G(x)))
-        D.head.backward(st, ctx, [d_in], R_w=0)
-        ind = D.head.in_dim
-        for t in range(T_STEPS):
-            K.gemm_nt(st.dXH[t][0][:, FEAT_C:ind], D.head.W_emb, gst.dOUT[0][:, t, :])
-        if self._relax is not None and self._relax.get("hard"):
-            # straight-through: d_in holds the one-hot rows; the soft row's gradient from the logits and the forward's draw, in place
-            gumbel = self._relax["mode"] == "gumbel"
-            K.relax_rows_hard_bwd(fake, gst.dOUT[0], self._relax["tau"], gumbel=gumbel, seed=self._relax["seed"],
-                                  draw=(int(draw or 0) if gumbel else 0))
-        elif self._relax is not None:
-            K.relax_rows_bwd(d_in, gst.dOUT[0], self._relax["tau"])        # d cost / d y -> d cost / d logits, in place
+        if score is not None:
+            self._score_logits_gradient(score, gst, ctx, draw)
+        else:
+            d_in = fake if self._relax is None else self._relax_fwd(fake, self._relax_buf, draw)
+            st = D.head.state(1, B, "g")
+            D.head.forward(st, ctx, [d_in])
+            K.wgan_losses(st.OUT[0].view(B, T_STEPS), None, 0.0, B, T_STEPS, False, self.g_losses)
+            K.fill(st.dOUT[0], -1.0 / (B * T_STEPS))  # gen_cost = -mean(D(G(x)))
+            D.head.backward(st, ctx, [d_in], R_w=0)
+            ind = D.head.in_dim
+            for t in range(T_STEPS):
+                K.gemm_nt(st.dXH[t][0][:, FEAT_C:ind], D.head.W_emb, gst.dOUT[0][:, t, :])
+            if self._relax is not None and self._relax.get("hard"):
+                # straight-through: d_in holds the one-hot rows; the soft row's gradient from the logits and the forward's draw, in place
+                gumbel = self._relax["mode"] == "gumbel"
+                K.relax_rows_hard_bwd(fake, gst.dOUT[0], self._relax["tau"], gumbel=gumbel, seed=self._relax["seed"],
+                                      draw=(int(draw or 0) if gumbel else 0))
+            elif self._relax is not None:
+                K.relax_rows_bwd(d_in, gst.dOUT[0], self._relax["tau"])        # d cost / d y -> d cost / d logits, in place
         if mle_weight > 0.0:
             self._xent(fake, labels, mle_weight / B, gst.dOUT[0], accumulate=True, out=self.mle_losses)
             self._sum_losses("m", self.mle_losses, mk, mN)
@@ -691,8 +745,26 @@ class GanStep:
         G.trunk.backward(dctx)
         G.head.join()
         self._sum_losses("g", self.g_losses, mk, mN)
+        if score is not None:
+            self._sum_losses("s", self.score_losses, mk, mN)
         G.end_micro_batch(mk, mN, self.reducer)
         return self.g_losses
+
+    def _score_logits_gradient(self, score, gst, ctx, draw):
+        """The middle of generator_step with the score-function estimator (set_estimator): D's head runs forward only, on the sampled
+        one-hot rows, into g_losses; the gradient of the logits (G's dOUT) comes from the samples' log-probabilities weighted by their
+        advantages, and the update's four numbers go into score_losses."""
+        K, B, D = self.K, self.B, self.D
+        fake, bufs, rx = gst.OUT[0], self._score_bufs, self._relax
+        # one launch: the one-hot rows D scores and the tokens they are the rows of - Gumbel-max samples of softmax(fake)
+        K.relax_rows_hard(fake, y=self._relax_buf, tok=bufs["tok"], gumbel=True, seed=rx["seed"], draw=int(draw or 0))
+        st = D.head.state(1, B, "g")
+        D.head.forward(st, ctx, [self._relax_buf])
+        K.wgan_losses(st.OUT[0].view(B, T_STEPS), None, 0.0, B, T_STEPS, False, self.g_losses)
+        K.score_advantage(st.OUT[0].view(B, T_STEPS), score["baseline"], adv=bufs["adv"], out2=self.score_losses[0:2])
+        K.score_rows(fake, bufs["tok"].view(-1), bufs["adv"], group=T_STEPS, coef=1.0 / B, ent_coef=score["entropy_weight"] / B,
+                     dx=gst.dOUT[0], logp=bufs["logp"], ent=bufs["ent"])
+        K.score_summary(bufs["logp"], bufs["ent"], out2=self.score_losses[2:4])
 
     # ---- generator likelihood (csrc/xent.hip) -------------------------------------------------------------
     def _need_xent(self, what):
@@ -776,6 +848,8 @@ class GanStep:
     g_losses_mean = property(lambda self: self._losses_mean("g", self.g_losses))
     # (nll per token, token accuracy, triple accuracy, valid rows) of the last cross-entropy of a training step, the same way
     mle_losses_mean = property(lambda self: self._losses_mean("m", self.mle_losses))
+    # (mean reward, mean advantage^2, mean log-probability per sampled token, mean entropy per token) of the last score-function update
+    score_losses_mean = property(lambda self: self._losses_mean("s", self.score_losses))
 
     def flush(self):
         """Apply any deferred optimiser update (before reading weights / at the end of the timed region)."""

@@ -11,6 +11,7 @@
     python train.py --checkpoints_dir ckpt --likelihood_out nll.json       # NLL of the test split's true triples under G
     python train.py --generator_output gumbel --relax_tau 2,0.5,20000 ...  # the critic sees Gumbel-softmax rows, tau annealed
     python train.py --generator_output gumbel --relax_tau 1 --relax_hard ...  # straight-through: one-hot rows to the critic, soft gradient
+    python train.py --generator_gradient score --entropy_weight 0.01 ...   # REINFORCE on sampled triples: no gradient through the critic
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -27,6 +28,7 @@ sys.path.append(os.getcwd())
 import argparse
 import contextlib
 import json
+import math
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -110,6 +112,33 @@ def relax_draw(it, update, micro, critic_iters, accumulate):
     return ((int(it) * (int(critic_iters) + 1) + int(update)) * int(accumulate) + int(micro)) & 0x7FFFFFFFFFFFFFFF
 
 
+GRADIENTS = ("pathwise", "score")
+SCORE_BASELINES = ("rloo", "none")
+
+
+def check_score_flags(generator_gradient, score_baseline, entropy_weight, generator_output, relax_tau):
+    """The combinations of --generator_gradient / --score_baseline / --entropy_weight with each other and with the relaxation's flags
+    that are refused (ValueError); returns (generator_gradient, score_baseline, entropy_weight) as given (None: not given)."""
+    if generator_gradient is not None and generator_gradient not in GRADIENTS:
+        raise ValueError("generator_gradient must be one of %s (got %r)" % (", ".join(GRADIENTS), generator_gradient))
+    if score_baseline is not None and score_baseline not in SCORE_BASELINES:
+        raise ValueError("score_baseline must be one of %s (got %r)" % (", ".join(SCORE_BASELINES), score_baseline))
+    if entropy_weight is not None:
+        entropy_weight = float(entropy_weight)
+        if not (0.0 <= entropy_weight < float("inf")):
+            raise ValueError("entropy_weight must be a finite number >= 0 (got %r)" % entropy_weight)
+    if generator_gradient != "score":
+        if score_baseline is not None or entropy_weight is not None:
+            raise ValueError("score_baseline and entropy_weight belong to generator_gradient score")
+    else:
+        if generator_output in ("logits", "softmax"):
+            raise ValueError("generator_gradient score implies generator_output gumbel with relax_hard: the critic must see samples of "
+                             "softmax(logits) (got generator_output %s)" % generator_output)
+        if relax_tau is not None:
+            raise ValueError("relax_tau has no meaning with generator_gradient score: no temperature enters either update")
+    return generator_gradient, score_baseline, entropy_weight
+
+
 def relax_val_draw(k):
     """... and of validation number k: the top bit set, so that no training launch shares it."""
     return (1 << 63) | (int(k) & 0x7FFFFFFFFFFFFFFF)
@@ -124,7 +153,8 @@ class SceneGraphGAN(object):
                  path_to_image_means, path_to_image_stds, critic_iters, batch_size, lambda_, resume,
                  synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True,
                  ema_decay=0.0, eval_live=False, accumulate=1, clip_grad_norm=0.0, skip_nonfinite=False,
-                 pretrain_iterations=0, mle_weight=0.0, validate_nll=False, generator_output=None, relax_tau=None, relax_hard=False):
+                 pretrain_iterations=0, mle_weight=0.0, validate_nll=False, generator_output=None, relax_tau=None, relax_hard=False,
+                 generator_gradient=None, score_baseline=None, entropy_weight=None):
         # Hyperparameters (train.py:26-32)
         self.CRITIC_ITERS = int(critic_iters)
         self.BATCH_SIZE = int(batch_size)
@@ -179,6 +209,15 @@ class SceneGraphGAN(object):
         # an error (_loadModel).
         if generator_output is not None and generator_output not in RELAX_MODES:
             raise ValueError("generator_output must be one of %s (got %r)" % (", ".join(RELAX_MODES), generator_output))
+        # generator_gradient = "score": the generator's update is the score-function (REINFORCE) estimator on the sampled triples
+        # (GanStep.set_estimator) - it implies generator_output gumbel with relax_hard (the critic sees Gumbel-max samples of
+        # softmax(logits) in both updates) and takes no temperature; score_baseline "rloo" (default) | "none", entropy_weight >= 0.
+        # None = not given: pathwise for a fresh run; a resumed run or an evaluation takes all three from the checkpoint.
+        self._score_flags = check_score_flags(generator_gradient, score_baseline, entropy_weight, generator_output, relax_tau)
+        self.score = None
+        if generator_gradient == "score":
+            generator_output, relax_hard = "gumbel", True
+            self.score = {"kind": "score", "baseline": score_baseline or "rloo", "entropy_weight": float(entropy_weight or 0.0)}
         self._relax_flags = (generator_output, None if relax_tau is None else parse_relax_tau(relax_tau))
         self.relax_mode = generator_output or "logits"
         # relax_hard: the straight-through estimator on top of "softmax" or "gumbel" - the critic sees onehot(argmax(logits [+ noise])),
@@ -365,7 +404,8 @@ class SceneGraphGAN(object):
 
     def _relax_label(self):
         """The "generator_output" entry of an evaluation's JSON output."""
-        return dict({"mode": self.relax_mode, "tau": relax_tau_at(self.relax_tau, self.itr)}, **self._hard_key())
+        return dict({"mode": self.relax_mode, "tau": relax_tau_at(self.relax_tau, self.itr)}, **self._hard_key(),
+                    **({"gradient": "score"} if self.score else {}))
 
     def _ensure_val_step(self, images):
         if self.val_step is None:
@@ -417,6 +457,8 @@ class SceneGraphGAN(object):
                 ck["pretrain_iterations"] = self.PRETRAIN
             if self.relaxed:                # (only a run with a relaxed generator output writes the key)
                 ck["generator_output"] = dict({"mode": self.relax_mode, "tau": list(self.relax_tau)}, **self._hard_key())
+                if self.score:              # (only a run with the score-function update writes the key)
+                    ck["generator_output"]["gradient"] = dict(self.score)
             if self.step.D.has_guard or self.step.G.has_guard:      # (only a guarded run writes the key: the clipped / skipped counts)
                 ck["guard"] = {n: net.guard_state() for n, net in (("D", self.step.D), ("G", self.step.G)) if net.has_guard}
             if self.step.G.has_average:     # (only a run that averages writes these keys: without it the checkpoint is what it was)
@@ -435,6 +477,15 @@ class SceneGraphGAN(object):
         saved_relax = ck.get("generator_output") or {"mode": "logits", "tau": [1.0, 1.0, 0]}
         saved_mode, saved_tau = saved_relax["mode"], (float(saved_relax["tau"][0]), float(saved_relax["tau"][1]), int(saved_relax["tau"][2]))
         flag_mode, flag_tau = self._relax_flags
+        saved_score = saved_relax.get("gradient")
+        flag_kind, flag_base, flag_ent = self._score_flags
+        if flag_kind is not None and flag_kind != (saved_score or {"kind": "pathwise"})["kind"]:
+            raise ValueError("--generator_gradient %s contradicts the checkpoint, which was trained with the %s update"
+                             % (flag_kind, (saved_score or {"kind": "pathwise"})["kind"]))
+        if saved_score and flag_base is not None and flag_base != saved_score["baseline"]:
+            raise ValueError("--score_baseline %s contradicts the checkpoint's %s" % (flag_base, saved_score["baseline"]))
+        if saved_score and flag_ent is not None and float(flag_ent) != float(saved_score["entropy_weight"]):
+            raise ValueError("--entropy_weight %g contradicts the checkpoint's %g" % (flag_ent, saved_score["entropy_weight"]))
         if flag_mode is not None and flag_mode != saved_mode:
             raise ValueError("--generator_output %s contradicts the checkpoint, which was trained with %s" % (flag_mode, saved_mode))
         if flag_tau is not None and saved_mode != "logits" and flag_tau != saved_tau:
@@ -444,6 +495,7 @@ class SceneGraphGAN(object):
             raise ValueError("--relax_hard contradicts the checkpoint, which was trained %s"
                              % ("on the raw logits" if saved_mode == "logits" else "with soft %s rows" % saved_mode))
         self.relax_mode, self.relax_tau, self.relax_hard = saved_mode, saved_tau, bool(saved_relax.get("hard"))
+        self.score = dict(saved_score) if saved_score else None
         self.g.load_state_dict(ck["G"])
         self.d.load_state_dict(ck["D"])
         for net, key in ((self.step.G, "G_adam"), (self.step.D, "D_adam")):
@@ -603,6 +655,8 @@ class SceneGraphGAN(object):
                 C = self.CRITIC_ITERS
                 # relaxed generator output: this iteration's temperature, and per launch a draw number made of (itr, update, micro-batch)
                 tau = self._set_relaxation(self.step, self.itr) if (self.relaxed and not pre) else None
+                if self.score and not pre:  # (behind the relaxation it needs; a pathwise run never calls it)
+                    self.step.set_estimator("score", self.score["baseline"], self.score["entropy_weight"])
                 draw = (lambda i: {"draw": relax_draw(self.itr, i, 0, C, 1)}) if self.relax_mode == "gumbel" else (lambda i: {})
                 if pre:
                     for k, (im, lb) in enumerate(batches if N > 1 else [(images, labels)]):
@@ -642,6 +696,10 @@ class SceneGraphGAN(object):
                             rec.update(mle)
                         if tau is not None:
                             rec["relax"] = dict({"mode": self.relax_mode, "tau": tau}, **self._hard_key())
+                        if self.score:
+                            sc = self.step.score_losses_mean.cpu().tolist()
+                            rec["score"] = {"reward": sc[0], "adv_rms": math.sqrt(max(sc[1], 0.0)), "logp_token": sc[2], "entropy_token": sc[3],
+                                            "baseline": self.score["baseline"], "entropy_weight": self.score["entropy_weight"]}
                     if N > 1:
                         rec["accumulate"] = N
                     if self.guarded:        # the records of each network's last update and the clipped / skipped counts so far
@@ -1390,6 +1448,18 @@ def build_parser():
                              "onehot(argmax(x + g)) in both updates and the generator's update takes the gradient of the soft row, rebuilt "
                              "from the logits and the same noise.  Recorded in the checkpoint and taken from there on --resume and at "
                              "evaluation, where the critic scores onehot(argmax(x)): the row of the reported token")
+    parser.add_argument("--generator_gradient", default=None, choices=list(GRADIENTS),
+                        help="how the generator's update gets its gradient: pathwise = through the critic's gradient of its input; "
+                             "score = the score-function (REINFORCE) estimator on triples sampled from softmax(x) - unbiased, no "
+                             "gradient through the critic.  score implies --generator_output gumbel --relax_hard and takes no "
+                             "--relax_tau.  Recorded in the checkpoint and taken from there on --resume and at evaluation "
+                             "(default: pathwise for a fresh run)")
+    parser.add_argument("--score_baseline", default=None, choices=list(SCORE_BASELINES),
+                        help="with --generator_gradient score: rloo = each sample's reward minus the mean reward of the other samples "
+                             "of its (micro-)batch; none = the reward itself (default rloo)")
+    parser.add_argument("--entropy_weight", default=None, type=float, metavar="W",
+                        help="with --generator_gradient score: W >= 0 adds W x the mean entropy of the decoder rows to what the "
+                             "generator maximises (default 0)")
     parser.add_argument("--seed", default=0, type=int,
                         help="the run's seed: the example stream, the noise streams and the Gumbel noise's key derive from it (default 0)")
     parser.add_argument("--relax_tau", default=None, metavar="T | T0,T1,N",
@@ -1419,6 +1489,12 @@ def parse_args(argv=None):
         parser.error("--mle_weight must be a finite number >= 0")
     if args.relax_hard and args.generator_output == "logits":
         parser.error("--relax_hard needs --generator_output softmax or gumbel")
+    try:
+        check_score_flags(args.generator_gradient, args.score_baseline, args.entropy_weight, args.generator_output, args.relax_tau)
+    except ValueError as e:
+        parser.error("--" + str(e))
+    if args.generator_gradient == "score":
+        args.generator_output, args.relax_hard = "gumbel", True
     if args.relax_tau is not None:
         try:
             args.relax_tau = parse_relax_tau(args.relax_tau)
@@ -1445,7 +1521,9 @@ if __name__ == "__main__":
                         clip_grad_norm=params["clip_grad_norm"], skip_nonfinite=params["skip_nonfinite"],
                         pretrain_iterations=params["pretrain_iterations"], mle_weight=params["mle_weight"],
                         validate_nll=params["validate_nll"], generator_output=params["generator_output"],
-                        relax_tau=params["relax_tau"], relax_hard=params["relax_hard"], seed=params["seed"])
+                        relax_tau=params["relax_tau"], relax_hard=params["relax_hard"], seed=params["seed"],
+                        generator_gradient=params["generator_gradient"], score_baseline=params["score_baseline"],
+                        entropy_weight=params["entropy_weight"])
     if params["likelihood_out"]:
         if not gan.load_checkpoint():
             print("--likelihood_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
