@@ -128,6 +128,10 @@ def test_embed_gather_equals_dense_onehot_product(hip, ref, V):
     assert float(XH[0, 512:812].abs().max()) == 0.0
 
 
+LN448_DBIAS_MEASURED = 3.327e-4      # max|hip - fp64| of dbias_prev in the test below, MI355X (max|dbias_ref| 829.0)
+LN448_DBIAS_ATOL = 10 * LN448_DBIAS_MEASURED
+
+
 def test_layernorm_448px_6M_elements_per_sample(hip, ref):
     shape = (2, 448, 448, 32)
     B, H, W, C = shape
@@ -152,6 +156,12 @@ def test_layernorm_448px_6M_elements_per_sample(hip, ref):
     close(dy, dy_ref, rtol=5e-5, what="LN bwd dy")
     close(dg, dg_ref, rtol=5e-5, what="LN dgamma (6.4 M terms per sample)")
     close(db, db_ref, rtol=5e-5, what="LN dbeta")
+    # the producing convolution's bias gradient, a cancelling combination of the per-sample sums: measured max|hip - fp64|
+    # LN448_DBIAS_MEASURED on an MI355X; atol = 10 x that, and never above 1e-3 * max|dbias_ref|
+    dbias_max = float(dbias_ref.abs().max())
+    print("LN dbias_prev: max|hip - fp64| %.3e, max|ref| %.3e" % (float((dbias.cpu().double() - dbias_ref).abs().max()), dbias_max))
+    assert LN448_DBIAS_ATOL <= 1e-3 * dbias_max
+    close(dbias, dbias_ref, rtol=0.0, atol=LN448_DBIAS_ATOL, what="LN dbias_prev")
 
 
 def tensor_err(a, b):
