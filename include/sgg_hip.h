@@ -396,7 +396,9 @@ int sgg_adam_tf_multi_guarded(float* params, const float* grads, float* m, float
 int sgg_adam_tf_multi_ema_guarded(float* params, const float* grads, float* m, float* v, float* ema, long long n, float lr_t,
                                   float beta1, float beta2, float eps, const double* record, float one_minus_decay, void* stream);
 
-/* ---- tf.argmax(x, axis=-1): train.py:270-271 ---------------------------------------------------------------- */
+/* ---- tf.argmax(x, axis=-1): train.py:270-271 ----------------------------------------------------------------
+ * out[r] = the first index of the maximum over the non-NaN entries of row r (x + r * ld, V entries, ld >= V).  A NaN entry is never
+ * selected; a row without a non-NaN entry gives 0: every token is in [0, V). */
 int sgg_argmax_rows(const float* x, long long* out, int rows, int V, int ld, void* stream);
 
 /* ---- scene-graph prediction: score_accumulator.argsort() and the top-k selection, train.py:314-327 -----------

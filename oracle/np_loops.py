@@ -92,9 +92,10 @@ def tf_adam(theta, g, m, v, t, lr=1e-4, b1=0.5, b2=0.9, eps=1e-8):
 def argmax_first(x):
     out = np.zeros(x.shape[:-1], dtype=np.int64)
     for idx in np.ndindex(*x.shape[:-1]):
-        best, bi = -np.inf, 0
+        best, bi = None, 0                                   # (no non-NaN entry seen yet; such a row gives 0)
         for k in range(x.shape[-1]):
-            if x[idx + (k,)] > best:
-                best, bi = x[idx + (k,)], k
+            v = x[idx + (k,)]
+            if v == v and (best is None or v > best):        # (a NaN entry is never selected)
+                best, bi = v, k
         out[idx] = bi
     return out

@@ -249,11 +249,16 @@ def g_loss(gp, dp, images, noise):
 
 
 def argmax_tokens(logits: torch.Tensor) -> torch.Tensor:
-    """tf.argmax(x, -1) (train.py:270): int64, first index on ties (A.9)."""
+    """tf.argmax(x, -1) (train.py:270): int64, first index on ties (A.9).  NaN rule (the one of sgg_argmax_rows): the maximum is
+    taken over the row's non-NaN entries, so a NaN entry is never selected; a row without a non-NaN entry gives 0.  Every token is
+    in [0, V)."""
     V = logits.shape[-1]
-    mx = logits.max(dim=-1, keepdim=True).values
+    valid = ~torch.isnan(logits)
+    x = torch.where(valid, logits, torch.full_like(logits, float("-inf")))
+    mx = x.max(dim=-1, keepdim=True).values
     idx = torch.arange(V, dtype=torch.int64).expand_as(logits)
-    return torch.where(logits == mx, idx, torch.full_like(idx, V)).min(dim=-1).values
+    first = torch.where(valid & (x == mx), idx, torch.full_like(idx, V)).min(dim=-1).values
+    return torch.where(first == V, torch.zeros_like(first), first)
 
 
 def top2_margin(logits: torch.Tensor) -> float:

@@ -1,7 +1,7 @@
 // Loss and utility kernels of the WGAN-GP step (gfx950); the optimiser's passes are in csrc/optim.hip.
 //   wgan_gp_loss_{fwd,bwd}  tfgan wasserstein_gradient_penalty(one_sided=True, epsilon=1e-10), train.py:249-250 (Appendix A.7)
 //   wgan_losses             wasserstein_{generator,discriminator}_loss, train.py:247-248 (Appendix A.6)
-//   argmax_rows             tf.argmax(x, -1), train.py:270-271: int64, first index on ties
+//   argmax_rows             tf.argmax(x, -1), train.py:270-271: int64, first index on ties, NaN entries never selected
 #include "sgg_common.h"
 #include <stdarg.h>
 #include <stdio.h>
@@ -111,7 +111,9 @@ __global__ __launch_bounds__(256) void wgan_losses_kernel(const float* __restric
   }
 }
 
-// one wave per row
+// one wave per row.  out[row] = the first index of the maximum over the row's non-NaN entries (argmax_merge's comparisons are false
+// for a NaN, so a NaN entry is never selected); a row without a non-NaN entry leaves the start pair untouched and gives 0.  The result
+// is in [0, V) for every input: it goes into onehot, embed_gather and the keys of the triple ranking.
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, long long* __restrict__ out, int rows, int V,
                                                           int ld) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
     argmax_merge(best, bi, v, i);
   }
   wave_argmax(best, bi);
-  if (lane == 0) out[row] = (long long)bi;
+  if (lane == 0) out[row] = bi == 0x7fffffff ? 0ll : (long long)bi;
 }
 
 // amax[0] = max(amax[0], max |x|)   (caller zeroes amax first); used to scale tensors for the f16x3 conv mode

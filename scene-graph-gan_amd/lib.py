@@ -848,7 +848,7 @@ class HipKernels:
     # -- loss / optimiser / misc -----------------------------------------------------------------------
     def onehot(self, labels, out):
         self._dev(labels, out)
-        assert labels.dtype == torch.int64
+        assert labels.dtype == torch.int64 and labels.is_contiguous() and out.is_contiguous()
         V = out.shape[-1]
         self._check(self.lib.sgg_onehot(_p(labels), _p(out), labels.numel(), V, self._stream()), "sgg_onehot")
 
@@ -881,24 +881,28 @@ class HipKernels:
 
     def interpolate(self, real, fake, alpha, out):
         self._dev(real, fake, alpha, out)
+        assert real.is_contiguous() and fake.is_contiguous() and alpha.is_contiguous() and out.is_contiguous()
         B = real.shape[0]
         self._check(self.lib.sgg_interpolate(_p(real), _p(fake), _p(alpha), _p(out), B, real.numel() // B, self._stream()),
                     "sgg_interpolate")
 
     def gp_fwd(self, g, slopes, pen):
         self._dev(g, slopes, pen)
+        assert g.is_contiguous() and slopes.is_contiguous() and pen.is_contiguous()
         B = g.shape[0]
         self._check(self.lib.sgg_wgan_gp_loss_fwd(_p(g), _p(slopes), _p(pen), B, g.numel() // B, self._stream()),
                     "sgg_wgan_gp_loss_fwd")
 
     def gp_bwd(self, g, slopes, pen, v, scale):
         self._dev(g, slopes, pen, v)
+        assert g.is_contiguous() and slopes.is_contiguous() and pen.is_contiguous() and v.is_contiguous()
         B = g.shape[0]
         self._check(self.lib.sgg_wgan_gp_loss_bwd(_p(g), _p(slopes), _p(pen), _p(v), B, g.numel() // B, float(scale),
                                                   self._stream()), "sgg_wgan_gp_loss_bwd")
 
     def wgan_losses(self, d_out, pen, lam, B, T, has_real, out4):
         self._dev(d_out, pen, out4)
+        assert d_out.is_contiguous() and (pen is None or pen.is_contiguous()) and out4.is_contiguous()
         self._check(self.lib.sgg_wgan_losses(_p(d_out), _p(pen), float(lam), B, T, int(has_real), _p(out4), self._stream()),
                     "sgg_wgan_losses")
 
@@ -1019,6 +1023,8 @@ class HipKernels:
         return out
 
     def argmax_rows(self, x, out):
+        """out[r] = the first index of the maximum over the non-NaN entries of row r of x [..., V] (rows may be strided); a NaN entry is
+        never selected, a row without a non-NaN entry gives 0: every token is in [0, V) (oracle.sgg_oracle.argmax_tokens)."""
         self._dev(x, out)
         assert x.stride(-1) == 1 and out.dtype == torch.int64
         V = x.shape[-1]

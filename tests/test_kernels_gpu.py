@@ -324,6 +324,7 @@ def test_lnlstm_gates(hip, ref, R, dual):
 
 
 def test_spatial_mean_colsum(hip, ref):
+    # (one toy shape; the feature maps' L = 196 / 784, L < 8, C % 128 != 0 and overwrite mode: tests/test_loss_geometry_gpu.py)
     B, L, C, npass = 3, 16, 512, 2
     R = B * npass
     ctx = rnd((B, L, C), 60)
@@ -347,6 +348,7 @@ def test_spatial_mean_colsum(hip, ref):
 
 
 def test_loss_adam_argmax(hip, ref):
+    # (one toy shape; the loss, fill and argmax kernels at the step's launch geometry, per element: tests/test_loss_geometry_gpu.py)
     B, T, V = 8, 3, 50
     labels = torch.randint(0, V, (B, T), generator=g(70))
     oh = torch.empty((B, T, V), device="cuda")

@@ -83,6 +83,31 @@ def test_argmax_first_index_A9():
     assert NL.argmax_first(x.numpy()).tolist() == [1, 0, 0]
 
 
+def test_argmax_nan_rule():
+    """The rule of sgg_argmax_rows: the maximum over the non-NaN entries (a NaN entry is never selected), 0 for a row without one,
+    always a token in [0, V)."""
+    nan, inf = float("nan"), float("inf")
+    rows = [([nan, 1.0, 3.0, 3.0], 2),          # a NaN in front of the maximum
+            ([2.0, nan, 1.0, nan], 0),          # NaNs behind it
+            ([1.0, nan, 5.0, 5.0], 2),
+            ([nan, nan, nan, nan], 0),          # no non-NaN entry
+            ([nan, -inf, -inf, nan], 1),        # the maximum of the non-NaN entries is -inf: its first index, not the NaN in front
+            ([-inf, -inf, -inf, -inf], 0),
+            ([nan, nan, nan, -7.0], 3),
+            ([inf, nan, inf, 0.0], 0)]
+    x = torch.tensor([r for r, _ in rows])
+    want = [k for _, k in rows]
+    for t in (x, x.double(), x.reshape(2, 4, 4)):
+        got = O.argmax_tokens(t)
+        assert got.dtype == torch.int64 and got.reshape(-1).tolist() == want
+    assert NL.argmax_first(x.numpy()).tolist() == want
+    # rows without a NaN: torch.argmax's first-index variant agrees on random rows with ties
+    g = torch.Generator().manual_seed(5)
+    y = torch.randint(0, 4, (64, 9), generator=g).float()
+    first = torch.stack([(r == r.max()).nonzero()[0, 0] for r in y])
+    assert torch.equal(O.argmax_tokens(y), first) and NL.argmax_first(y.numpy()).tolist() == first.tolist()
+
+
 def test_numpy_loop_restatement_agrees():
     g = torch.Generator().manual_seed(0)
     for (H, W, Ci, Co, k, s) in [(5, 6, 3, 4, 3, 1), (6, 6, 2, 3, 5, 2), (7, 5, 2, 2, 5, 2)]:
