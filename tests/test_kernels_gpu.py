@@ -378,6 +378,7 @@ def test_loss_adam_argmax(hip, ref):
     ref.wgan_losses(d_out.double(), penr, 10.0, B, T, True, o4)
     close(out4, o4, what="wgan_losses")
     # TF Adam, 3 steps, odd length (tail path)
+    # (one toy size; the four Adam kernels per element against fp64 at the arena's launch geometry: tests/test_optim_geometry_gpu.py)
     n = 4099
     p, gg = rnd((n,), 75), rnd((n,), 76, 0.1)
     pr, mr, vr_ = p.double().clone(), torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
@@ -390,6 +391,7 @@ def test_loss_adam_argmax(hip, ref):
         ref.adam(pr, gg.double(), mr, vr_, lr_t, O.ADAM_B1, O.ADAM_B2, O.ADAM_EPS)
     close(pd, pr, rtol=1e-6, what="adam params")
     close(md, mr, rtol=1e-5, what="adam m")
+    close(vd, vr_, rtol=1e-5, atol=0.0, what="adam v")
     # argmax with ties: first index wins
     x = rnd((B * T, V), 77)
     x[0, 7] = x[0, 31] = 100.0
