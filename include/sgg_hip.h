@@ -552,6 +552,34 @@ int sgg_score_rows(const float* x, long long ldx, int R, int V, const long long*
                    float ent_coef, int accumulate, float* dx, long long lddx, float* logp, float* ent, void* stream);
 int sgg_score_summary(const float* logp, const float* ent, int R, float* out2, void* stream);
 
+/* ---- score-function update with S samples per row (csrc/score.hip) -------------------------------------------------------------
+ * S Gumbel-max samples of every decoder row in one launch, advantages against the other samples of the same image, one gradient
+ * launch for all of them.  Layout everywhere: sample s of logits row r sits at index s * R + r (with R = B * T rows a sample's
+ * tokens are a contiguous [B][T] block, and critic row s * B + b scores sample s of image b).  1 <= S <= 16.  No workspace, no
+ * float atomic, fixed summation orders: two calls give the same bits; anything outside the stated ranges is refused without a launch.
+ * sgg_sample_rows_multi: tok int64 [S][R]; tok[s][r] = the first argmax_j of x[r][j] + g_j with g drawn as sgg_relax_rows draws it at
+ *   draw number draw | (s << 56) - bit for bit the tok of sgg_relax_rows_hard(gumbel = 1, seed, draw | (s << 56)); draw < 2^56.  A row
+ *   of V <= 1024 stays in registers for all S draws; a longer row is read once for S <= 8 and twice for S <= 16.  No one-hot row is
+ *   written and no load or store is addressed by a token.  1 <= R <= 2^24, 1 <= V <= 2^21, ldx >= V.
+ * sgg_score_advantage_multi: one workgroup.  d_out fp32 [S * B][T], rows ldd >= T apart; r[s][b] = (sum_t d_out[s * B + b][t]) / T in
+ *   fp32 in order of t.  baseline = 0 (none): adv = r.  1 (leave-one-out over all): adv[n] = r_n - (sum_all - r_n) / (S * B - 1), it
+ *   needs S * B >= 2.  2 (image): adv[s][b] = r[s][b] - (sum_s' r[s'][b] - r[s][b]) / (S - 1), the reward against the mean of the
+ *   OTHER samples of the same image; it needs S >= 2, B = 1 is allowed.  Sums in fp64 in index order.  adv fp32 [S * B]; out2
+ *   (optional) fp32 = { mean r, mean adv^2 } over S * B.  1 <= B <= 2^20, 1 <= T <= 64.
+ * sgg_score_rows_multi: x, lse, p, H_r, dx, accumulate, ent as sgg_score_rows.  tok int64 [S][R]; w_s = coef * adv[s * (R / group) +
+ *   r / group] (adv = NULL: coef); R % group == 0.  With the sum over the samples s whose token a_s lies in [0, V):
+ *   dx[r][j] = (sum_s w_s) p_j - sum_s w_s [j == a_s] + ent_coef * p_j ((x_j - lse) + H_r); logp fp32 [S][R]: logp[s][r] = x_{a_s} - lse.
+ *   A token sampled twice counts twice.  A token outside [0, V) drops that sample's term alone (its logp = 0): the other samples'
+ *   terms, the entropy term and the row's store stay.  The S tokens of a row are read once and address no load or store.
+ * sgg_score_summary_multi: one workgroup.  out2 fp32 = { mean of logp[0 .. n_logp), mean of ent[0 .. n_ent) }, fp64 sums in index
+ *   order.  1 <= n_logp <= 2^28, 1 <= n_ent <= 2^24. */
+int sgg_sample_rows_multi(const float* x, long long ldx, int R, int V, int S, unsigned long long seed, unsigned long long draw,
+                          long long* tok, void* stream);
+int sgg_score_advantage_multi(const float* d_out, long long ldd, int B, int S, int T, int baseline, float* adv, float* out2, void* stream);
+int sgg_score_rows_multi(const float* x, long long ldx, int R, int V, int S, const long long* tok, const float* adv, int group, float coef,
+                         float ent_coef, int accumulate, float* dx, long long lddx, float* logp, float* ent, void* stream);
+int sgg_score_summary_multi(const float* logp, int n_logp, const float* ent, int n_ent, float* out2, void* stream);
+
 /* ---- training diagnostics: per-tensor norms and non-finite counts of a network's arenas (csrc/stats.hip) ----------------------
  * One read-only streaming pass over params, grads, m and v: fp32 arenas of ONE layout, every tensor 16-byte aligned and rounded up
  * to 4 elements (the arena ends on such a boundary), as sgg_adam_tf_multi takes them.

@@ -104,6 +104,10 @@ SIGNATURES = {
     "sgg_score_advantage": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _vp]),
     "sgg_score_rows": (_i, [_vp, _ll, _i, _i, _vp, _vp, _i, _f, _f, _i, _vp, _ll, _vp, _vp, _vp]),
     "sgg_score_summary": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "sgg_sample_rows_multi": (_i, [_vp, _ll, _i, _i, _i, _ull, _ull, _vp, _vp]),
+    "sgg_score_advantage_multi": (_i, [_vp, _ll, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sgg_score_rows_multi": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _i, _f, _f, _i, _vp, _ll, _vp, _vp, _vp]),
+    "sgg_score_summary_multi": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     "sgg_arena_stats_chunk": (_i, []),
     "sgg_arena_stats_nstat": (_i, []),
     "sgg_arena_stats_workspace_bytes": (_sz, [_i]),
@@ -1338,6 +1342,87 @@ class HipKernels:
             out2 = torch.empty(2, dtype=torch.float32, device=logp.device)
         assert out2.dtype == torch.float32 and out2.numel() == 2 and out2.is_contiguous()
         self._check(self.lib.sgg_score_summary(_p(logp), _p(ent), R, _p(out2), self._stream()), "sgg_score_summary")
+        return out2
+
+    # -- S samples per row (csrc/score.hip, "S samples per row"): sample s of logits row r sits at index s * R + r ---------------
+    SCORE_BASELINES_MULTI = {"none": 0, "rloo": 1, "image": 2}
+    SCORE_MAX_SAMPLES = 16
+
+    def sample_rows_multi(self, x, tok, seed=0, draw=0):
+        """S Gumbel-max samples of softmax(x) per row in one launch (include/sgg_hip.h): x fp32 [..., V] (R rows one stride apart), tok
+        contiguous int64 [S, ...] with S * R elements, S = tok.shape[0] in 1..16.  tok[s] is, bit for bit, the tok of
+        relax_rows_hard(x, tok=..., gumbel=True, seed=seed, draw=draw | (s << 56)); draw < 2^56.  The row is read once for S <= 8 and at
+        most twice above; no one-hot row is written.  Returns tok."""
+        self._dev(x, tok)
+        xv, ldx = self._rows(x, "x")
+        R, V = int(xv.shape[0]), int(xv.shape[1])
+        assert tok.dtype == torch.int64 and tok.dim() >= 1 and tok.is_contiguous(), "tok: contiguous int64 [S, ...]"
+        S = int(tok.shape[0])
+        assert S < 1 or tok.numel() == S * R, "tok: one token per sample and row (S * R = %d elements, got %d)" % (S * R, tok.numel())
+        self._check(self._timed("sample_rows_multi_%s_kernel" % ("resident" if V <= 1024 else "stream"), 0.0,
+                                lambda: self.lib.sgg_sample_rows_multi(_p(xv), ldx, R, V, S, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                                       int(draw) & 0xFFFFFFFFFFFFFFFF, _p(tok), self._stream()),
+                                4.0 * R * V * (1 if S <= 8 or V <= 1024 else 2)), "sgg_sample_rows_multi")
+        return tok
+
+    def score_advantage_multi(self, d_out, samples, baseline="image", adv=None, out2=None):
+        """Rewards and advantages of S = samples sampled triples per image: d_out fp32 [S * B, T] (rows one stride apart; row s * B + b
+        = sample s of image b), r = the row means; adv fp32 [S * B] = r ("none"), r minus the mean of the other S * B - 1 rewards
+        ("rloo"), or r[s, b] minus the mean reward of the other samples of image b ("image": S >= 2).  out2 (optional) fp32 [2] =
+        (mean reward, mean advantage^2).  One workgroup.  Returns adv."""
+        if baseline not in self.SCORE_BASELINES_MULTI:
+            raise ValueError("score_advantage_multi: baseline must be one of %s (got %r)" % (", ".join(sorted(self.SCORE_BASELINES_MULTI)), baseline))
+        self._dev(d_out, adv, out2)
+        assert d_out.dim() == 2, "d_out must be [S * B, T]"
+        dv, ldd = self._rows(d_out, "d_out")
+        N, T, S = int(dv.shape[0]), int(dv.shape[1]), int(samples)
+        assert S < 1 or N % S == 0, "d_out has %d rows: not S = %d samples of every image" % (N, S)
+        if adv is None:
+            adv = torch.empty(N, dtype=torch.float32, device=d_out.device)
+        assert adv.dtype == torch.float32 and adv.numel() == N and adv.is_contiguous(), "adv: contiguous fp32, one per row of d_out"
+        assert out2 is None or (out2.dtype == torch.float32 and out2.numel() == 2 and out2.is_contiguous()), "out2: contiguous fp32 [2]"
+        self._check(self.lib.sgg_score_advantage_multi(_p(dv), ldd, N // max(S, 1), S, T, self.SCORE_BASELINES_MULTI[baseline], _p(adv),
+                                                       _p(out2), self._stream()), "sgg_score_advantage_multi")
+        return adv
+
+    def score_rows_multi(self, x, tok, adv=None, group=1, coef=1.0, ent_coef=0.0, accumulate=False, dx=None, logp=None, ent=None):
+        """The policy gradient of S sampled tokens per row in one launch: x fp32 [..., V] (R rows one stride apart), tok contiguous
+        int64 [S, ...] (S * R elements), adv fp32 with S * (R / group) elements (None: every weight is coef; R % group == 0).  Outputs,
+        each optional (not all absent): dx (x's rows, its own stride; never x itself) = (sum_s w_s) softmax - sum_s w_s onehot(tok_s)
+        + ent_coef * softmax * (log softmax + H) with w_s = coef * adv[s * (R / group) + r // group], stored or - accumulate - added;
+        logp fp32 [S * R] = log softmax(x)[tok_s]; ent fp32 [R] = H.  A token outside [0, V) drops that sample's term alone (logp 0)."""
+        self._dev(x, tok, adv, dx, logp, ent)
+        xv, ldx = self._rows(x, "x")
+        R, V = int(xv.shape[0]), int(xv.shape[1])
+        group = int(group)
+        assert tok.dtype == torch.int64 and tok.dim() >= 1 and tok.is_contiguous(), "tok: contiguous int64 [S, ...]"
+        S = int(tok.shape[0])
+        assert S < 1 or tok.numel() == S * R, "tok: one token per sample and row (S * R = %d elements, got %d)" % (S * R, tok.numel())
+        if adv is not None:
+            assert adv.dtype == torch.float32 and adv.is_contiguous(), "adv: contiguous fp32"
+            assert group < 1 or adv.numel() >= S * (R // group), "adv needs S * (R / group) = %d elements (got %d)" % (S * (R // max(group, 1)), adv.numel())
+        dv, lddx = None, 0
+        if dx is not None:
+            dv, lddx = self._rows(dx, "dx")
+            assert tuple(dv.shape) == (R, V), "dx must have x's rows"
+        assert logp is None or (logp.dtype == torch.float32 and logp.numel() == S * R and logp.is_contiguous()), "logp: contiguous fp32 [S * R]"
+        assert ent is None or (ent.dtype == torch.float32 and ent.numel() == R and ent.is_contiguous()), "ent: contiguous fp32, one per row"
+        nb = 4.0 * R * V * (1 + (0 if dx is None else (2 if accumulate else 1)))
+        self._check(self._timed("score_rows_multi_%s_kernel" % ("resident" if V <= 1024 else "stream"), 0.0,
+                                lambda: self.lib.sgg_score_rows_multi(_p(xv), ldx, R, V, S, _p(tok), _p(adv), group, float(coef), float(ent_coef),
+                                                                      int(bool(accumulate)), _p(dv), lddx, _p(logp), _p(ent), self._stream()),
+                                nb), "sgg_score_rows_multi")
+        return dx
+
+    def score_summary_multi(self, logp, ent, out2=None):
+        """out2 fp32 [2] = (mean logp, mean ent) of score_rows_multi's outputs (S * R and R values); one workgroup, fp64, index order."""
+        self._dev(logp, ent, out2)
+        assert logp.dtype == torch.float32 and ent.dtype == torch.float32 and logp.is_contiguous() and ent.is_contiguous()
+        if out2 is None:
+            out2 = torch.empty(2, dtype=torch.float32, device=logp.device)
+        assert out2.dtype == torch.float32 and out2.numel() == 2 and out2.is_contiguous()
+        self._check(self.lib.sgg_score_summary_multi(_p(logp), logp.numel(), _p(ent), ent.numel(), _p(out2), self._stream()),
+                    "sgg_score_summary_multi")
         return out2
 
     def fill(self, t, value):

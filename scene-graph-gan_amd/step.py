@@ -366,7 +366,7 @@ class GanStep:
         # relaxed generator output (set_relaxation; csrc/relax.hip): None = the critic sees the raw decoder logits
         self._relax, self._relax_buf = None, None
         # score-function generator update (set_estimator; csrc/score.hip): None = the pathwise update, nothing of it is launched or allocated
-        self._estimator, self._score_bufs = None, None
+        self._estimator, self._score_bufs, self._score_multi_bufs = None, None, {}
         # (option side_priority: priority of the side streams - everything on them is off the critical chain of the main stream)
         prio = int(option(K, "side_priority"))
         self.side = torch.cuda.Stream(device=dev, priority=prio) if (overlap_streams and dev.type == "cuda") else None
@@ -541,7 +541,8 @@ class GanStep:
 
     # ---- score-function generator update (csrc/score.hip) ---------------------------------------------------
     ESTIMATORS = ("pathwise", "score")
-    SCORE_BASELINES = ("rloo", "none")
+    SCORE_BASELINES = ("rloo", "none", "image")
+    SCORE_MAX_SAMPLES = 16
 
     def _check_score_relaxation(self):
         rx = self._relax
@@ -550,7 +551,7 @@ class GanStep:
             raise ValueError("generator_gradient=score needs generator_output=gumbel with hard=True - the critic must see Gumbel-max "
                              "samples of softmax(logits) in both updates (the relaxation in force is generator_output=%s)" % have)
 
-    def set_estimator(self, kind="pathwise", baseline="rloo", entropy_weight=0.0):
+    def set_estimator(self, kind="pathwise", baseline=None, entropy_weight=0.0, samples=1):
         """How the generator's update gets its gradient.  "pathwise" (default): through the critic's gradient of its input, as
         set_relaxation describes - today's path, nothing new launched.  "score": the score-function (REINFORCE) estimator.  The critic
         scores the sampled one-hot rows (the relaxation must be "gumbel" with hard=True: tok is then an exact sample of
@@ -558,31 +559,57 @@ class GanStep:
             -(1/B) sum_b A_b sum_t log p(a_bt) - (entropy_weight / B) sum_{b,t} H(p_bt)
         with A_b a constant: the reward r_b = mean_t D(sample b)[t], minus - baseline "rloo" - the mean reward of the OTHER samples of
         the (micro-)batch, which leaves the estimator unbiased; "none": r_b itself.  entropy_weight >= 0: an entropy bonus on the
-        policy.  Four numbers of the update land in score_losses."""
+        policy.  Four numbers of the update land in score_losses.
+        samples = S >= 2 (at most 16): S triples per image are drawn from the one set of logits (draw numbers draw | (s << 56)), D's head
+        scores the S * B of them against the B feature maps, and the first term becomes
+            -(1/(B S)) sum_{b,s} A_sb sum_t log p(a_sbt).
+        baseline "image" (the default there; refused at S = 1): r_sb minus the mean reward of the other samples of the SAME image, which
+        takes the image's own difficulty out of the advantage and exists at B = 1; "rloo": minus the mean of the other S * B - 1 rewards.
+        The critic's updates keep one sample per image.  samples = 1 is the path above, call for call."""
         if kind not in self.ESTIMATORS:
             raise ValueError("generator_gradient must be one of %s (got %r)" % (", ".join(self.ESTIMATORS), kind))
         if kind == "pathwise":
             self._estimator = None
             return
+        S = int(samples)
+        if S != samples or not 1 <= S <= self.SCORE_MAX_SAMPLES:
+            raise ValueError("score_samples must be an integer in 1..%d (got %r)" % (self.SCORE_MAX_SAMPLES, samples))
+        if baseline is None:
+            baseline = "image" if S > 1 else "rloo"
         if baseline not in self.SCORE_BASELINES:
             raise ValueError("score_baseline must be one of %s (got %r)" % (", ".join(self.SCORE_BASELINES), baseline))
         entropy_weight = float(entropy_weight)
         if not (math.isfinite(entropy_weight) and entropy_weight >= 0.0):
             raise ValueError("entropy_weight must be a finite number >= 0 (got %r)" % entropy_weight)
         self._check_score_relaxation()
-        need_kernels(self.K, "generator_gradient=score", "score_advantage", "score_rows", "score_summary", "relax_rows_hard")
-        if baseline == "rloo" and self.B < 2:
+        if S == 1:
+            need_kernels(self.K, "generator_gradient=score", "score_advantage", "score_rows", "score_summary", "relax_rows_hard")
+        else:
+            need_kernels(self.K, "generator_gradient=score with score_samples > 1", "sample_rows_multi", "score_advantage_multi",
+                         "score_rows_multi", "score_summary_multi")
+        if baseline == "image" and S < 2:
+            raise ValueError("score_baseline=image compares each sample with the other samples of its image: it needs score_samples >= 2 "
+                             "(got %d)" % S)
+        if baseline == "rloo" and S * self.B < 2:
             raise ValueError("score_baseline=rloo compares each sample with the others of its batch: it needs B >= 2 (got B = %d)" % self.B)
-        if self._score_bufs is None:
-            dev, dt, R = self.g_losses.device, self.g_losses.dtype, self.B * T_STEPS
+        dev, dt, R = self.g_losses.device, self.g_losses.dtype, self.B * T_STEPS
+        if S == 1 and self._score_bufs is None:
             self._score_bufs = {"tok": torch.zeros((self.B, T_STEPS), dtype=torch.int64, device=dev), "adv": torch.zeros(self.B, dtype=dt, device=dev),
                                 "logp": torch.zeros(R, dtype=dt, device=dev), "ent": torch.zeros(R, dtype=dt, device=dev)}
+        if S > 1 and self._score_multi_bufs.get("S") != S:
+            self._score_multi_bufs = {"S": S, "tok": torch.zeros((S, self.B, T_STEPS), dtype=torch.int64, device=dev),
+                                      "adv": torch.zeros(S * self.B, dtype=dt, device=dev), "logp": torch.zeros(S * R, dtype=dt, device=dev),
+                                      "ent": torch.zeros(R, dtype=dt, device=dev)}
+        if getattr(self, "score_losses", None) is None:
             self.score_losses = torch.zeros(4, dtype=dt, device=dev)
         self._estimator = {"kind": "score", "baseline": baseline, "entropy_weight": entropy_weight}
+        if S > 1:
+            self._estimator["samples"] = S
 
     estimator = property(lambda self: {"kind": "pathwise"} if self._estimator is None else dict(self._estimator))
-    _score_tok = property(lambda self: self._score_bufs["tok"])
-    _score_adv = property(lambda self: self._score_bufs["adv"])
+    _score_now = property(lambda self: self._score_multi_bufs if (self._estimator or {}).get("samples", 1) > 1 else self._score_bufs)
+    _score_tok = property(lambda self: self._score_now["tok"])
+    _score_adv = property(lambda self: self._score_now["adv"])
 
     def critic_step(self, images, labels, noise, alpha, micro=None, draw=None):
         """One disc_train_op (train.py:365). labels int64 [B,3]; noise [B,512]; alpha [B]. Returns self.d_losses
@@ -755,6 +782,8 @@ class GanStep:
         one-hot rows, into g_losses; the gradient of the logits (G's dOUT) comes from the samples' log-probabilities weighted by their
         advantages, and the update's four numbers go into score_losses."""
         K, B, D = self.K, self.B, self.D
+        if score.get("samples", 1) > 1:
+            return self._score_logits_gradient_multi(score, gst, ctx, draw)
         fake, bufs, rx = gst.OUT[0], self._score_bufs, self._relax
         # one launch: the one-hot rows D scores and the tokens they are the rows of - Gumbel-max samples of softmax(fake)
         K.relax_rows_hard(fake, y=self._relax_buf, tok=bufs["tok"], gumbel=True, seed=rx["seed"], draw=int(draw or 0))
@@ -765,6 +794,22 @@ class GanStep:
         K.score_rows(fake, bufs["tok"].view(-1), bufs["adv"], group=T_STEPS, coef=1.0 / B, ent_coef=score["entropy_weight"] / B,
                      dx=gst.dOUT[0], logp=bufs["logp"], ent=bufs["ent"])
         K.score_summary(bufs["logp"], bufs["ent"], out2=self.score_losses[2:4])
+
+    def _score_logits_gradient_multi(self, score, gst, ctx, draw):
+        """_score_logits_gradient with S = score["samples"] >= 2 triples per image: one launch draws them all from G's logits, D's head
+        runs forward only on S * B rows against the B feature maps (row s * B + b reads image b) and takes the tokens as a row gather of
+        its embedding - no one-hot row exists -, and one launch turns the S * B advantages into the gradient of the B * 3 logits rows."""
+        K, B, D, S = self.K, self.B, self.D, score["samples"]
+        fake, bufs, rx = gst.OUT[0], self._score_multi_bufs, self._relax
+        assert bufs.get("S") == S
+        K.sample_rows_multi(fake, bufs["tok"], seed=rx["seed"], draw=int(draw or 0))
+        st = D.head.sample_state(S * B)
+        D.head.forward(st, ctx, [None], bufs["tok"].view(S * B, T_STEPS), (0, S * B))
+        K.wgan_losses(st.OUT[0].view(S * B, T_STEPS), None, 0.0, S * B, T_STEPS, False, self.g_losses)
+        K.score_advantage_multi(st.OUT[0].view(S * B, T_STEPS), S, score["baseline"], adv=bufs["adv"], out2=self.score_losses[0:2])
+        K.score_rows_multi(fake, bufs["tok"], bufs["adv"], group=T_STEPS, coef=1.0 / (B * S), ent_coef=score["entropy_weight"] / B,
+                           dx=gst.dOUT[0], logp=bufs["logp"], ent=bufs["ent"])
+        K.score_summary_multi(bufs["logp"], bufs["ent"], out2=self.score_losses[2:4])
 
     # ---- generator likelihood (csrc/xent.hip) -------------------------------------------------------------
     def _need_xent(self, what):

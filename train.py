@@ -12,6 +12,7 @@
     python train.py --generator_output gumbel --relax_tau 2,0.5,20000 ...  # the critic sees Gumbel-softmax rows, tau annealed
     python train.py --generator_output gumbel --relax_tau 1 --relax_hard ...  # straight-through: one-hot rows to the critic, soft gradient
     python train.py --generator_gradient score --entropy_weight 0.01 ...   # REINFORCE on sampled triples: no gradient through the critic
+    python train.py --generator_gradient score --score_samples 4 ...       # ... with 4 sampled triples per image and a per-image baseline
     python train.py --path_to_ims_to_triples ... --path_to_vocab ... --path_to_word_embeddings ...
 
 Reference: train.py:17-422.  Kept: constructor signature (:23-24), `_Generator` / `_Discriminator` wrappers with
@@ -113,12 +114,14 @@ def relax_draw(it, update, micro, critic_iters, accumulate):
 
 
 GRADIENTS = ("pathwise", "score")
-SCORE_BASELINES = ("rloo", "none")
+SCORE_BASELINES = ("rloo", "none", "image")
+SCORE_MAX_SAMPLES = 16
 
 
-def check_score_flags(generator_gradient, score_baseline, entropy_weight, generator_output, relax_tau):
-    """The combinations of --generator_gradient / --score_baseline / --entropy_weight with each other and with the relaxation's flags
-    that are refused (ValueError); returns (generator_gradient, score_baseline, entropy_weight) as given (None: not given)."""
+def check_score_flags(generator_gradient, score_baseline, entropy_weight, generator_output, relax_tau, score_samples=None):
+    """The combinations of --generator_gradient / --score_baseline / --entropy_weight / --score_samples with each other and with the
+    relaxation's flags that are refused (ValueError); returns (generator_gradient, score_baseline, entropy_weight, score_samples) as
+    given (None: not given)."""
     if generator_gradient is not None and generator_gradient not in GRADIENTS:
         raise ValueError("generator_gradient must be one of %s (got %r)" % (", ".join(GRADIENTS), generator_gradient))
     if score_baseline is not None and score_baseline not in SCORE_BASELINES:
@@ -127,16 +130,24 @@ def check_score_flags(generator_gradient, score_baseline, entropy_weight, genera
         entropy_weight = float(entropy_weight)
         if not (0.0 <= entropy_weight < float("inf")):
             raise ValueError("entropy_weight must be a finite number >= 0 (got %r)" % entropy_weight)
+    if score_samples is not None:
+        if isinstance(score_samples, bool) or int(score_samples) != score_samples or not 1 <= int(score_samples) <= SCORE_MAX_SAMPLES:
+            raise ValueError("score_samples must be an integer in 1..%d (got %r)" % (SCORE_MAX_SAMPLES, score_samples))
+        score_samples = int(score_samples)
     if generator_gradient != "score":
         if score_baseline is not None or entropy_weight is not None:
             raise ValueError("score_baseline and entropy_weight belong to generator_gradient score")
+        if score_samples is not None:
+            raise ValueError("score_samples belongs to generator_gradient score")
     else:
+        if score_baseline == "image" and (score_samples or 1) < 2:
+            raise ValueError("score_baseline image compares the samples of one image: it needs score_samples >= 2")
         if generator_output in ("logits", "softmax"):
             raise ValueError("generator_gradient score implies generator_output gumbel with relax_hard: the critic must see samples of "
                              "softmax(logits) (got generator_output %s)" % generator_output)
         if relax_tau is not None:
             raise ValueError("relax_tau has no meaning with generator_gradient score: no temperature enters either update")
-    return generator_gradient, score_baseline, entropy_weight
+    return generator_gradient, score_baseline, entropy_weight, score_samples
 
 
 def relax_val_draw(k):
@@ -154,7 +165,7 @@ class SceneGraphGAN(object):
                  synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True,
                  ema_decay=0.0, eval_live=False, accumulate=1, clip_grad_norm=0.0, skip_nonfinite=False,
                  pretrain_iterations=0, mle_weight=0.0, validate_nll=False, generator_output=None, relax_tau=None, relax_hard=False,
-                 generator_gradient=None, score_baseline=None, entropy_weight=None):
+                 generator_gradient=None, score_baseline=None, entropy_weight=None, score_samples=None):
         # Hyperparameters (train.py:26-32)
         self.CRITIC_ITERS = int(critic_iters)
         self.BATCH_SIZE = int(batch_size)
@@ -212,12 +223,18 @@ class SceneGraphGAN(object):
         # generator_gradient = "score": the generator's update is the score-function (REINFORCE) estimator on the sampled triples
         # (GanStep.set_estimator) - it implies generator_output gumbel with relax_hard (the critic sees Gumbel-max samples of
         # softmax(logits) in both updates) and takes no temperature; score_baseline "rloo" (default) | "none", entropy_weight >= 0.
-        # None = not given: pathwise for a fresh run; a resumed run or an evaluation takes all three from the checkpoint.
-        self._score_flags = check_score_flags(generator_gradient, score_baseline, entropy_weight, generator_output, relax_tau)
+        # score_samples = S in 1..16 (default 1): S triples per image in the generator's update, score_baseline "image" (the default
+        # for S > 1) = against the other samples of the same image; the dict carries "samples" only when S > 1.
+        # None = not given: pathwise for a fresh run; a resumed run or an evaluation takes all four from the checkpoint.
+        self._score_flags = check_score_flags(generator_gradient, score_baseline, entropy_weight, generator_output, relax_tau, score_samples)
         self.score = None
         if generator_gradient == "score":
             generator_output, relax_hard = "gumbel", True
-            self.score = {"kind": "score", "baseline": score_baseline or "rloo", "entropy_weight": float(entropy_weight or 0.0)}
+            S = self._score_flags[3] or 1
+            self.score = {"kind": "score", "baseline": score_baseline or ("image" if S > 1 else "rloo"),
+                          "entropy_weight": float(entropy_weight or 0.0)}
+            if S > 1:
+                self.score["samples"] = S
         self._relax_flags = (generator_output, None if relax_tau is None else parse_relax_tau(relax_tau))
         self.relax_mode = generator_output or "logits"
         # relax_hard: the straight-through estimator on top of "softmax" or "gumbel" - the critic sees onehot(argmax(logits [+ noise])),
@@ -405,7 +422,8 @@ class SceneGraphGAN(object):
     def _relax_label(self):
         """The "generator_output" entry of an evaluation's JSON output."""
         return dict({"mode": self.relax_mode, "tau": relax_tau_at(self.relax_tau, self.itr)}, **self._hard_key(),
-                    **({"gradient": "score"} if self.score else {}))
+                    **({"gradient": "score"} if self.score else {}),
+                    **({"samples": self.score["samples"]} if self.score and self.score.get("samples", 1) > 1 else {}))
 
     def _ensure_val_step(self, images):
         if self.val_step is None:
@@ -478,7 +496,7 @@ class SceneGraphGAN(object):
         saved_mode, saved_tau = saved_relax["mode"], (float(saved_relax["tau"][0]), float(saved_relax["tau"][1]), int(saved_relax["tau"][2]))
         flag_mode, flag_tau = self._relax_flags
         saved_score = saved_relax.get("gradient")
-        flag_kind, flag_base, flag_ent = self._score_flags
+        flag_kind, flag_base, flag_ent, flag_samples = self._score_flags
         if flag_kind is not None and flag_kind != (saved_score or {"kind": "pathwise"})["kind"]:
             raise ValueError("--generator_gradient %s contradicts the checkpoint, which was trained with the %s update"
                              % (flag_kind, (saved_score or {"kind": "pathwise"})["kind"]))
@@ -486,6 +504,8 @@ class SceneGraphGAN(object):
             raise ValueError("--score_baseline %s contradicts the checkpoint's %s" % (flag_base, saved_score["baseline"]))
         if saved_score and flag_ent is not None and float(flag_ent) != float(saved_score["entropy_weight"]):
             raise ValueError("--entropy_weight %g contradicts the checkpoint's %g" % (flag_ent, saved_score["entropy_weight"]))
+        if saved_score and flag_samples is not None and flag_samples != int(saved_score.get("samples", 1)):
+            raise ValueError("--score_samples %d contradicts the checkpoint's %d" % (flag_samples, int(saved_score.get("samples", 1))))
         if flag_mode is not None and flag_mode != saved_mode:
             raise ValueError("--generator_output %s contradicts the checkpoint, which was trained with %s" % (flag_mode, saved_mode))
         if flag_tau is not None and saved_mode != "logits" and flag_tau != saved_tau:
@@ -656,7 +676,8 @@ class SceneGraphGAN(object):
                 # relaxed generator output: this iteration's temperature, and per launch a draw number made of (itr, update, micro-batch)
                 tau = self._set_relaxation(self.step, self.itr) if (self.relaxed and not pre) else None
                 if self.score and not pre:  # (behind the relaxation it needs; a pathwise run never calls it)
-                    self.step.set_estimator("score", self.score["baseline"], self.score["entropy_weight"])
+                    self.step.set_estimator("score", self.score["baseline"], self.score["entropy_weight"],
+                                            **({"samples": self.score["samples"]} if self.score.get("samples", 1) > 1 else {}))
                 draw = (lambda i: {"draw": relax_draw(self.itr, i, 0, C, 1)}) if self.relax_mode == "gumbel" else (lambda i: {})
                 if pre:
                     for k, (im, lb) in enumerate(batches if N > 1 else [(images, labels)]):
@@ -700,6 +721,8 @@ class SceneGraphGAN(object):
                             sc = self.step.score_losses_mean.cpu().tolist()
                             rec["score"] = {"reward": sc[0], "adv_rms": math.sqrt(max(sc[1], 0.0)), "logp_token": sc[2], "entropy_token": sc[3],
                                             "baseline": self.score["baseline"], "entropy_weight": self.score["entropy_weight"]}
+                            if self.score.get("samples", 1) > 1:        # (only a run with several samples per image writes the key)
+                                rec["score"]["samples"] = self.score["samples"]
                     if N > 1:
                         rec["accumulate"] = N
                     if self.guarded:        # the records of each network's last update and the clipped / skipped counts so far
@@ -1456,7 +1479,13 @@ def build_parser():
                              "(default: pathwise for a fresh run)")
     parser.add_argument("--score_baseline", default=None, choices=list(SCORE_BASELINES),
                         help="with --generator_gradient score: rloo = each sample's reward minus the mean reward of the other samples "
-                             "of its (micro-)batch; none = the reward itself (default rloo)")
+                             "of its (micro-)batch; none = the reward itself; image (needs --score_samples >= 2) = minus the mean "
+                             "reward of the other samples of the same image (default rloo; image with --score_samples >= 2)")
+    parser.add_argument("--score_samples", default=None, type=int, metavar="S",
+                        help="with --generator_gradient score: S in 1..16 triples are sampled per image in the generator's update "
+                             "from one set of logits, the critic's head scores all S x batch of them against the batch's feature "
+                             "maps; the encoders run once either way.  The critic's updates keep one sample.  Recorded in the "
+                             "checkpoint when S > 1 (default 1)")
     parser.add_argument("--entropy_weight", default=None, type=float, metavar="W",
                         help="with --generator_gradient score: W >= 0 adds W x the mean entropy of the decoder rows to what the "
                              "generator maximises (default 0)")
@@ -1490,7 +1519,8 @@ def parse_args(argv=None):
     if args.relax_hard and args.generator_output == "logits":
         parser.error("--relax_hard needs --generator_output softmax or gumbel")
     try:
-        check_score_flags(args.generator_gradient, args.score_baseline, args.entropy_weight, args.generator_output, args.relax_tau)
+        check_score_flags(args.generator_gradient, args.score_baseline, args.entropy_weight, args.generator_output, args.relax_tau,
+                          args.score_samples)
     except ValueError as e:
         parser.error("--" + str(e))
     if args.generator_gradient == "score":
@@ -1523,7 +1553,7 @@ if __name__ == "__main__":
                         validate_nll=params["validate_nll"], generator_output=params["generator_output"],
                         relax_tau=params["relax_tau"], relax_hard=params["relax_hard"], seed=params["seed"],
                         generator_gradient=params["generator_gradient"], score_baseline=params["score_baseline"],
-                        entropy_weight=params["entropy_weight"])
+                        entropy_weight=params["entropy_weight"], score_samples=params["score_samples"])
     if params["likelihood_out"]:
         if not gan.load_checkpoint():
             print("--likelihood_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
