@@ -463,6 +463,44 @@ int sgg_kbest_merge(const long long* lists, const float* logits, long long ld, c
                     long long* triples, float* scores, int* best_sample, float* best_logp, int* counts, int* n_distinct,
                     void* stream);
 
+/* ---- grounded scene graphs: entity instances from the pooled attention of an image's samples (csrc/ground.hip) ---------------
+ * From the ranked distinct triples of an image (sgg_rank_triples / sgg_kbest_merge) and the generator's attention rows of its N
+ * samples to the nodes of a scene graph of entity INSTANCES.  The definitions are stated in fp64 by sgg_amd/ground.py
+ * (ground_reference).  Three launches, no host read-back between them, no float atomics: two calls give the same bits.
+ * n_distinct is a device array and is clamped to [0, K]: U_j = min(n_distinct[j], K).
+ * sgg_ground_assign: which samples are which slot; one workgroup per image.
+ *   tokens int64 [N][nb][3], triples int64 [nb][K][3].  slot_of_sample int32 [nb][N]: the slot u < U_j whose triple equals the
+ *   sample's three tokens (the smallest such slot, should the list not be distinct), -1 when there is none or a token lies outside
+ *   [0, V).  members int32 [nb][N]: the assigned samples grouped by slot, ascending sample inside a slot, -1 in the tail of
+ *   unassigned samples.  start int32 [nb][K + 1]: the members of slot u are members[j][start[u] .. start[u + 1]); start[u] =
+ *   start[U_j] for u >= U_j.  1 <= N <= 4096, 1 <= K <= 4096, 1 <= V <= 2^21.
+ * sgg_ground_pool: the mean attention of every slot's members; one workgroup per (slot, image).
+ *   alpha0 / alpha1 / alpha2 fp32: the attention of decoding step t (subject, predicate, object), row k * nb + j of sample k of
+ *   image j, rows lda >= L floats apart (plane 0 of the head's attention buffers: not copied).  members, start: as above.
+ *   maps fp32 [nb][K][3][L]: the mean of the member rows in member order, fp32, one division.  A slot without a member takes the
+ *   single row fallback_sample[j][u] (int32 [nb][K]: first_sample / best_sample of the ranking), or zeros when that lies outside
+ *   [0, N).  n_pooled int32 [nb][K]: the number of members (0 when the fallback was used).  Slots u >= U_j: zeros and 0.
+ *   1 <= N <= 4096, 1 <= K <= 4096, 1 <= nb <= 65535, 1 <= L <= 2^20.
+ * sgg_ground_resolve: mentions joined into nodes; one workgroup per image.
+ *   Mention m = 2u + r of slot u < U_j (r = 0 subject, 1 object) has token triples[j][u][2r], map maps[j][u][2r] and weight
+ *   max(n_pooled[j][u], 1).  ov(m, m') = sum_l min(a_l, b_l).  Two mentions are joined when their tokens are equal and
+ *   ov >= overlap; the nodes are the connected components, numbered in the order of their smallest mention.
+ *   mention_node int32 [nb][K][2] (-1 behind U_j), n_nodes int32 [nb]; per node n < n_nodes[j], in arrays of 2 K rows per image:
+ *   node_word int64 (its token), node_first int32 (its smallest mention), node_weight int32 (sum of its mentions' weights),
+ *   node_mentions int32, node_map fp32 [L] (sum_m w_m map_m / sum_m w_m over its mentions in ascending order, fp32), node_box
+ *   int32 [4] = { y0, x0, y1, x1 } (inclusive: the smallest cell rectangle with every cell a >= box_frac * max a), node_center
+ *   fp32 [2] = (sum a (y + 0.5), sum a (x + 0.5)) / sum a in cell units (NaN for an all-zero map).  Rows behind n_nodes[j] hold
+ *   -1 (integers), 0 (node_map), NaN (node_center).  overlap and box_frac in (0, 1].  1 <= K <= 1024 (the pair work of an image
+ *   whose mentions all share one word is quadratic in 2 K), Hf * Wf <= 2^20. */
+int sgg_ground_assign(const long long* tokens, const long long* triples, const int* n_distinct, int N, int nb, int K, int V,
+                      int* slot_of_sample, int* members, int* start, void* stream);
+int sgg_ground_pool(const float* alpha0, const float* alpha1, const float* alpha2, long long lda, const int* members, const int* start,
+                    const int* fallback_sample, const int* n_distinct, int N, int nb, int K, int L, float* maps, int* n_pooled,
+                    void* stream);
+int sgg_ground_resolve(const float* maps, const long long* triples, const int* n_distinct, const int* n_pooled, int nb, int K, int Hf,
+                       int Wf, float overlap, float box_frac, int* mention_node, int* n_nodes, long long* node_word, int* node_first,
+                       int* node_weight, int* node_mentions, float* node_map, int* node_box, float* node_center, void* stream);
+
 /* ---- generator likelihood: softmax cross-entropy and the log-probability of given triples (csrc/xent.hip) -------------------
  * The likelihood K-best decoding ranks by (above), as a training objective and as a held-out measurement.  Finite logits are a
  * precondition of all three entry points; none uses a workspace or a float atomic, and two calls give the same bits.

@@ -94,6 +94,9 @@ SIGNATURES = {
     "sgg_match_triples": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "sgg_kbest_triples": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sgg_kbest_merge": (_i, [_vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgg_ground_assign": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "sgg_ground_pool": (_i, [_vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sgg_ground_resolve": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f] + [_vp] * 10),
     "sgg_softmax_xent": (_i, [_vp, _ll, _i, _i, _vp, _f, _i, _vp, _ll, _vp, _vp, _vp, _vp]),
     "sgg_xent_summary": (_i, [_vp, _vp, _i, _vp, _vp]),
     "sgg_triple_logp": (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -1141,6 +1144,70 @@ class HipKernels:
         self._check(self.lib.sgg_kbest_merge(_p(triples), _p(x), ld, _p(lse), N, nb, Kc, V, K, _p(res["triples"]), _p(res["scores"]),
                                              _p(res["best_sample"]), _p(res["best_logp"]), _p(res["counts"]), _p(res["n_distinct"]),
                                              self._stream()), "sgg_kbest_merge")
+        return res
+
+    # -- grounded scene graphs (csrc/ground.hip; the definitions: sgg_amd/ground.py) ---------------------------
+    def ground_assign(self, tokens, triples, n_distinct, vocab=None, out=None):
+        """Which samples are which slot of their image's ranked list: tokens int64 [N, nb, 3], triples int64 [nb, K, 3] and n_distinct
+        int32 [nb] (rank_triples' / kbest_merge's outputs) -> {"slot_of_sample": int32 [nb, N] (-1: none), "members": int32 [nb, N]
+        (grouped by slot, ascending sample inside a slot, -1 in the unassigned tail), "start": int32 [nb, K + 1]}.  vocab: default
+        the library's limit, 2^21.  out: optional dict of preallocated contiguous tensors under those names."""
+        self._dev(tokens, triples, n_distinct)
+        assert tokens.dtype == torch.int64 and tokens.dim() == 3 and tokens.shape[2] == 3 and tokens.is_contiguous()
+        assert triples.dtype == torch.int64 and triples.dim() == 3 and triples.shape[2] == 3 and triples.is_contiguous()
+        N, nb, K = int(tokens.shape[0]), int(tokens.shape[1]), int(triples.shape[1])
+        assert triples.shape[0] == nb and n_distinct.dtype == torch.int32 and tuple(n_distinct.shape) == (nb,) and n_distinct.is_contiguous()
+        V = (1 << 21) if vocab is None else int(vocab)
+        res = self._out_tensors({"slot_of_sample": ((nb, N), torch.int32), "members": ((nb, N), torch.int32),
+                                 "start": ((nb, K + 1), torch.int32)}, out, tokens.device)
+        self._check(self.lib.sgg_ground_assign(_p(tokens), _p(triples), _p(n_distinct), N, nb, K, V, _p(res["slot_of_sample"]),
+                                               _p(res["members"]), _p(res["start"]), self._stream()), "sgg_ground_assign")
+        return res
+
+    def ground_pool(self, alphas, members, start, fallback_sample, n_distinct, out=None):
+        """The mean attention of every slot's members: alphas = the three fp32 [N * nb, L] attention views of the decoding steps (row
+        k * nb + j; one common row stride, read in place - never a stacked copy), members int32 [nb, N] and start int32 [nb, K + 1]
+        (ground_assign), fallback_sample int32 [nb, K] (the row a slot without a member takes; outside [0, N): zeros), n_distinct
+        int32 [nb] -> {"maps": fp32 [nb, K, 3, L], "n_pooled": int32 [nb, K]}; slots behind n_distinct: zeros.  out: optional dict of
+        preallocated contiguous tensors."""
+        a0, a1, a2 = alphas
+        self._dev(a0, a1, a2, members, start, fallback_sample, n_distinct)
+        nb, N, K = int(members.shape[0]), int(members.shape[1]), int(start.shape[1]) - 1
+        L = int(a0.shape[1])
+        for a in (a0, a1, a2):
+            assert a.dtype == torch.float32 and a.dim() == 2 and tuple(a.shape) == (N * nb, L) and (a.stride(1) == 1 or L == 1), \
+                "alphas: three fp32 [N * nb, L] views with a contiguous last dimension"
+        lda = int(_ld(a0))
+        assert int(_ld(a1)) == lda and int(_ld(a2)) == lda, "alphas: one common row stride"
+        for t, shape in ((members, (nb, N)), (start, (nb, K + 1)), (fallback_sample, (nb, K)), (n_distinct, (nb,))):
+            assert t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()
+        res = self._out_tensors({"maps": ((nb, K, 3, L), torch.float32), "n_pooled": ((nb, K), torch.int32)}, out, a0.device)
+        self._check(self.lib.sgg_ground_pool(_p(a0), _p(a1), _p(a2), lda, _p(members), _p(start), _p(fallback_sample), _p(n_distinct),
+                                             N, nb, K, L, _p(res["maps"]), _p(res["n_pooled"]), self._stream()), "sgg_ground_pool")
+        return res
+
+    def ground_resolve(self, maps, triples, n_distinct, n_pooled, Hf, Wf, overlap=0.5, box_frac=0.5, out=None):
+        """Mentions joined into entity nodes: maps fp32 [nb, K, 3, Hf * Wf] and n_pooled int32 [nb, K] (ground_pool), triples int64
+        [nb, K, 3], n_distinct int32 [nb] -> {"mention_node": int32 [nb, K, 2], "n_nodes": int32 [nb], "node_word": int64 [nb, 2K],
+        "node_first" / "node_weight" / "node_mentions": int32 [nb, 2K], "node_map": fp32 [nb, 2K, L], "node_box": int32 [nb, 2K, 4]
+        (y0, x0, y1, x1 inclusive), "node_center": fp32 [nb, 2K, 2] (y, x in cells)}; behind n_nodes: -1 / 0 / NaN.  overlap and
+        box_frac in (0, 1]; K <= 1024.  out: optional dict of preallocated contiguous tensors."""
+        self._dev(maps, triples, n_distinct, n_pooled)
+        nb, K, L = int(triples.shape[0]), int(triples.shape[1]), int(Hf) * int(Wf)
+        assert triples.dtype == torch.int64 and triples.dim() == 3 and triples.shape[2] == 3 and triples.is_contiguous()
+        assert maps.dtype == torch.float32 and tuple(maps.shape) == (nb, K, 3, L) and maps.is_contiguous()
+        for t, shape in ((n_distinct, (nb,)), (n_pooled, (nb, K))):
+            assert t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()
+        i32 = torch.int32
+        res = self._out_tensors({"mention_node": ((nb, K, 2), i32), "n_nodes": ((nb,), i32), "node_word": ((nb, 2 * K), torch.int64),
+                                 "node_first": ((nb, 2 * K), i32), "node_weight": ((nb, 2 * K), i32), "node_mentions": ((nb, 2 * K), i32),
+                                 "node_map": ((nb, 2 * K, L), torch.float32), "node_box": ((nb, 2 * K, 4), i32),
+                                 "node_center": ((nb, 2 * K, 2), torch.float32)}, out, maps.device)
+        self._check(self.lib.sgg_ground_resolve(_p(maps), _p(triples), _p(n_distinct), _p(n_pooled), nb, K, int(Hf), int(Wf),
+                                                float(overlap), float(box_frac), _p(res["mention_node"]), _p(res["n_nodes"]),
+                                                _p(res["node_word"]), _p(res["node_first"]), _p(res["node_weight"]),
+                                                _p(res["node_mentions"]), _p(res["node_map"]), _p(res["node_box"]),
+                                                _p(res["node_center"]), self._stream()), "sgg_ground_resolve")
         return res
 
     # -- generator likelihood (csrc/xent.hip) ---------------------------------------------------------------

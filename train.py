@@ -3,6 +3,7 @@
     python train.py --synthetic 64,224,1000 --max_iterations 20           # no Visual Genome files needed
     python train.py --checkpoints_dir ckpt --saliency_dir maps             # per-word saliency maps of the test split
     python train.py --checkpoints_dir ckpt --predict_dir graphs            # ranked scene graph of every test image
+    python train.py --checkpoints_dir ckpt --predict_dir graphs --ground   # ... with subjects / objects resolved to entity instances
     python train.py --checkpoints_dir ckpt --metrics_out metrics.json      # R@K, mR@K, zsR@K of the test split
     python train.py --ema_decay 0.999 ...                                  # keep an average of G's weights; evaluation then uses it
     python train.py --batch_size 64 --accumulate 8 ...                     # every update from 8 micro-batches: the batch-512 update
@@ -41,6 +42,7 @@ from architectures.discriminator_with_attention import Discriminator
 
 import sgg_amd  # noqa: F401
 from sgg_amd import dp as dpmod
+from sgg_amd import ground as groundmod
 from sgg_amd import guard as guardmod
 from sgg_amd import kbest as kbestmod
 from sgg_amd.api import kernels_for
@@ -49,7 +51,7 @@ from sgg_amd.diagnostics import raise_if_nonfinite
 from sgg_amd.params import EMBED_DIM
 from sgg_amd.metrics import MAX_GT, RecallAccumulator, zero_shot_mask
 from sgg_amd.predict import DEFAULT_LOGITS_BUDGET_BYTES, images_per_pass, scene_graph
-from sgg_amd.step import GanStep
+from sgg_amd.step import GanStep, need_kernels
 
 
 class ValidationEarlyStop(object):
@@ -1031,12 +1033,13 @@ class SceneGraphGAN(object):
             if pool is not None:
                 pool.shutdown(wait=True, cancel_futures=True)
 
-    def _ranked_batches(self, K, items, N, nb, top_k, descending, out):
+    def _ranked_batches(self, K, items, N, nb, top_k, descending, out, toks=None):
         """The sampling passes predict() and evaluate() share: per batch of _sample_batches, argmax_rows ->
         Discriminator.score_samples -> rank_triples into `out`; yields (i0, n) with `out` (and self.g.alphas) holding the batch's
-        results."""
+        results.  toks: an int64 [N, nb, 3] tensor of the caller's that receives the sample tokens (grounding reads them)."""
         V = len(self.vocab)
-        toks = torch.empty((N, nb, 3), dtype=torch.int64, device=self.device)
+        if toks is None:
+            toks = torch.empty((N, nb, 3), dtype=torch.int64, device=self.device)
         relax = self._eval_relax_kw()       # the critic scores what it was trained on
         with contextlib.closing(self._sample_batches(items, N, nb)) as batches:
             for i0, n, images, logits in batches:
@@ -1045,9 +1048,10 @@ class SceneGraphGAN(object):
                 K.rank_triples(toks, d.view(N, nb, 3), top_k, descending=descending, vocab=V, out=out)
                 yield i0, n
 
-    def _kbest_batches(self, K, items, N, nb, top_k, out):
+    def _kbest_batches(self, K, items, N, nb, top_k, out, toks=None):
         """K-best decoding of the same passes: per batch of _sample_batches, kbest_triples (the list_width most probable triples of
-        every head row) -> kbest_merge into `out`.  The discriminator is not run."""
+        every head row) -> kbest_merge into `out`.  The discriminator is not run.  toks: an int64 [N, nb, 3] tensor of the caller's;
+        given, one argmax_rows of the logits fills it with the sample tokens (grounding reads them)."""
         width = kbestmod.list_width(N, len(self.vocab))
         lists = {"triples": torch.empty((N * nb, width, 3), dtype=torch.int64, device=self.device),
                  # (the per-row logp is an output the binding requires; nothing here reads it: the merge scores every triple anew
@@ -1056,15 +1060,23 @@ class SceneGraphGAN(object):
                  "lse": torch.empty((N * nb, 3), dtype=torch.float32, device=self.device)}
         with contextlib.closing(self._sample_batches(items, N, nb)) as batches:
             for i0, n, images, logits in batches:
+                if toks is not None:
+                    K.argmax_rows(logits, toks.view(-1))
                 K.kbest_triples(logits, width, out=lists)
                 K.kbest_merge(lists["triples"].view(N, nb, width, 3), logits, lists["lse"], top_k, out=out)
                 yield i0, n
 
     def _predict_iter(self, items=None, max_images=None, n_samples=None, top_k=None, descending=False, with_attention=False,
-                      logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES, decode="samples"):
+                      logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES, decode="samples", ground=False,
+                      ground_overlap=groundmod.DEFAULT_OVERLAP, ground_box_frac=groundmod.DEFAULT_BOX_FRAC):
         """predict(), one image at a time (write_predictions streams it to disk)."""
         kbest = kbestmod.check_decode(decode, descending) == "kbest"
+        if ground:
+            ground_overlap, ground_box_frac = groundmod.check_ground_args(ground_overlap, ground_box_frac)
         K, V, TB, N, top_k = self._sampling_setup("predict", n_samples, top_k, decode)
+        if ground:
+            groundmod.check_ground_args(ground_overlap, ground_box_frac, top_k)
+            need_kernels(K, "predict(ground=True)", "ground_assign", "ground_pool", "ground_resolve")
         items = self._predict_items(items, max_images)
         if not items:
             return
@@ -1074,19 +1086,45 @@ class SceneGraphGAN(object):
         # (K-best: the kernel's best_sample is the record's first_sample, the sample that gives the triple its highest probability)
         fields = [("scores", np.float32), ("best_sample", np.int32), ("best_logp", np.float32), ("counts", np.int32)] if kbest else \
                  [("scores", np.float32), ("first_rank", np.int32), ("first_sample", np.int32), ("counts", np.int32)]
-        packed, out, views = self._device_pack([("triples", np.int64, (nb, top_k, 3))] + [(f, dt, (nb, top_k)) for f, dt in fields] +
-                                               [("n_distinct", np.int32, (nb,))], self.device)
+        parts = [("triples", np.int64, (nb, top_k, 3))] + [(f, dt, (nb, top_k)) for f, dt in fields] + [("n_distinct", np.int32, (nb,))]
         sample_of = "best_sample" if kbest else "first_sample"
+        toks = gbuf = None
+        if ground:
+            # grounding (csrc/ground.hip): its outputs join the packed buffer, except the node maps, of which only the rows in front
+            # of the batch's largest n_nodes are copied; the sample tokens and the three intermediate arrays never leave the device
+            L, S = int(self.g.net.trunk.L), int(self.g.net.trunk.S)
+            Hf = Wf = int(round(L ** 0.5))
+            i32, dev = torch.int32, self.device
+            parts += [("mention_node", np.int32, (nb, top_k, 2)), ("n_pooled", np.int32, (nb, top_k)),
+                      ("maps", np.float32, (nb, top_k, 3, L)), ("n_nodes", np.int32, (nb,)), ("node_word", np.int64, (nb, 2 * top_k)),
+                      ("node_first", np.int32, (nb, 2 * top_k)), ("node_weight", np.int32, (nb, 2 * top_k)),
+                      ("node_mentions", np.int32, (nb, 2 * top_k)), ("node_box", np.int32, (nb, 2 * top_k, 4)),
+                      ("node_center", np.float32, (nb, 2 * top_k, 2))]
+            toks = torch.empty((N, nb, 3), dtype=torch.int64, device=dev)
+            gbuf = {"slot_of_sample": torch.empty((nb, N), dtype=i32, device=dev), "members": torch.empty((nb, N), dtype=i32, device=dev),
+                    "start": torch.empty((nb, top_k + 1), dtype=i32, device=dev),
+                    "node_map": torch.empty((nb, 2 * top_k, L), dtype=torch.float32, device=dev)}
+        packed, out, views = self._device_pack(parts, self.device)
         col = torch.arange(nb, device=self.device).view(nb, 1)
-        batches = self._kbest_batches(K, items, N, nb, top_k, out) if kbest else \
-            self._ranked_batches(K, items, N, nb, top_k, descending, out)
+        batches = self._kbest_batches(K, items, N, nb, top_k, out, toks) if kbest else \
+            self._ranked_batches(K, items, N, nb, top_k, descending, out, toks)
         for i0, n in batches:
+            if ground:              # right behind the ranking, on the attention of the same g.sample call (score_samples ran D's head)
+                K.ground_assign(toks, out["triples"], out["n_distinct"], vocab=V, out=gbuf)
+                K.ground_pool([a[0] for a in self.g._alphas], gbuf["members"], gbuf["start"], out[sample_of], out["n_distinct"], out=out)
+                res_names = ("mention_node", "n_nodes", "node_word", "node_first", "node_weight", "node_mentions", "node_box",
+                             "node_center")
+                K.ground_resolve(out["maps"], out["triples"], out["n_distinct"], out["n_pooled"], Hf, Wf, ground_overlap,
+                                 ground_box_frac, out=dict({k: out[k] for k in res_names}, node_map=gbuf["node_map"]))
             if with_attention:      # the attention of every triple's first-occurrence sample: head row first_sample * nb + j
                 rows = out[sample_of].long().clamp_(min=0) * nb + col
                 al = self.g.alphas
                 side = int(round(al.shape[-1] ** 0.5))
                 att_h = al[rows.view(-1)].view(nb, top_k, 3, side, side).cpu().numpy()
             h = views(packed.cpu().numpy())
+            if ground:
+                most = int(h["n_nodes"][:n].max())
+                node_map_h = gbuf["node_map"][:, :most].cpu().numpy()
             for j in range(n):
                 nd = int(h["n_distinct"][j])
                 U = min(nd, top_k)
@@ -1097,10 +1135,19 @@ class SceneGraphGAN(object):
                 r["graph"] = scene_graph(r["triples"], r["scores"], r["counts"], self.reverse_vocab)
                 if with_attention:
                     r["attention"] = att_h[j, :U].copy()
+                if ground:
+                    nn = int(h["n_nodes"][j])
+                    nodes = {f: h["node_" + f][j, :nn].copy() for f in groundmod.NODE_FIELDS if f != "map"}
+                    nodes["map"] = node_map_h[j, :nn].reshape(nn, Hf, Wf).copy()
+                    r["grounding"] = {"mention_node": h["mention_node"][j, :U].copy(), "n_pooled": h["n_pooled"][j, :U].copy(),
+                                      "pooled_attention": h["maps"][j, :U].reshape(U, 3, Hf, Wf).copy(), "nodes": nodes}
+                    r["grounded_graph"] = groundmod.grounded_scene_graph(r["triples"], r["scores"], r["counts"], self.reverse_vocab,
+                                                                         r["grounding"]["mention_node"], nodes, S)
                 yield r
 
     def predict(self, items=None, max_images=None, n_samples=None, top_k=None, descending=False, with_attention=False,
-                logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES, decode="samples"):
+                logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES, decode="samples", ground=False,
+                ground_overlap=groundmod.DEFAULT_OVERLAP, ground_box_frac=groundmod.DEFAULT_BOX_FRAC):
         """The scene graph of every image: its n_samples generator samples (default TEST_BATCH_MULTIPLIER x TEST_BATCH_SIZE) scored by
         the critic as in test(), reduced on the device to the DISTINCT triples in ranked order (K.rank_triples: ascending mean
         critic score - the order of test() - or descending=True for the highest score first; ties by sample index), the first top_k
@@ -1128,28 +1175,56 @@ class SceneGraphGAN(object):
         probability: with_attention shows that sample's attention), best_logp [U] (that probability's log), counts [U] (lists that
         hold the triple), n_distinct, graph, ordering and image, and no first_rank.  top_k <= n_samples x list width (default: all
         of them); descending=True is rejected.  With one sample the list is the exact K-best list; with more, the candidates are the
-        union of the per-sample lists, which approximates the mixture's own K best."""
+        union of the per-sample lists, which approximates the mixture's own K best.
+
+        ground=True (either decoding mode; top_k <= 1024): the subjects and objects of the ranked triples are resolved to entity
+        INSTANCES from the generator's attention (sgg_amd/ground.py states the definitions; csrc/ground.hip).  Right behind the
+        ranking, on the attention of the same Generator.sample call: K.ground_assign (which samples are which triple; under
+        decode="kbest" the sample tokens come from one argmax_rows of the logits) -> K.ground_pool (per triple and decoding step
+        the mean attention of its samples; a K-best triple that is no sample's argmax takes its first_sample's row) ->
+        K.ground_resolve (two mentions of one word are one node when their pooled maps overlap by ground_overlap or more, sum of
+        the cell-wise minimum; per node the weighted mean map, the cell box of everything at or above ground_box_frac of its
+        maximum, and the centre of mass).  The outputs ride in the same packed copy; of the node maps only the rows in front of the
+        batch's largest node count are copied.  The record gains "grounding": mention_node [U, 2], n_pooled [U], pooled_attention
+        [U, 3, Hf, Wf] and nodes (word, first, weight, mentions [n], map [n, Hf, Wf], box [n, 4] as y0, x0, y1, x1 inclusive cells,
+        center [n, 2] as y, x in cells), and "grounded_graph" (sgg_amd.ground.grounded_scene_graph: boxes and centres in input
+        pixels); "graph" stays the word-merged graph.  Both thresholds default to 0.5 and are untuned, and whether the attention
+        of a trained model localises entities has not been measured.  With ground=False nothing of this is allocated or launched."""
         kbestmod.check_decode(decode, descending)
         with self._eval_weights():
             return list(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention, logits_budget_bytes,
-                                           decode))
+                                           decode, ground, ground_overlap, ground_box_frac))
 
-    def write_predictions(self, out_dir, max_images=None, n_samples=None, top_k=None, descending=False, items=None, decode="samples"):
+    def write_predictions(self, out_dir, max_images=None, n_samples=None, top_k=None, descending=False, items=None, decode="samples",
+                          ground=False, ground_overlap=groundmod.DEFAULT_OVERLAP, ground_box_frac=groundmod.DEFAULT_BOX_FRAC):
         """predict(with_attention=True) of the test images to disk: one <index>.npz per image (triples, words, scores, first_rank,
         first_sample, counts, n_distinct, attention) and index.json (image path or index -> npz file, n_distinct and the graph).
-        decode="kbest": the arrays of that record (best_logp in place of first_rank), and index.json says "decode": "kbest"."""
+        decode="kbest": the arrays of that record (best_logp in place of first_rank), and index.json says "decode": "kbest".
+        ground=True: predict(ground=True); the .npz gains ground_mention_node, ground_n_pooled, ground_pooled_attention and
+        ground_node_word / _first / _weight / _mentions / _map / _box / _center, every image of index.json gains "grounded_graph",
+        and index.json says "ground": {"overlap", "box_frac"}."""
         kbestmod.check_decode(decode, descending)
+        if ground:
+            ground_overlap, ground_box_frac = groundmod.check_ground_args(ground_overlap, ground_box_frac)
         os.makedirs(out_dir, exist_ok=True)
         index = {}
         extra = "best_logp" if decode == "kbest" else "first_rank"
         with self._eval_weights() as weights:
             for i, r in enumerate(self._predict_iter(items, max_images, n_samples, top_k, descending, with_attention=True,
-                                                     decode=decode)):
+                                                     decode=decode, ground=ground, ground_overlap=ground_overlap,
+                                                     ground_box_frac=ground_box_frac)):
                 name = "%06d.npz" % i
+                arrays = {extra: r[extra]}
+                if ground:
+                    gr = r["grounding"]
+                    arrays.update({"ground_" + k: gr[k] for k in ("mention_node", "n_pooled", "pooled_attention")})
+                    arrays.update({"ground_node_" + k: v for k, v in gr["nodes"].items()})
                 np.savez(os.path.join(out_dir, name), triples=r["triples"], words=np.array(r["words"], dtype=str).reshape(-1, 3),
                          scores=r["scores"], first_sample=r["first_sample"], counts=r["counts"],
-                         n_distinct=np.int32(r["n_distinct"]), attention=r["attention"], **{extra: r[extra]})
+                         n_distinct=np.int32(r["n_distinct"]), attention=r["attention"], **arrays)
                 index[r["image"]] = {"file": name, "n_distinct": r["n_distinct"], "graph": r["graph"]}
+                if ground:
+                    index[r["image"]]["grounded_graph"] = r["grounded_graph"]
         n_images = len(index)
         if weights == "ema":
             index["generator_weights"] = "ema"
@@ -1157,6 +1232,8 @@ class SceneGraphGAN(object):
             index["decode"] = "kbest"
         elif self.relaxed:                  # (the critic ranked softmax(logits / tau); K-best decoding does not run it)
             index["generator_output"] = self._relax_label()
+        if ground:
+            index["ground"] = {"overlap": ground_overlap, "box_frac": ground_box_frac}
         with open(os.path.join(out_dir, "index.json"), "w") as f:
             json.dump(index, f, indent=1)
         if self.rank == 0:
@@ -1416,6 +1493,15 @@ def build_parser():
                              "noise sample, ranked by critic score (the default); kbest = the K most probable triples of each sample's "
                              "three softmaxes, merged and ranked by the generator's log-probability, no critic pass (--predict_samples "
                              "then defaults to the test batch size; not with --predict_descending)")
+    parser.add_argument("--ground", action="store_true",
+                        help="with --predict_dir: resolve the subjects and objects of the ranked triples to entity instances from the "
+                             "generator's pooled attention (nodes with boxes and centres; \"grounded_graph\" in index.json)")
+    parser.add_argument("--ground_overlap", default=groundmod.DEFAULT_OVERLAP, type=float,
+                        help="with --ground: two mentions of one word are one entity when their pooled attention maps overlap by at "
+                             "least this much, in (0, 1] (default 0.5; untuned)")
+    parser.add_argument("--ground_box_frac", default=groundmod.DEFAULT_BOX_FRAC, type=float,
+                        help="with --ground: an entity's box holds every cell at or above this fraction of its map's maximum, in "
+                             "(0, 1] (default 0.5; untuned)")
     parser.add_argument("--metrics_out", default=None,
                         help="load the checkpoint in --checkpoints_dir, write R@K, mR@K and zsR@K of the test images (distinct "
                              "predictions, denominators |GT|) as JSON to this file and exit; no training")
@@ -1512,6 +1598,13 @@ def parse_args(argv=None):
         kbestmod.check_decode(args.decode, args.predict_descending)
     except ValueError as e:
         parser.error(str(e))
+    if args.ground:
+        if not args.predict_dir:
+            parser.error("--ground needs --predict_dir")
+        try:
+            groundmod.check_ground_args(args.ground_overlap, args.ground_box_frac, args.top_k)
+        except ValueError as e:
+            parser.error(str(e))
     if args.pretrain_iterations < 0:
         parser.error("--pretrain_iterations must be >= 0")
     if not (0.0 <= args.mle_weight < float("inf")):
@@ -1574,7 +1667,9 @@ if __name__ == "__main__":
                   file=sys.stderr)
             sys.exit(2)
         gan.write_predictions(params["predict_dir"], max_images=params["max_test_images"], n_samples=params["predict_samples"],
-                              top_k=params["top_k"], descending=params["predict_descending"], decode=params["decode"])
+                              top_k=params["top_k"], descending=params["predict_descending"], decode=params["decode"],
+                              ground=params["ground"], ground_overlap=params["ground_overlap"],
+                              ground_box_frac=params["ground_box_frac"])
     elif params["metrics_out"]:
         if not gan.load_checkpoint():
             print("--metrics_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
