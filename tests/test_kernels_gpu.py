@@ -74,6 +74,7 @@ CONV_CASES = [
 
 
 ONE_PIECE_TOL = {1: 2e-3, 4: 1.5e-2}     # single-piece (mixed-precision) modes: operands rounded to fp16 (2^-11) / bf16 (2^-8)
+CONV_TOL = {0: 2e-5, 2: 2e-5, 6: 2e-5, 3: 1e-4, **ONE_PIECE_TOL}     # per conv precision mode, of max|ref| (fixture conv_mode below)
 
 
 @pytest.fixture(params=[0, 2, 6, 3, 1, 4], ids=["f32mfma", "f16x3", "bf16x6", "bf16x3", "f16x1", "bf16x1"])
@@ -84,7 +85,7 @@ def conv_mode(request, hip):
     fp16 / bf16: mixed-precision arithmetic) 2e-3 / 1.5e-2."""
     old = hip.conv_precision
     hip.conv_precision = request.param
-    yield {0: 2e-5, 2: 2e-5, 6: 2e-5, 3: 1e-4, **ONE_PIECE_TOL}[request.param]
+    yield CONV_TOL[request.param]
     hip.conv_precision = old
 
 
