@@ -530,6 +530,36 @@ int sgg_xent_summary(const float* nll, const int* hit, int R, float* out4, void*
 int sgg_triple_logp(const float* logits, long long ld, const float* lse, int N, int nb, int V, const long long* gt,
                     const int* gt_count, int M, float* mix, float* mean, float* slot, int* status, void* stream);
 
+/* ---- image retrieval by triple query: the generator's likelihood ranked across images (csrc/retrieve.hip) -------------------
+ * The other direction of the likelihood above: ONE list of Q (partial) triples scored against every image of a collection, and the
+ * images ranked per query.  No entry point uses a workspace or a float atomic, and two calls give the same bits.
+ * sgg_query_logp: the mixture log-probability of Q shared queries for the nb images of one batch; grid (image, query tile).
+ *   logits, ld, lse, N, nb, V: as sgg_triple_logp takes them (finite logits are a precondition).  tok int32 [3][U]: per slot the
+ *   distinct tokens the queries use, u0 / u1 / u2 <= U of them valid (built on the host; every token in [0, V) - one outside
+ *   makes the scores of the queries that name it NaN, nothing is read out of bounds).  qidx int32 [Q][3]: per slot an index into
+ *   that slot's list, or -1 for an unspecified slot (a wildcard); any other value makes the query's score NaN.
+ *   a_t = logits[t][tok] - lse[t], or exactly 0.f for a wildcard (the slot is marginalised: its softmax sums to 1);
+ *   lp_k = (a_0 + a_1) + a_2; score = m + (log(sum_k exp(lp_k - m)) - log N) with (m, sum) kept ONLINE over the samples in sample
+ *   order (the sum rescaled by exp(m_old - m_new) when the maximum rises): the arithmetic of sgg_triple_logp's mix up to that
+ *   summation.  A query of three wildcards scores 0.  scores[q * lds + col0 + j] for j < nb; nothing else is written.
+ *   1 <= N <= 4096, 1 <= Q <= 4096, 1 <= U <= Q, 1 <= nb <= 65535, 1 <= V <= 2^21, 0 <= col0, col0 + nb <= lds.
+ * sgg_retrieve_topk: per query the first K images of the row scores[q * lds .. + n_images) under the total order (score
+ *   descending, image index ascending; +0 and -0 are equal); one workgroup per query.  idx int32 [Q][K], top fp32 [Q][K] (the
+ *   scores' own bits); slots behind min(K, n_images) hold -1 and NaN.  Exact: a radix selection of the K-th key (seven passes over
+ *   the row) and one sort of the K survivors.  1 <= K <= 1024, 1 <= n_images <= 2^21 <= lds.  Columns >= n_images are not read.
+ * sgg_retrieve_ranks: where a query's relevant images stand in that order; one workgroup per query.
+ *   rel_ptr int32 [Q + 1], rel_idx int32 [rel_ptr[Q]] (CSR; at least one entry allocated): the relevant images of query q are
+ *   rel_idx[rel_ptr[q] .. rel_ptr[q + 1]), ascending, at most 4096, all in [0, n_images).  ranks int32, parallel to rel_idx: 1 + the
+ *   number of images that precede the image in the total order (integers).  first_rank int32 [Q]: the smallest of them.
+ *   ap fp64 [Q]: average precision = mean_i (i + 1) / rank_(i) over the ascending ranks, in fp64, fixed order.  status int32 [Q]:
+ *   0 valid; -3 no relevant image (first_rank 0, ap NaN); -4 a list longer than 4096 or an index outside [0, n_images) (first_rank
+ *   0, ap NaN, its ranks not written). */
+int sgg_query_logp(const float* logits, long long ld, const float* lse, int N, int nb, int V, const int* tok, int U, int u0, int u1,
+                   int u2, const int* qidx, int Q, float* scores, long long lds, long long col0, void* stream);
+int sgg_retrieve_topk(const float* scores, long long lds, int Q, int n_images, int K, int* idx, float* top, void* stream);
+int sgg_retrieve_ranks(const float* scores, long long lds, int Q, int n_images, const int* rel_ptr, const int* rel_idx, int* ranks,
+                       int* first_rank, double* ap, int* status, void* stream);
+
 /* ---- relaxed generator output: softmax / Gumbel-softmax rows for the critic, and their gradient (csrc/relax.hip) ---------------
  * The critic's fake rows as points of the probability simplex instead of raw decoder logits.  Neither entry point uses a workspace
  * or a float atomic, and two calls give the same bits.  Rows are any 4-byte alignment; element offsets are 64-bit.  R >= 1,

@@ -100,6 +100,9 @@ SIGNATURES = {
     "sgg_softmax_xent": (_i, [_vp, _ll, _i, _i, _vp, _f, _i, _vp, _ll, _vp, _vp, _vp, _vp]),
     "sgg_xent_summary": (_i, [_vp, _vp, _i, _vp, _vp]),
     "sgg_triple_logp": (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sgg_query_logp": (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _ll, _ll, _vp]),
+    "sgg_retrieve_topk": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _vp]),
+    "sgg_retrieve_ranks": (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgg_relax_rows": (_i, [_vp, _ll, _i, _i, _f, _i, _ull, _ull, _vp, _ll, _vp, _ll, _vp]),
     "sgg_relax_rows_bwd": (_i, [_vp, _ll, _vp, _ll, _i, _i, _f, _f, _vp, _ll, _vp]),
     "sgg_relax_rows_hard": (_i, [_vp, _ll, _i, _i, _i, _ull, _ull, _vp, _ll, _vp, _vp]),
@@ -1278,6 +1281,59 @@ class HipKernels:
                                  "status": ((nb, M), torch.int32)}, out, logits.device)
         self._check(self.lib.sgg_triple_logp(_p(x), ld, _p(lse), N, nb, V, _p(gt), _p(gt_count), M, _p(res["mix"]), _p(res["mean"]),
                                              _p(res["slot"]), _p(res["status"]), self._stream()), "sgg_triple_logp")
+        return res
+
+    # -- image retrieval by triple query (csrc/retrieve.hip; host side: sgg_amd/retrieve.py) ------------------------------
+    def query_logp(self, logits, lse, tok, ucount, qidx, scores, col0=0):
+        """The mixture log-probability of Q shared (partial) triples for the nb images of a batch (csrc/retrieve.hip): logits fp32
+        [N, nb, 3, V], lse fp32 [N, nb, 3], tok int32 [3, U] and ucount (three host integers) - per slot the distinct tokens the
+        queries use, sgg_amd.retrieve.compile_queries builds them - qidx int32 [Q, 3] (index into the slot's list; -1: wildcard)
+        -> scores[q, col0 + j] for j < nb of the caller's fp32 [Q, n_columns] matrix (rows one stride apart); nothing else of it is
+        written.  1 <= Q <= 4096 per launch.  Returns scores."""
+        self._dev(logits, lse, tok, qidx, scores)
+        assert logits.dim() == 4 and logits.shape[2] == 3, "logits must be [N, nb, 3, V]"
+        N, nb = int(logits.shape[0]), int(logits.shape[1])
+        x, ld = self._logit_rows(logits)
+        V = int(x.shape[2])
+        assert lse.dtype == torch.float32 and lse.numel() == N * nb * 3 and lse.is_contiguous(), "lse must be contiguous [N, nb, 3]"
+        assert tok.dtype == torch.int32 and tok.dim() == 2 and tok.shape[0] == 3 and tok.is_contiguous(), "tok must be int32 [3, U]"
+        assert qidx.dtype == torch.int32 and qidx.dim() == 2 and qidx.shape[1] == 3 and qidx.is_contiguous(), "qidx must be int32 [Q, 3]"
+        U, Q = int(tok.shape[1]), int(qidx.shape[0])
+        u0, u1, u2 = (int(u) for u in ucount)
+        sc, lds = self._rows(scores, "scores")
+        assert sc.dim() == 2 and sc.shape[0] == Q and 0 <= int(col0) and int(col0) + nb <= sc.shape[1], "scores must be [Q, >= col0 + nb]"
+        self._check(self.lib.sgg_query_logp(_p(x), ld, _p(lse), N, nb, V, _p(tok), U, u0, u1, u2, _p(qidx), Q, _p(sc), lds, int(col0),
+                                            self._stream()), "sgg_query_logp")
+        return scores
+
+    def retrieve_topk(self, scores, n_images, K, out=None):
+        """Per query the first K images of scores[:, :n_images] (fp32 [Q, >= n_images], rows one stride apart) under (score
+        descending, image index ascending; +-0 equal) -> {"idx": int32 [Q, K], "scores": fp32 [Q, K] (the inputs' bits)}; slots
+        behind min(K, n_images) hold -1 / NaN.  Exact; 1 <= K <= 1024.  out: optional dict of preallocated contiguous tensors."""
+        self._dev(scores)
+        sc, lds = self._rows(scores, "scores")
+        Q, K, n = int(sc.shape[0]), max(int(K), 0), int(n_images)
+        assert sc.dim() == 2 and 1 <= n <= sc.shape[1], "scores must be [Q, >= n_images]"
+        res = self._out_tensors({"idx": ((Q, K), torch.int32), "scores": ((Q, K), torch.float32)}, out, scores.device)
+        self._check(self.lib.sgg_retrieve_topk(_p(sc), lds, Q, n, K, _p(res["idx"]), _p(res["scores"]), self._stream()),
+                    "sgg_retrieve_topk")
+        return res
+
+    def retrieve_ranks(self, scores, n_images, rel_ptr, rel_idx, out=None):
+        """Where every query's relevant images stand in the order of retrieve_topk: scores fp32 [Q, >= n_images], rel_ptr int32
+        [Q + 1] and rel_idx int32 [max(1, rel_ptr[Q])] (CSR, sgg_amd.retrieve.relevance) -> {"ranks": int32 like rel_idx (1-based),
+        "first_rank": int32 [Q], "ap": fp64 [Q], "status": int32 [Q] (0 valid, -3 no relevant image: first_rank 0, ap NaN)}.
+        out: optional dict of preallocated contiguous tensors."""
+        self._dev(scores, rel_ptr, rel_idx)
+        sc, lds = self._rows(scores, "scores")
+        Q, n = int(sc.shape[0]), int(n_images)
+        assert sc.dim() == 2 and 1 <= n <= sc.shape[1], "scores must be [Q, >= n_images]"
+        assert rel_ptr.dtype == torch.int32 and tuple(rel_ptr.shape) == (Q + 1,) and rel_ptr.is_contiguous()
+        assert rel_idx.dtype == torch.int32 and rel_idx.dim() == 1 and rel_idx.numel() >= 1 and rel_idx.is_contiguous()
+        res = self._out_tensors({"ranks": (tuple(rel_idx.shape), torch.int32), "first_rank": ((Q,), torch.int32),
+                                 "ap": ((Q,), torch.float64), "status": ((Q,), torch.int32)}, out, scores.device)
+        self._check(self.lib.sgg_retrieve_ranks(_p(sc), lds, Q, n, _p(rel_ptr), _p(rel_idx), _p(res["ranks"]), _p(res["first_rank"]),
+                                                _p(res["ap"]), _p(res["status"]), self._stream()), "sgg_retrieve_ranks")
         return res
 
     # -- relaxed generator output (csrc/relax.hip) ---------------------------------------------------------------

@@ -45,6 +45,7 @@ from sgg_amd import dp as dpmod
 from sgg_amd import ground as groundmod
 from sgg_amd import guard as guardmod
 from sgg_amd import kbest as kbestmod
+from sgg_amd import retrieve as retrmod
 from sgg_amd.api import kernels_for
 from sgg_amd.data import PrefetchLoader, ShuffledStream, parse_image
 from sgg_amd.diagnostics import raise_if_nonfinite
@@ -1000,7 +1001,7 @@ class SceneGraphGAN(object):
             offs[name] = total
             total += -(-int(np.prod(shape)) * np.dtype(dt).itemsize // 8) * 8
         packed = torch.empty((total,), dtype=torch.uint8, device=device)
-        tdt = {np.int64: torch.int64, np.float32: torch.float32, np.int32: torch.int32}
+        tdt = {np.int64: torch.int64, np.float32: torch.float32, np.int32: torch.int32, np.float64: torch.float64}
         size = lambda dt, shape: int(np.prod(shape)) * np.dtype(dt).itemsize
         out = {name: packed[offs[name]:offs[name] + size(dt, shape)].view(tdt[dt]).view(shape) for name, dt, shape in parts}
         views = lambda host: {name: host[offs[name]:offs[name] + size(dt, shape)].view(dt).reshape(shape) for name, dt, shape in parts}
@@ -1431,6 +1432,109 @@ class SceneGraphGAN(object):
                     json.dump(res, f, indent=1)
             return res
 
+    ############################################################
+    ## Retrieval: images ranked by the generator's likelihood of a (partial) triple (csrc/retrieve.hip, sgg_amd/retrieve.py)
+    ############################################################
+    def retrieve(self, queries=None, items=None, max_images=None, n_samples=None, ks=(1, 5, 10), top_k=10, max_queries=retrmod.MAX_QUERIES,
+                 return_details=False, out_path=None, logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES,
+                 score_budget_bytes=retrmod.DEFAULT_SCORE_BUDGET_BYTES):
+        """The other direction of likelihood(): given triples - whole ("man riding horse") or with open slots ("? riding horse") -
+        rank the IMAGES of a collection by the probability the generator gives the query.  score(query, image) = log of the
+        probability of the query's specified slots under the mixture of the image's n_samples noise draws (default
+        TEST_BATCH_MULTIPLIER x TEST_BATCH_SIZE); an open slot is marginalised exactly (sgg_amd/retrieve.py).
+
+        queries: list of triples as words or token ids, None / "?" / -1 for an open slot; default: sgg_amd.retrieve.default_queries
+        of the evaluated images (their distinct true triples, most frequent first, at most max_queries).  A query with a word or id
+        outside the vocabulary is counted (n_out_of_vocab) and not scored.  items: as evaluate(); an image is RELEVANT to a query
+        when one of its true triples equals the query on every specified slot.
+
+        Schedule: the passes and the noise stream of likelihood().  Per batch K.softmax_xent (lse only), then K.query_logp per block
+        of 4096 queries, which writes the batch's columns of a device-resident [n_queries, n_images] score matrix (nothing is read
+        back per batch; the padded images of the last batch land in columns behind n_images that nothing reads).  Behind the last
+        batch one K.retrieve_topk and one K.retrieve_ranks per query block, one copy back, the sums in fp64 on the host
+        (sgg_amd.retrieve.summarise).  A score matrix above score_budget_bytes raises ValueError before anything is launched.
+
+        Returns (rank 0 writes it as JSON to out_path): retrieval {"R@K" for K in ks: share of the queries with a relevant image
+        whose best-ranked relevant image is within the first K; median_rank; mrr; map}, ks, n_queries (scored), n_images,
+        n_samples, n_without_relevant (scored queries without a relevant image: excluded from the metrics), n_out_of_vocab,
+        generator_weights, decode ("likelihood": the generator alone ranks, the critic is not run) and, with return_details,
+        details: per scored query {"query" (ids), "words", "top": [{"image", "score"}] (the first top_k images), "first_rank",
+        "ap"} (None where there is no relevant image).  Touches no weights and no optimiser state."""
+        with self._eval_weights() as weights:
+            ks = tuple(sorted(set(int(k) for k in ks)))
+            if not ks or ks[0] < 1:
+                raise ValueError("retrieve: ks must be positive integers (got %r)" % (ks,))
+            if not 1 <= int(top_k) <= retrmod.MAX_TOP:
+                raise ValueError("retrieve: 1 <= top_k <= %d (got %r)" % (retrmod.MAX_TOP, top_k))
+            top_k = int(top_k)
+            items = self._evaluate_items(items, max_images)
+            gt = [real for _, _, real in items]
+            if queries is None:
+                queries = retrmod.default_queries(gt, max_queries)
+            queries = list(queries)[:max(0, int(max_queries))]
+            cq = retrmod.compile_queries(queries, self.vocab)
+            ids, Q, n_img = cq["ids"], int(cq["ids"].shape[0]), len(items)
+            rel_ptr, rel_idx = retrmod.relevance(ids, gt)
+            K, V, TB, N, _ = self._sampling_setup("retrieve", n_samples, None)
+            first_rank, ap, status = np.zeros(Q, dtype=np.int32), np.full(Q, np.nan), np.full(Q, -3, dtype=np.int32)
+            details = []
+            if items and Q:
+                need_kernels(K, "retrieve", "query_logp", "retrieve_topk", "retrieve_ranks")
+                nb = images_per_pass(N, V, TB, n_img, logits_budget_bytes)
+                cols = -(-n_img // nb) * nb                   # (the last batch's padded images get columns of their own)
+                if retrmod.score_matrix_bytes(Q, cols) > score_budget_bytes:
+                    raise ValueError("retrieve: the score matrix of %d queries x %d images takes %d bytes, above the budget of %d: "
+                                     "pass fewer queries (max_queries / --retrieve_max_queries), fewer images (max_images / "
+                                     "--max_test_images) or a larger score_budget_bytes"
+                                     % (Q, cols, retrmod.score_matrix_bytes(Q, cols), score_budget_bytes))
+                dev, QB = self.device, retrmod.MAX_QUERIES
+                scores = torch.empty((Q, cols), dtype=torch.float32, device=dev)
+                blocks = []                                   # per block of 4096 queries: its own token lists and indices
+                for b0 in range(0, Q, QB):
+                    c = retrmod.compile_queries(ids[b0:b0 + QB].tolist(), self.vocab)
+                    blocks.append((b0, torch.from_numpy(c["tok"]).to(dev), c["ucount"], torch.from_numpy(c["qidx"]).to(dev)))
+                lse = torch.empty((N, nb, 3), dtype=torch.float32, device=dev)
+                with contextlib.closing(self._sample_batches([(key, x) for key, x, _ in items], N, nb)) as batches:
+                    for i0, n, images, logits in batches:
+                        K.softmax_xent(logits, None, lse=lse.view(-1))
+                        for b0, tok, ucount, qidx in blocks:
+                            K.query_logp(logits, lse, tok, ucount, qidx, scores[b0:b0 + qidx.shape[0]], col0=i0)
+                top_w = min(top_k, n_img)
+                # (the CSR arrays carry one spare entry: a block without a relevant image still hands the kernel an allocated one)
+                parts = [("ap", np.float64, (Q,)), ("idx", np.int32, (Q, top_k)), ("scores", np.float32, (Q, top_k)),
+                         ("ranks", np.int32, (len(rel_idx) + 1,)), ("first_rank", np.int32, (Q,)), ("status", np.int32, (Q,))]
+                packed, out, views = self._device_pack(parts, dev)
+                ptr_h = rel_ptr.astype(np.int64)
+                idx_d = torch.from_numpy(np.concatenate([rel_idx, np.zeros(1, dtype=np.int32)])).to(dev)
+                for b0, _, _, qidx in blocks:
+                    b1 = b0 + int(qidx.shape[0])
+                    K.retrieve_topk(scores[b0:b1], n_img, top_k, out={"idx": out["idx"][b0:b1], "scores": out["scores"][b0:b1]})
+                    r0, r1 = int(ptr_h[b0]), int(ptr_h[b1])
+                    ptr_d = torch.from_numpy((ptr_h[b0:b1 + 1] - r0).astype(np.int32)).to(dev)
+                    K.retrieve_ranks(scores[b0:b1], n_img, ptr_d, idx_d[r0:max(r1, r0 + 1)],
+                                     out={"ranks": out["ranks"][r0:max(r1, r0 + 1)], "first_rank": out["first_rank"][b0:b1],
+                                          "ap": out["ap"][b0:b1], "status": out["status"][b0:b1]})
+                h = views(packed.cpu().numpy())
+                first_rank, status, ap = h["first_rank"].copy(), h["status"].copy(), h["ap"].copy()
+                if return_details:
+                    for q in range(Q):
+                        ok = int(status[q]) == 0
+                        details.append({"query": [int(x) for x in ids[q]],
+                                        "words": ["?" if x < 0 else self.reverse_vocab.get(int(x), "UNK") for x in ids[q]],
+                                        "top": [{"image": items[int(i)][0], "score": float(s)}
+                                                for i, s in zip(h["idx"][q, :top_w], h["scores"][q, :top_w])],
+                                        "first_rank": int(first_rank[q]) if ok else None, "ap": float(ap[q]) if ok else None})
+            summ = retrmod.summarise(first_rank, ap, status, ks)      # (raises on a status other than 0 / -3: a refused list is a bug)
+            res = {"retrieval": {k: v for k, v in summ.items() if k not in ("n_valid", "n_without_relevant")},
+                   "ks": list(ks), "n_queries": Q, "n_images": n_img, "n_samples": N, "n_without_relevant": summ["n_without_relevant"],
+                   "n_out_of_vocab": len(cq["rejected"]), "generator_weights": weights, "decode": "likelihood"}
+            if return_details:
+                res["details"] = details
+            if self.rank == 0 and out_path:
+                with open(out_path, "w") as f:
+                    json.dump(res, f, indent=1)
+            return res
+
 
 def _str2bool(v):
     """--resume of the reference is `type=bool` (train.py:410), which makes every non-empty string - "False" included - true."""
@@ -1584,6 +1688,17 @@ def build_parser():
                         help="load the checkpoint in --checkpoints_dir, write the negative log-likelihood of the test images' true "
                              "triples under the generator (mixture over --predict_samples noise draws, per draw, per slot; token "
                              "perplexity) as JSON to this file and exit; no training")
+    parser.add_argument("--retrieve_out", default=None,
+                        help="load the checkpoint in --checkpoints_dir, rank the test images for a list of triple queries by the "
+                             "generator's likelihood (mixture over --predict_samples noise draws), write R@K, median rank, MRR and mAP "
+                             "as JSON to this file and exit; no training")
+    parser.add_argument("--retrieve_queries", default=None,
+                        help="with --retrieve_out: a JSON file holding a list of triples as words or token ids, \"?\" or null for an "
+                             "open slot (default: the distinct true triples of the evaluated images, most frequent first)")
+    parser.add_argument("--retrieve_top", default=None, type=int,
+                        help="with --retrieve_out: the JSON lists the first K images of every query (1..1024; default 10)")
+    parser.add_argument("--retrieve_max_queries", default=None, type=int,
+                        help="with --retrieve_out: score at most Q queries (default 4096)")
     parser.add_argument("--log_every", default=10, type=int, help="iterations between the loss records of losses.jsonl (default 10)")
     parser.add_argument("--eval_live", action="store_true",
                         help="evaluate the generator's live weights even where an average exists (from --ema_decay or the checkpoint)")
@@ -1605,6 +1720,17 @@ def parse_args(argv=None):
             groundmod.check_ground_args(args.ground_overlap, args.ground_box_frac, args.top_k)
         except ValueError as e:
             parser.error(str(e))
+    for flag in ("retrieve_queries", "retrieve_top", "retrieve_max_queries"):
+        if getattr(args, flag) is not None and not args.retrieve_out:
+            parser.error("--%s needs --retrieve_out" % flag)
+    if args.retrieve_out:
+        for flag in ("likelihood_out", "saliency_dir", "predict_dir", "metrics_out", "test_only"):
+            if getattr(args, flag):
+                parser.error("--retrieve_out is a run of its own: not together with --%s" % flag)
+    if args.retrieve_top is not None and not 1 <= args.retrieve_top <= retrmod.MAX_TOP:
+        parser.error("--retrieve_top must be in 1..%d" % retrmod.MAX_TOP)
+    if args.retrieve_max_queries is not None and args.retrieve_max_queries < 1:
+        parser.error("--retrieve_max_queries must be >= 1")
     if args.pretrain_iterations < 0:
         parser.error("--pretrain_iterations must be >= 0")
     if not (0.0 <= args.mle_weight < float("inf")):
@@ -1647,7 +1773,21 @@ if __name__ == "__main__":
                         relax_tau=params["relax_tau"], relax_hard=params["relax_hard"], seed=params["seed"],
                         generator_gradient=params["generator_gradient"], score_baseline=params["score_baseline"],
                         entropy_weight=params["entropy_weight"], score_samples=params["score_samples"])
-    if params["likelihood_out"]:
+    if params["retrieve_out"]:
+        if not gan.load_checkpoint():
+            print("--retrieve_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
+                  file=sys.stderr)
+            sys.exit(2)
+        queries = None
+        if params["retrieve_queries"]:
+            with open(params["retrieve_queries"]) as f:
+                queries = json.load(f)
+        res = gan.retrieve(queries=queries, max_images=params["max_test_images"], n_samples=params["predict_samples"],
+                           top_k=params["retrieve_top"] or 10, max_queries=params["retrieve_max_queries"] or retrmod.MAX_QUERIES,
+                           return_details=True, out_path=params["retrieve_out"])
+        if gan.rank == 0:
+            print({k: v for k, v in res.items() if k != "details"})
+    elif params["likelihood_out"]:
         if not gan.load_checkpoint():
             print("--likelihood_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
                   file=sys.stderr)
