@@ -11,14 +11,10 @@
 //                    prefix-counted into node ids; a sort of (root, mention) makes every node's mentions contiguous for the pass
 //                    that accumulates node maps, boxes and centres.
 // No float atomics anywhere: two launches give the same bits.  No host read-back between the three.  Not on the training path.
-#include "bitonic.h"
+#include "sort_select.h"
 
 #define GROUND_MAX_K 1024                       // resolve: 2 K mentions per image, compared pairwise within a token
 #define GROUND_UNASSIGNED 0x7fffffffffffffffull // second sort of assign: behind every slot, in front of the padding
-
-__device__ __forceinline__ bool ground_in_vocab(const long long* t, int V) {
-  return t[0] >= 0 && t[0] < V && t[1] >= 0 && t[1] < V && t[2] >= 0 && t[2] < V;
-}
 
 // LDS: key[P] (8 B), pay[P] (2 B) = 10 * P bytes (40 KB at P = 4096); P >= max(N, K), at most 4 samples per thread
 __global__ __launch_bounds__(1024) void ground_assign_kernel(const long long* __restrict__ tokens, const long long* __restrict__ triples,
@@ -35,7 +31,7 @@ __global__ __launch_bounds__(1024) void ground_assign_kernel(const long long* __
   // 1. (packed triple, slot); a slot with a token outside [0, V) can equal no sample
   for (int u = tid; u < P; u += T) {
     unsigned long long c = SGG_SORT_PAD;
-    if (u < U && ground_in_vocab(tj + (size_t)u * 3, V)) c = sgg_pack_triple(tj[(size_t)u * 3], tj[(size_t)u * 3 + 1], tj[(size_t)u * 3 + 2]);
+    if (u < U && sgg_in_vocab3(tj + (size_t)u * 3, V)) c = sgg_pack_triple(tj[(size_t)u * 3], tj[(size_t)u * 3 + 1], tj[(size_t)u * 3 + 2]);
     key[u] = c;
     pay[u] = (unsigned short)u;
   }
@@ -48,13 +44,9 @@ __global__ __launch_bounds__(1024) void ground_assign_kernel(const long long* __
     slot[e] = -1;
     if (k < N) {
       const long long* t = tokens + ((size_t)k * nb + j) * 3;
-      if (ground_in_vocab(t, V)) {
+      if (sgg_in_vocab3(t, V)) {
         const unsigned long long c = sgg_pack_triple(t[0], t[1], t[2]);
-        int lo = 0, hi = P;                          // first position whose key is >= c
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (key[mid] < c) lo = mid + 1; else hi = mid;
-        }
+        const int lo = sgg_lower_bound(key, 0, P, c);
         if (lo < P && key[lo] == c) slot[e] = pay[lo];
       }
       slot_of_sample[(size_t)j * N + k] = slot[e];
@@ -72,14 +64,8 @@ __global__ __launch_bounds__(1024) void ground_assign_kernel(const long long* __
   for (int k = tid; k < P; k += T) pay[k] = (unsigned short)k;
   sgg_bitonic_pairs(key, pay, P);
   for (int q = tid; q < N; q += T) members[(size_t)j * N + q] = key[q] < (unsigned long long)K ? (int)pay[q] : -1;
-  for (int u = tid; u <= K; u += T) {               // first position whose slot is >= u (slots >= U have no sample: start[U])
-    int lo = 0, hi = N;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (key[mid] < (unsigned long long)u) lo = mid + 1; else hi = mid;
-    }
-    start[(size_t)j * (K + 1) + u] = lo;
-  }
+  // first position whose slot is >= u (slots >= U have no sample: start[U])
+  for (int u = tid; u <= K; u += T) start[(size_t)j * (K + 1) + u] = sgg_lower_bound(key, 0, N, (unsigned long long)u);
 }
 
 // grid (K, nb), 256 threads over the 3 * L cells of the slot
@@ -221,19 +207,7 @@ __global__ __launch_bounds__(1024) void ground_resolve_kernel(const float* __res
     const int m = tid * C + e;
     mine += m < M && parent[m] == m;
   }
-  int incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  int base = incl - mine, total = 0;
-  for (int w = 0; w < waves; ++w) {
-    if (w < wave) base += wave_tot[w];
-    total += wave_tot[w];
-  }
+  int total, base = sgg_block_scan(mine, wave_tot, &total);
   for (int e = 0; e < C; ++e) {
     const int m = tid * C + e;
     if (m < M && parent[m] == m) node[m] = base++;
@@ -310,19 +284,13 @@ __global__ __launch_bounds__(1024) void ground_resolve_kernel(const float* __res
     node_mentions[nj + n] = -1;
     int* bx = node_box + (nj + n) * 4;
     bx[0] = -1; bx[1] = -1; bx[2] = -1; bx[3] = -1;
-    node_center[(nj + n) * 2] = __uint_as_float(0x7fc00000u);
-    node_center[(nj + n) * 2 + 1] = __uint_as_float(0x7fc00000u);
+    node_center[(nj + n) * 2] = SGG_QNAN;
+    node_center[(nj + n) * 2 + 1] = SGG_QNAN;
   }
   const size_t pad0 = (size_t)total * L, pad1 = (size_t)2 * K * L;
   for (size_t e = pad0 + tid; e < pad1; e += T) node_map[nj * L + e] = 0.f;
 #undef GROUND_MAP
 #undef GROUND_TOKEN
-}
-
-static int ground_sort_size(int n) {              // power of two >= n; at least two entries per thread
-  int P = 128;
-  while (P < n) P <<= 1;
-  return P;
 }
 
 extern "C" int sgg_ground_assign(const long long* tokens, const long long* triples, const int* n_distinct, int N, int nb, int K, int V,
@@ -331,10 +299,9 @@ extern "C" int sgg_ground_assign(const long long* tokens, const long long* tripl
   SGG_CHECK_ARG(K >= 1 && K <= SGG_SORT_MAX_P, "sgg_ground_assign: 1 <= K <= %d list slots per image (got %d)", SGG_SORT_MAX_P, K);
   SGG_CHECK_ARG(nb >= 1 && V >= 1 && V <= SGG_SORT_MAX_V, "sgg_ground_assign: nb >= 1 and 1 <= V <= 2^21 (got nb = %d, V = %d)", nb, V);
   SGG_CHECK_ARG(tokens && triples && n_distinct && slot_of_sample && members && start, "sgg_ground_assign: null pointer");
-  const int P = ground_sort_size(N > K ? N : K);
-  const int T = P / 2 > 1024 ? 1024 : P / 2;      // 64 .. 1024: at most 4 entries per thread
-  hipLaunchKernelGGL(ground_assign_kernel, dim3(nb), dim3(T), (size_t)P * 10, (hipStream_t)stream, tokens, triples, n_distinct, N, nb,
-                     K, V, P, slot_of_sample, members, start);
+  const sgg_sort_geometry g(N > K ? N : K, 128);  // at most 4 entries per thread
+  hipLaunchKernelGGL(ground_assign_kernel, dim3(nb), dim3(g.T), (size_t)g.P * 10, (hipStream_t)stream, tokens, triples, n_distinct, N, nb,
+                     K, V, g.P, slot_of_sample, members, start);
   SGG_LAUNCH_CHECK("sgg_ground_assign");
   return SGG_OK;
 }
@@ -366,10 +333,9 @@ extern "C" int sgg_ground_resolve(const float* maps, const long long* triples, c
   SGG_CHECK_ARG(box_frac > 0.f && box_frac <= 1.f, "sgg_ground_resolve: box_frac must be in (0, 1] (got %g)", (double)box_frac);
   SGG_CHECK_ARG(maps && triples && n_distinct && n_pooled && mention_node && n_nodes && node_word && node_first && node_weight &&
                 node_mentions && node_map && node_box && node_center, "sgg_ground_resolve: null pointer");
-  const int P = ground_sort_size(2 * K);
-  const int T = P / 2 > 1024 ? 1024 : P / 2;      // 64 .. 1024
-  hipLaunchKernelGGL(ground_resolve_kernel, dim3(nb), dim3(T), (size_t)P * 22, (hipStream_t)stream, maps, triples, n_distinct, n_pooled,
-                     K, Hf, Wf, overlap, box_frac, P, mention_node, n_nodes, node_word, node_first, node_weight, node_mentions,
+  const sgg_sort_geometry g(2 * K, 128);
+  hipLaunchKernelGGL(ground_resolve_kernel, dim3(nb), dim3(g.T), (size_t)g.P * 22, (hipStream_t)stream, maps, triples, n_distinct, n_pooled,
+                     K, Hf, Wf, overlap, box_frac, g.P, mention_node, n_nodes, node_word, node_first, node_weight, node_mentions,
                      node_map, node_box, node_center);
   SGG_LAUNCH_CHECK("sgg_ground_resolve");
   return SGG_OK;

@@ -8,16 +8,12 @@
 //                     3. every prediction slot u < min(n_distinct, K) binary-searches the sorted keys and writes u into pos of
 //                        the head of the run it finds.  The list is distinct, so at most one slot writes a row.
 // Integers only: two launches give the same bits.  Not on the training path.
-#include "bitonic.h"
+#include "sort_select.h"
 
 #define MATCH_ABSENT (-1)
 #define MATCH_DUPLICATE (-2)
 #define MATCH_PADDING (-3)
 #define MATCH_INVALID (-4)
-
-__device__ __forceinline__ bool match_in_vocab(const long long* t, int V) {
-  return t[0] >= 0 && t[0] < V && t[1] >= 0 && t[1] < V && t[2] >= 0 && t[2] < V;
-}
 
 // LDS: key[P] (8 B), pay[P] (2 B) = 10 * P bytes (40 KB at P = 4096)
 __global__ __launch_bounds__(1024) void match_triples_kernel(const long long* __restrict__ ranked, const int* __restrict__ n_distinct,
@@ -40,7 +36,7 @@ __global__ __launch_bounds__(1024) void match_triples_kernel(const long long* __
     if (m < M) {
       int code = MATCH_PADDING;
       if (m < count) {
-        const bool ok = match_in_vocab(g + (size_t)m * 3, V);
+        const bool ok = sgg_in_vocab3(g + (size_t)m * 3, V);
         code = ok ? MATCH_ABSENT : MATCH_INVALID;
         if (ok) c = sgg_pack_triple(g[(size_t)m * 3], g[(size_t)m * 3 + 1], g[(size_t)m * 3 + 2]);
       }
@@ -66,13 +62,9 @@ __global__ __launch_bounds__(1024) void match_triples_kernel(const long long* __
   const long long* rj = ranked + (size_t)j * K * 3;
   for (int u = tid; u < U; u += T) {
     const long long* t = rj + (size_t)u * 3;
-    if (!match_in_vocab(t, V)) continue;
+    if (!sgg_in_vocab3(t, V)) continue;
     const unsigned long long c = sgg_pack_triple(t[0], t[1], t[2]);
-    int lo = 0, hi = P;                            // first position whose key is >= c
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (key[mid] < c) lo = mid + 1; else hi = mid;
-    }
+    const int lo = sgg_lower_bound(key, 0, P, c);
     if (lo < P && key[lo] == c) pj[pay[lo]] = u;
   }
   __syncthreads();
@@ -86,11 +78,9 @@ extern "C" int sgg_match_triples(const long long* ranked, const int* n_distinct,
                 SGG_SORT_MAX_P, M);
   SGG_CHECK_ARG(nb >= 1 && V >= 1 && V <= SGG_SORT_MAX_V, "sgg_match_triples: nb >= 1 and 1 <= V <= 2^21 (got nb = %d, V = %d)", nb, V);
   SGG_CHECK_ARG(ranked && n_distinct && gt && gt_count && pos && n_gt, "sgg_match_triples: null pointer");
-  int P = 128;                                   // power of two >= M; at least two entries per thread
-  while (P < M) P <<= 1;
-  const int T = P / 2 > 1024 ? 1024 : P / 2;     // 64 .. 1024
-  hipLaunchKernelGGL(match_triples_kernel, dim3(nb), dim3(T), (size_t)P * 10, (hipStream_t)stream, ranked, n_distinct, K, gt, gt_count,
-                     M, V, P, pos, n_gt);
+  const sgg_sort_geometry g(M, 128);
+  hipLaunchKernelGGL(match_triples_kernel, dim3(nb), dim3(g.T), (size_t)g.P * 10, (hipStream_t)stream, ranked, n_distinct, K, gt, gt_count,
+                     M, V, g.P, pos, n_gt);
   SGG_LAUNCH_CHECK("sgg_match_triples");
   return SGG_OK;
 }

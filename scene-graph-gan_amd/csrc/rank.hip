@@ -7,17 +7,7 @@
 //                       the run length (binary search for its end) is the triple's count;
 //                    4. prefix sum of the run heads in rank order = the slot of every distinct triple.
 // Not on the training path.
-#include "bitonic.h"
-
-#define RANK_MAX_N SGG_SORT_MAX_P
-#define RANK_MAX_V SGG_SORT_MAX_V       // three tokens pack into 63 bits
-#define RANK_PAD SGG_SORT_PAD           // sorts behind every sample in both sorts
-
-// float -> unsigned whose order is the float order (-inf lowest, +inf = 0xff800000 highest); +-0 are one value
-__device__ __forceinline__ unsigned rank_orderable(float s) {
-  const unsigned b = (s == 0.f) ? 0u : __float_as_uint(s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+#include "sort_select.h"
 
 __device__ __forceinline__ float rank_score(const float* __restrict__ d, int k, int nb, int j) {
   const float* p = d + ((size_t)k * nb + j) * 3;
@@ -40,12 +30,12 @@ __global__ __launch_bounds__(1024) void rank_triples_kernel(const long long* __r
 
   // 1. scores -> (orderable key, sample index)
   for (int k = tid; k < P; k += T) {
-    unsigned long long kk = RANK_PAD;
+    unsigned long long kk = SGG_SORT_PAD;                         // behind every sample in both sorts
     if (k < N) {
       const float s = rank_score(d, k, nb, j);
       if (sample_scores) sample_scores[(size_t)j * N + k] = s;
       unsigned o = 0xffffffffu;                                 // NaN: behind every number, in sample order
-      if (s == s) o = descending ? ~rank_orderable(s) : rank_orderable(s);
+      if (s == s) o = descending ? ~sgg_orderable(s) : sgg_orderable(s);
       kk = ((unsigned long long)o << 32) | (unsigned)k;
     }
     key[k] = kk;
@@ -56,7 +46,7 @@ __global__ __launch_bounds__(1024) void rank_triples_kernel(const long long* __r
   sgg_bitonic_pairs(key, order, P);
   // 3. (packed triple, rank)
   for (int r = tid; r < P; r += T) {
-    unsigned long long c = RANK_PAD;
+    unsigned long long c = SGG_SORT_PAD;
     if (r < N) {
       const long long* t = tokens + ((size_t)order[r] * nb + j) * 3;
       c = sgg_pack_triple(t[0], t[1], t[2]);
@@ -68,31 +58,14 @@ __global__ __launch_bounds__(1024) void rank_triples_kernel(const long long* __r
   for (int q = tid; q < N; q += T) {             // (the first N sorted entries are the samples: the padding sorts last)
     const unsigned long long c = key[q];
     if (q > 0 && key[q - 1] == c) continue;
-    int lo = q + 1, hi = N;                      // first position in (q, N] whose triple differs
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (key[mid] == c) lo = mid + 1; else hi = mid;
-    }
-    cnt[pay[q]] = (unsigned short)(lo - q);      // head of the run = its smallest rank
+    cnt[pay[q]] = (unsigned short)(sgg_upper_bound(key, q + 1, N, c) - q);      // head of the run = its smallest rank
   }
   __syncthreads();
   // 4. slot of every first occurrence: exclusive prefix sum of (cnt > 0) over the ranks, C consecutive ranks per thread
   const int C = P / T;
   int mine = 0;
   for (int e = 0; e < C; ++e) mine += cnt[tid * C + e] > 0;
-  int incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(incl, o, 64);
-    if ((tid & 63) >= o) incl += v;
-  }
-  if ((tid & 63) == 63) wave_tot[tid >> 6] = incl;
-  __syncthreads();
-  int base = incl - mine, total = 0;
-  for (int w = 0; w < (T >> 6); ++w) {
-    if (w < (tid >> 6)) base += wave_tot[w];
-    total += wave_tot[w];
-  }
+  int total, base = sgg_block_scan(mine, wave_tot, &total);
   for (int e = 0; e < C; ++e) {
     const int r = tid * C + e, c = cnt[r];
     if (c == 0) continue;
@@ -112,7 +85,7 @@ __global__ __launch_bounds__(1024) void rank_triples_kernel(const long long* __r
   for (int u = total + tid; u < K; u += T) {
     const size_t o = (size_t)j * K + u;
     triples[o * 3 + 0] = -1; triples[o * 3 + 1] = -1; triples[o * 3 + 2] = -1;
-    scores[o] = __uint_as_float(0x7fc00000u);
+    scores[o] = SGG_QNAN;
     first_rank[o] = -1;
     first_sample[o] = -1;
     counts[o] = 0;
@@ -123,16 +96,14 @@ __global__ __launch_bounds__(1024) void rank_triples_kernel(const long long* __r
 extern "C" int sgg_rank_triples(const long long* tokens, const float* d, int N, int nb, int V, int K, int descending,
                                 long long* triples, float* scores, int* first_rank, int* first_sample, int* counts, int* n_distinct,
                                 float* sample_scores, void* stream) {
-  SGG_CHECK_ARG(N >= 1 && N <= RANK_MAX_N, "sgg_rank_triples: 1 <= N <= %d samples per image (got %d)", RANK_MAX_N, N);
+  SGG_CHECK_ARG(N >= 1 && N <= SGG_SORT_MAX_P, "sgg_rank_triples: 1 <= N <= %d samples per image (got %d)", SGG_SORT_MAX_P, N);
   SGG_CHECK_ARG(K >= 1 && K <= N, "sgg_rank_triples: 1 <= K <= N (got K = %d, N = %d)", K, N);
-  SGG_CHECK_ARG(nb >= 1 && V >= 1 && V <= RANK_MAX_V, "sgg_rank_triples: nb >= 1 and 1 <= V <= 2^21 (got nb = %d, V = %d)", nb, V);
+  SGG_CHECK_ARG(nb >= 1 && V >= 1 && V <= SGG_SORT_MAX_V, "sgg_rank_triples: nb >= 1 and 1 <= V <= 2^21 (got nb = %d, V = %d)", nb, V);
   SGG_CHECK_ARG(descending == 0 || descending == 1, "sgg_rank_triples: descending is 0 or 1 (got %d)", descending);
   SGG_CHECK_ARG(tokens && d && triples && scores && first_rank && first_sample && counts && n_distinct,
                 "sgg_rank_triples: null pointer");
-  int P = 128;                                   // power of two >= N; at least two entries per thread
-  while (P < N) P <<= 1;
-  const int T = P / 2 > 1024 ? 1024 : P / 2;     // 64 .. 1024, divides P
-  hipLaunchKernelGGL(rank_triples_kernel, dim3(nb), dim3(T), (size_t)P * 14, (hipStream_t)stream, tokens, d, N, nb, K, P,
+  const sgg_sort_geometry g(N, 128);
+  hipLaunchKernelGGL(rank_triples_kernel, dim3(nb), dim3(g.T), (size_t)g.P * 14, (hipStream_t)stream, tokens, d, N, nb, K, g.P,
                      descending, triples, scores, first_rank, first_sample, counts, n_distinct, sample_scores);
   SGG_LAUNCH_CHECK("sgg_rank_triples");
   return SGG_OK;

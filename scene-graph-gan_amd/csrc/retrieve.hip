@@ -7,31 +7,20 @@
 //                   thread updates the online (max, sum) pair of its query from three LDS operands.  One array of LDS, 49 KB;
 //                   the next round's loads are in flight in registers while the current one is consumed.
 //   retrieve_topk   one workgroup per query: exact radix selection of the K-th smallest 53-bit key (~orderable score, image) - seven
-//                   histogram passes over the row, as kbest_triples selects tokens - then ONE bitonic sort of the survivors.
+//                   histogram passes over the row - then ONE bitonic sort of the survivors (sgg_select_sorted, csrc/sort_select.h).
 //   retrieve_ranks  one workgroup per query: the keys of its relevant images sorted, every image of the row placed among them by a
 //                   binary search (integer LDS counters), a prefix sum -> 1-based ranks; average precision in fp64 in a fixed order.
 // Finite logits are a precondition of query_logp.  No float atomics: the LDS atomics count integers or hand out slots of an array
 // that is sorted by unique keys afterwards, so two calls give the same bits.  Not on the training path.
-#include "bitonic.h"
+#include "sort_select.h"
 
-#define RETR_NAN __uint_as_float(0x7fc00000u)
 #define RETR_LDS_FLOATS 12288                    // 48 KB: one sample's logits of three full token lists of 4096
 #define RETR_MAX_Q 4096
 #define RETR_MAX_N 4096
 #define RETR_MAX_K 1024
 #define RETR_MAX_REL 4096
-#define RETR_MAX_IMAGES (1 << 21)
+#define RETR_MAX_IMAGES SGG_KEY_MAX_INDEX        // the image is the index of a value key
 #define RETR_MAX_ROUND 64                        // samples per gather round at most (3 * 64 lse values: the first 192 threads load them)
-
-// float -> unsigned whose order is the float order; +-0 are one value (kbest.hip's kbest_orderable)
-__device__ __forceinline__ unsigned retr_orderable(float s) {
-  const unsigned b = (s == 0.f) ? 0u : __float_as_uint(s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-// ascending key order = (score descending, image ascending); 32 + 21 bits
-__device__ __forceinline__ unsigned long long retr_key(float s, int image) {
-  return ((unsigned long long)(unsigned)~retr_orderable(s) << 21) | (unsigned long long)image;
-}
 
 // ---- query_logp ----------------------------------------------------------------------------------------------------------------
 // One query per thread: thread `tid` of tile blockIdx.y owns query blockIdx.y * blockDim.x + tid.
@@ -83,7 +72,7 @@ __global__ __launch_bounds__(RETR_T) void query_logp_kernel(const float* __restr
     const float* x = logits + (size_t)k0 * nb * (size_t)ld;
 #pragma unroll
     for (int i = 0; i < RETR_SLOTS; ++i) {
-      v[i] = RETR_NAN;
+      v[i] = SGG_QNAN;
       if (goff[i] != RETR_BAD && tid + i * T < ns * W) v[i] = x[goff[i]];
     }
     if (tid < 3 * ns) zv = lse[((size_t)(k0 + tid / 3) * nb + j) * 3 + tid % 3];
@@ -113,82 +102,31 @@ __global__ __launch_bounds__(RETR_T) void query_logp_kernel(const float* __restr
         s += expf(lp - m);
     }
   }
-  if (q < Q) scores[(size_t)q * (size_t)lds + (size_t)col0 + j] = live ? m + (logf(s) - logf((float)N)) : RETR_NAN;
+  if (q < Q) scores[(size_t)q * (size_t)lds + (size_t)col0 + j] = live ? m + (logf(s) - logf((float)N)) : SGG_QNAN;
 }
 
 // ---- retrieve_topk ---------------------------------------------------------------------------------------------------------------
-// the key of rank `rem` among the n distinct keys of a row: radix selection, most significant digit first (kbest_triples' loop)
-__device__ __forceinline__ unsigned long long retr_select(const float* __restrict__ x, int n, int rem, int* hist,
-                                                          unsigned long long* prefix_s, int* rem_s) {
-  const int T = blockDim.x, tid = threadIdx.x;
-  unsigned long long prefix = 0;
-  for (int pass = 0; pass < 7; ++pass) {
-    const int width = pass < 6 ? 8 : 5, shift = pass < 6 ? 45 - 8 * pass : 0;
-    for (int b = tid; b < 256; b += T) hist[b] = 0;
-    __syncthreads();
-    for (int t = tid; t < n; t += T) {
-      const unsigned long long k = retr_key(x[t], t);
-      if ((k >> (shift + width)) == prefix) atomicAdd(&hist[(int)(k >> shift) & ((1 << width) - 1)], 1);
-    }
-    __syncthreads();
-    if (tid < 64) {
-      const int c0 = hist[4 * tid], c1 = hist[4 * tid + 1], c2 = hist[4 * tid + 2], c3 = hist[4 * tid + 3];
-      const int tot = c0 + c1 + c2 + c3;
-      int incl = tot;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (tid >= o) incl += v;
-      }
-      const unsigned long long ahead = __ballot(incl > rem);      // (never empty: rem < the keys under this prefix)
-      if (ahead != 0 && tid == __ffsll((long long)ahead) - 1) {
-        int r = rem - (incl - tot), d = 0;
-        if (r >= c0) { r -= c0; d = 1; if (r >= c1) { r -= c1; d = 2; if (r >= c2) { r -= c2; d = 3; } } }
-        *prefix_s = (prefix << width) | (unsigned long long)(4 * tid + d);
-        *rem_s = r;
-      }
-    }
-    __syncthreads();
-    prefix = *prefix_s;
-    rem = *rem_s;
-  }
-  return prefix;
-}
-
-// LDS: sel 8 KB + pay 2 KB + hist 1 KB
+// LDS: sel 8 KB + pay 2 KB + the selection's scratch 1 KB
 __global__ __launch_bounds__(1024) void retrieve_topk_kernel(const float* __restrict__ scores, long long lds, int n, int K, int M, int P,
                                                              int* __restrict__ idx, float* __restrict__ top) {
   __shared__ unsigned long long sel[RETR_MAX_K];
   __shared__ unsigned short sel_pay[RETR_MAX_K];
-  __shared__ int hist[256];
-  __shared__ unsigned long long prefix_s;
-  __shared__ int rem_s, cnt_s;
+  __shared__ sgg_select_lds sl;
   const int T = blockDim.x, tid = threadIdx.x;
   const size_t q = blockIdx.x;
   const float* x = scores + q * (size_t)lds;
-  const unsigned long long kth = retr_select(x, n, M - 1, hist, &prefix_s, &rem_s);
-  // the M keys up to it (unique keys: exactly M), in any order, then sorted
-  for (int r = tid; r < P; r += T) { sel[r] = SGG_SORT_PAD; sel_pay[r] = 0; }
-  if (tid == 0) cnt_s = 0;
-  __syncthreads();
-  for (int t = tid; t < n; t += T) {
-    const unsigned long long k = retr_key(x[t], t);
-    if (k <= kth) {
-      const int pos = atomicAdd(&cnt_s, 1);
-      if (pos < P) sel[pos] = k;
-    }
-  }
-  sgg_bitonic_pairs(sel, sel_pay, P);
+  // the M best images under (score descending, image ascending)
+  sgg_select_sorted([x](int t) { return sgg_value_key(x[t], t); }, n, M, sel, sel_pay, P, sl);
   for (int u = tid; u < K; u += T) {
     const size_t o = q * (size_t)K + u;
     if (u < M) {
-      const int image = (int)(sel[u] & (unsigned long long)(RETR_MAX_IMAGES - 1));
+      const int image = sgg_value_key_index(sel[u]);
       const bool in = image < n;                 // (always: the M smallest keys are real ones)
       idx[o] = in ? image : -1;
-      top[o] = in ? x[image] : RETR_NAN;         // the input's own bits (the key has folded -0 into +0)
+      top[o] = in ? x[image] : SGG_QNAN;         // the input's own bits (the key has folded -0 into +0)
     } else {
       idx[o] = -1;
-      top[o] = RETR_NAN;
+      top[o] = SGG_QNAN;
     }
   }
 }
@@ -219,15 +157,14 @@ __global__ __launch_bounds__(1024) void retrieve_ranks_kernel(const float* __res
     return;
   }
   const int R = (int)R64;
-  int P = 64;
-  while (P < R) P <<= 1;
+  const int P = sgg_sort_geometry(R, 64).P;
   if (tid == 0) bad_s = 0;
   __syncthreads();
   for (int i = tid; i < P; i += T) {
     unsigned long long k = SGG_SORT_PAD;
     if (i < R) {
       const int image = rel_idx[p0 + i];
-      if (image >= 0 && image < n) k = retr_key(x[image], image);
+      if (image >= 0 && image < n) k = sgg_value_key(x[image], image);
       else bad_s = 1;
     }
     key[i] = k;
@@ -245,12 +182,7 @@ __global__ __launch_bounds__(1024) void retrieve_ranks_kernel(const float* __res
   }
   // image t precedes every relevant key above its own: count it at the first such position
   for (int t = tid; t < n; t += T) {
-    const unsigned long long k = retr_key(x[t], t);
-    int lo = 0, hi = R;                          // first position whose key is > k
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (key[mid] <= k) lo = mid + 1; else hi = mid;
-    }
+    const int lo = sgg_upper_bound(key, 0, R, sgg_value_key(x[t], t));
     if (lo < R) atomicAdd(&ahead[lo], 1);
   }
   __syncthreads();
@@ -263,16 +195,7 @@ __global__ __launch_bounds__(1024) void retrieve_ranks_kernel(const float* __res
     loc[c] = (c < C && i < P) ? ahead[i] : 0;
     run += loc[c];
   }
-  int incl = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  int before = incl - run;
-  for (int w = 0; w < wave; ++w) before += wave_tot[w];
+  int before = sgg_block_scan(run, wave_tot);
   // rank of the i-th sorted relevant image = 1 + images ahead of it; AP = mean_i (i + 1) / rank_i, fp64, fixed order
   double part = 0.0;
 #pragma unroll
@@ -333,10 +256,9 @@ extern "C" int sgg_retrieve_topk(const float* scores, long long lds, int Q, int 
   SGG_CHECK_ARG(lds >= n_images, "sgg_retrieve_topk: row stride lds >= n_images (got lds = %lld, n_images = %d)", lds, n_images);
   SGG_CHECK_ARG(scores && idx && top, "sgg_retrieve_topk: null pointer");
   const int M = K < n_images ? K : n_images;
-  int P = 64;
-  while (P < M) P <<= 1;
-  const int T = n_images >= 1024 ? 1024 : 256;
-  hipLaunchKernelGGL(retrieve_topk_kernel, dim3(Q), dim3(T), 0, (hipStream_t)stream, scores, lds, n_images, K, M, P, idx, top);
+  const int T = n_images >= 1024 ? 1024 : 256;   // threads for the passes over the row, not for the sort of the M survivors
+  hipLaunchKernelGGL(retrieve_topk_kernel, dim3(Q), dim3(T), 0, (hipStream_t)stream, scores, lds, n_images, K, M,
+                     sgg_sort_geometry(M, 64).P, idx, top);
   SGG_LAUNCH_CHECK("sgg_retrieve_topk");
   return SGG_OK;
 }
