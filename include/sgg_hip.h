@@ -674,6 +674,52 @@ int sgg_vector_stats(const float* x, int n, float threshold, double* out, void* 
 
 int sgg_fill(float* p, long long n, float value, void* stream);
 
+/* ---- training-time augmentation in the input kernel (csrc/augment.hip) ----------------------------------------------------------
+ * Random crop, mirror and colour jitter of the loader's packed uint8 batch, drawn on the device and applied by the launch that resizes
+ * and standardises it.  The reference has none (train.py:167-172 feeds every image pixel-identical every epoch).  numpy restatement:
+ * tests/augment_ref.py; host path of the CPU loader: sgg_amd/augment.py.
+ *
+ * Amplitudes arrive as 16-bit fixed point, q = round(a * 65536):
+ *   crop_q in [1, 65536]        the smallest side fraction of the crop box; 65536 = off: the box is the image
+ *   flip_q in [0, 65536]        probability of mirroring the output; 0 = off
+ *   brightness_q, contrast_q, saturation_q in [0, 65535]   factor in [1 - a, 1 + a]; 0 = off: factor exactly 1.0f, stage not executed
+ *
+ * The table, one row per example b, a pure function of (seed, draw = draw0 + b as a 64-bit sum, H_b, W_b, amplitudes, labels):
+ *   box int32 [B][6] = y0, x0, ch, cw, flip, 0 (reserved)        factors fp32 [B][4] = brightness, contrast, saturation, grey mean
+ * Philox4x32-10, key (seed & 0xffffffff, (seed >> 32) ^ 0x41554731) - seed is --seed, never the rank; the relaxation kernels key on
+ * (rank, --seed) - counters (0, 0, draw lo, draw hi) -> words w0..w3 and (1, 0, draw lo, draw hi) -> w4..w7.  With r(w) = w >> 8:
+ *   hmin = max(1, (H * crop_q + 65535) >> 16)     ch = hmin + (((H - hmin + 1) * r(w0)) >> 24)     y0 = ((H - ch + 1) * r(w1)) >> 24
+ *   wmin, cw, x0 the same from W, w2, w3 (64-bit products)          flip = (w4 >> 16) < flip_q
+ *   factor(a_q, w) = (float)(2^39 + a_q * (2 * (w >> 9) + 1 - 2^23)) * 2^-39: brightness from w5, contrast from w6, saturation w7
+ * - integers throughout and ONE int64 -> fp32 conversion (round to nearest even) per factor, no transcendental function: 0 <= y0,
+ * y0 + ch <= H always, crop_q = 65536 gives (0, 0, H, W), and numpy reproduces every row bit for bit.
+ * Grey mean (contrast_q > 0 only, else 0.0f): the integer sum of 77 R + 150 G + 29 B over the SOURCE pixels of the box, 64 bits,
+ * divided by 256 * ch * cw in fp64 and rounded once to fp32.  32 workgroups per image, one 64-bit integer atomic each into
+ * `workspace` (sgg_augment_plan_workspace_bytes(B), 8-byte aligned, needed with contrast_q > 0 only): integer sums commute, the
+ * result does not depend on the order.  No float atomics.
+ * Labels: swap int32 [V] maps a word to the word with the tokens `left` and `right` exchanged (itself without them, -1 where the
+ * vocabulary lacks the counterpart: sgg_amd/augment.py flip_swap_table).  An example whose triple holds a word with swap < 0 (or a
+ * label outside [0, V)) is not mirrored: its flip is cleared.  labels_out int64 [B][3] = the remapped triple of a mirrored example,
+ * labels_in's row otherwise.  B <= 65535.
+ *
+ * sgg_augment_resize: dst [B][out_h][out_w][3] fp32 from src and the table alone (`stages`: bit 0 saturation, bit 1 contrast, bit 2
+ * brightness).  Every table row is clamped into its image first (ch to [1, H], y0 to [0, H - ch], ...; flip = box[4] != 0): no row
+ * is followed out of the image.  Output pixel (y, x), with xs = flip ? out_w - 1 - x : x (the mirror of the unflipped output):
+ *   the legacy TF-1.x grid of sgg_resize_bilinear_tf1 laid over the BOX: sy = (float)ch / out_h, fy = fl(y * sy), row y0 + floor(fy),
+ *   upper neighbour min(floor(fy) + 1, ch - 1) - clamped to the box, not the image - and the same in x; every product rounded
+ *   before it is added.  With stages = 0 the output equals sgg_resize_bilinear_tf1 on a copy of the box's pixels bit for bit.
+ *   Then on the interpolated 0..255 values v_c:  saturation v = g + s (v - g), g = 0.299 v_r + 0.587 v_g + 0.114 v_b of that pixel;
+ *   contrast v = m + c (v - m), m the grey mean;  brightness v = b v;  clamp to [0, 255] (only where a stage ran);
+ *   (v - means[c]) / stds[c].  The colour stages are plain fp32 and may be fused: they are compared with fp64 (tests/augment_ref.py). */
+size_t sgg_augment_plan_workspace_bytes(int B);
+int sgg_augment_plan(const unsigned char* src, const long long* offsets, const int* heights, const int* widths, const long long* labels_in,
+                     const int* swap, int V, int B, int crop_q, int flip_q, int brightness_q, int contrast_q, int saturation_q,
+                     unsigned long long seed, unsigned long long draw0, int* box, float* factors, long long* labels_out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int sgg_augment_resize(const unsigned char* src, const long long* offsets, const int* heights, const int* widths, const int* box,
+                       const float* factors, int stages, float* dst, int B, int out_h, int out_w, const float* means, const float* stds,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,14 @@ def _parse_task(task):
     return parse_image(path, means, stds, side)
 
 
+def _augment_task(task):
+    """Worker entry point of an augmenting CPU loader: decode, then plan + augment_image at the example's stream position
+    (sgg_amd/augment.py) -> (float32 [side, side, 3], int64 [3])."""
+    from .augment import augment_example
+    path, means, stds, side, spec, seed, draw, label, swap = task
+    return augment_example(decode_rgb(path), spec, seed, draw, label, swap, means, stds, side)
+
+
 class ShuffledStream:
     """Example indices in the order of the reference's training / validation datasets (train.py:176-179):
 
@@ -137,10 +145,18 @@ class PrefetchLoader:
     equal to `resize_bilinear_tf1` within a few ulps), so batch k+1 is decoded, copied and resized while batch k trains.
     On the CPU (tests; `processes=True` uses spawned worker processes instead of threads) the workers run `parse_image`.
     `index_fn(it)` gives the example indices of iteration `it` (the trainer's shard of the shuffled file list); iteration
-    order is deterministic."""
+    order is deterministic.
+
+    augment = an AugmentSpec (or its text; sgg_amd/augment.py): training-time crop / mirror / colour jitter.  Row j of batch `it` on
+    rank `rank` of `world` sits at position (it * world + rank) * B + j of the training stream, and its parameters are a pure
+    function of (seed, that position, the image's size, the spec, its labels) - a resumed run (start = k) and every data-parallel
+    layout of the same global batch see the same pixels.  On a HIP device the producer launches sgg_augment_plan +
+    sgg_augment_resize in place of the resize kernel, on the copy stream; on the CPU the workers run augment.augment_image.  The
+    labels returned are the remapped ones (swap = augment.flip_swap_table(vocabulary): a mirrored "left of" is a "right of"; without
+    a table labels are never remapped).  augment=None: nothing of this runs."""
 
     def __init__(self, files, labels, batch_size, index_fn, means, stds, device, num_iterations, start=0, workers=16, depth=2,
-                 side=IMAGE_SIDE, processes=False):
+                 side=IMAGE_SIDE, processes=False, augment=None, seed=0, rank=0, world=1, swap=None):
         self.files, self.labels = files, np.asarray(labels, dtype=np.int64)
         self.B, self.index_fn, self.means, self.stds, self.side = batch_size, index_fn, means, stds, side
         self.device = torch.device(device)
@@ -153,6 +169,14 @@ class PrefetchLoader:
         else:
             self.pool = ThreadPoolExecutor(max_workers=workers)
         self.depth = depth
+        self.augment = None
+        if augment is not None:
+            from .augment import AugmentSpec
+            self.augment = AugmentSpec.parse(augment)
+            self.seed, self.rank, self.world = int(seed), int(rank), int(world)
+            if swap is None:                    # no vocabulary given: every word is its own mirror image
+                swap = np.arange(int(self.labels.max()) + 1 if self.labels.size else 1, dtype=np.int32)
+            self.swap = np.ascontiguousarray(swap, dtype=np.int32)
         pin = self.device.type == "cuda"
         self.K = None
         if pin:
@@ -162,6 +186,8 @@ class PrefetchLoader:
             self.meta = [torch.empty(batch_size * 2, dtype=torch.int64, pin_memory=True) for _ in range(depth)]   # offsets | (h, w) pairs
             self.d_means = torch.tensor(np.asarray(means, np.float32), device=self.device)
             self.d_stds = torch.tensor(np.asarray(stds, np.float32), device=self.device)
+            if self.augment is not None:
+                self.d_swap = torch.from_numpy(self.swap).to(self.device)
         self.host = [torch.empty((batch_size, side, side, 3), dtype=torch.float32) for _ in range(depth if not pin else 0)]
         self.free = queue.Queue()
         for i in range(depth):
@@ -222,6 +248,20 @@ class PrefetchLoader:
     def _fill(self, dst, j, path):
         dst[j] = torch.from_numpy(parse_image(path, self.means, self.stds, self.side))
 
+    def _draw0(self, it):
+        """Stream position of row 0 of this rank's batch `it`."""
+        return (int(it) * self.world + self.rank) * self.B
+
+    def _fill_augmented(self, buf, lab, it, idx):
+        """CPU path with augmentation: the workers decode and augment, the labels come back remapped."""
+        means, stds = np.asarray(self.means, np.float32), np.asarray(self.stds, np.float32)
+        tasks = [(self.files[i], means, stds, self.side, self.augment, self.seed, self._draw0(it) + j, self.labels[i], self.swap)
+                 for j, i in enumerate(idx)]
+        chunk = {"chunksize": max(1, len(tasks) // 64)} if self.processes else {}
+        for j, (arr, label) in enumerate(self.pool.map(_augment_task, tasks, **chunk)):
+            buf[j] = torch.from_numpy(arr)
+            lab[j] = label
+
     def _produce(self):
         try:
             for it in range(self.start, self.stop):
@@ -230,18 +270,22 @@ class PrefetchLoader:
                 if slot is None:
                     return
                 if self.K is not None:
-                    if not self._put_ready(self._produce_device(slot, idx)):
+                    if not self._put_ready(self._produce_device(slot, idx, it)):
                         return
                     continue
                 buf = self.host[slot]
-                if self.processes:
+                aug_labels = None
+                if self.augment is not None:
+                    aug_labels = np.empty((len(idx), 3), np.int64)
+                    self._fill_augmented(buf, aug_labels, it, idx)
+                elif self.processes:
                     means, stds = np.asarray(self.means, np.float32), np.asarray(self.stds, np.float32)
                     tasks = [(self.files[i], means, stds, self.side) for i in idx]
                     for j, arr in enumerate(self.pool.map(_parse_task, tasks, chunksize=max(1, len(tasks) // 64))):
                         buf[j] = torch.from_numpy(arr)
                 else:
                     list(self.pool.map(lambda jp: self._fill(buf, jp[0], self.files[jp[1]]), enumerate(idx)))
-                labels = torch.from_numpy(self.labels[idx])
+                labels = torch.from_numpy(self.labels[idx] if aug_labels is None else aug_labels)
                 if self.copy_stream is not None:
                     with torch.cuda.stream(self.copy_stream):
                         dev_images = buf.to(self.device, non_blocking=True)
@@ -257,8 +301,9 @@ class PrefetchLoader:
         finally:
             self._put_ready(None)         # (gives up when close() was called: nobody is waiting then)
 
-    def _produce_device(self, slot, idx):
-        """Decode on worker threads, pack, one host-to-device copy, one resize + standardise launch (copy stream)."""
+    def _produce_device(self, slot, idx, it=0):
+        """Decode on worker threads, pack, one host-to-device copy, one resize + standardise launch (copy stream) - with
+        augmentation the plan launches and the augmenting resize in its place."""
         rgbs = list(self.pool.map(lambda i: decode_rgb(self.files[i]), idx))
         sizes = [a.size for a in rgbs]
         total = int(sum(sizes))
@@ -284,7 +329,16 @@ class PrefetchLoader:
             dev_labels = labels.pin_memory().to(self.device, non_blocking=True)
             dev_images = torch.empty((len(rgbs), self.side, self.side, 3), dtype=torch.float32, device=self.device)
             d_h, d_w = d_hw[:, 0].contiguous(), d_hw[:, 1].contiguous()
-            self.K.resize_bilinear_tf1(d_packed, d_offs, d_h, d_w, dev_images, self.d_means, self.d_stds)
+            if self.augment is None:
+                self.K.resize_bilinear_tf1(d_packed, d_offs, d_h, d_w, dev_images, self.d_means, self.d_stds)
+            else:
+                box = torch.empty((len(rgbs), 6), dtype=torch.int32, device=self.device)
+                factors = torch.empty((len(rgbs), 4), dtype=torch.float32, device=self.device)
+                plain_labels, dev_labels = dev_labels, torch.empty_like(dev_labels)
+                self.K.augment_plan(d_packed, d_offs, d_h, d_w, plain_labels, self.d_swap, self.augment.quantised(), self.seed,
+                                    self._draw0(it), box, factors, dev_labels)
+                self.K.augment_resize(d_packed, d_offs, d_h, d_w, box, factors, self.augment.stages, dev_images, self.d_means,
+                                      self.d_stds)
             done = torch.cuda.Event()
             done.record(self.copy_stream)
         return (slot, dev_images, dev_labels, done)

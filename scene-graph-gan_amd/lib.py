@@ -120,6 +120,9 @@ SIGNATURES = {
     "sgg_arena_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _vp, _sz, _vp, _vp]),
     "sgg_vector_stats": (_i, [_vp, _i, _f, _vp, _vp]),
     "sgg_fill": (_i, [_vp, _ll, _f, _vp]),
+    "sgg_augment_plan_workspace_bytes": (_sz, [_i]),
+    "sgg_augment_plan": (_i, [_vp] * 6 + [_i] * 7 + [_ull, _ull, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgg_augment_resize": (_i, [_vp] * 6 + [_i, _vp, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 # timing label of a conv_wgrad call by the first matching prefix of the kernel the library routes it to (bench.py's output and
@@ -888,6 +891,38 @@ class HipKernels:
         B, oh, ow, _ = out.shape
         self._check(self.lib.sgg_resize_bilinear_tf1(_p(packed), _p(offsets), _p(heights), _p(widths), _p(out), B, oh, ow, _p(means),
                                                      _p(stds), self._stream()), "sgg_resize_bilinear_tf1")
+
+    def augment_plan(self, packed, offsets, heights, widths, labels_in, swap, amplitudes_q, seed, draw0, box, factors, labels_out):
+        """The augmentation table of a packed batch (include/sgg_hip.h, "training-time augmentation"): amplitudes_q = (crop, flip,
+        brightness, contrast, saturation) as 16-bit fixed point, example b at stream position draw0 + b -> box int32 [B,6], factors
+        fp32 [B,4], labels_out int64 [B,3] (labels_in [B,3] with mirrored examples remapped through swap int32 [V])."""
+        self._dev(packed, offsets, heights, widths, labels_in, swap, box, factors, labels_out)
+        assert packed.dtype == torch.uint8 and offsets.dtype == torch.int64 and heights.dtype == torch.int32 and widths.dtype == torch.int32
+        assert labels_in.dtype == torch.int64 and labels_out.dtype == torch.int64 and swap.dtype == torch.int32
+        assert box.dtype == torch.int32 and factors.dtype == torch.float32
+        B = offsets.shape[0]
+        assert labels_in.is_contiguous() and labels_out.is_contiguous() and box.is_contiguous() and factors.is_contiguous()
+        assert labels_in.shape == (B, 3) and labels_out.shape == (B, 3) and box.shape == (B, 6) and factors.shape == (B, 4)
+        crop_q, flip_q, bright_q, contrast_q, sat_q = (int(q) for q in amplitudes_q)
+        ws, nbytes = None, 0
+        if contrast_q > 0:
+            nbytes = self.lib.sgg_augment_plan_workspace_bytes(B)
+            ws = self.workspace(nbytes)
+        self._check(self.lib.sgg_augment_plan(_p(packed), _p(offsets), _p(heights), _p(widths), _p(labels_in), _p(swap), swap.numel(), B,
+                                              crop_q, flip_q, bright_q, contrast_q, sat_q, int(seed) & (2 ** 64 - 1),
+                                              int(draw0) & (2 ** 64 - 1), _p(box), _p(factors), _p(labels_out), _p(ws), nbytes,
+                                              self._stream()), "sgg_augment_plan")
+
+    def augment_resize(self, packed, offsets, heights, widths, box, factors, stages, out, means, stds):
+        """out [B,oh,ow,3] fp32 = the crop box of every image resized on the TF-1.x grid, mirrored where box[b,4] != 0, the colour
+        stages of `stages` (bit 0 saturation, 1 contrast, 2 brightness) applied, standardised: a function of the source and the table."""
+        self._dev(packed, offsets, heights, widths, box, factors, out, means, stds)
+        assert packed.dtype == torch.uint8 and offsets.dtype == torch.int64 and heights.dtype == torch.int32 and widths.dtype == torch.int32
+        assert box.dtype == torch.int32 and factors.dtype == torch.float32 and box.is_contiguous() and factors.is_contiguous()
+        B, oh, ow, _ = out.shape
+        assert out.is_contiguous() and box.shape == (B, 6) and factors.shape == (B, 4)
+        self._check(self.lib.sgg_augment_resize(_p(packed), _p(offsets), _p(heights), _p(widths), _p(box), _p(factors), int(stages),
+                                                _p(out), B, oh, ow, _p(means), _p(stds), self._stream()), "sgg_augment_resize")
 
     def interpolate(self, real, fake, alpha, out):
         self._dev(real, fake, alpha, out)

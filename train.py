@@ -47,6 +47,7 @@ from sgg_amd import guard as guardmod
 from sgg_amd import kbest as kbestmod
 from sgg_amd import retrieve as retrmod
 from sgg_amd.api import kernels_for
+from sgg_amd.augment import AugmentSpec, flip_swap_table
 from sgg_amd.data import PrefetchLoader, ShuffledStream, parse_image
 from sgg_amd.diagnostics import raise_if_nonfinite
 from sgg_amd.params import EMBED_DIM
@@ -168,7 +169,7 @@ class SceneGraphGAN(object):
                  synthetic=None, device=None, seed=0, two_streams=True, reuse_g_encoder=True, shuffle_buffer=True,
                  ema_decay=0.0, eval_live=False, accumulate=1, clip_grad_norm=0.0, skip_nonfinite=False,
                  pretrain_iterations=0, mle_weight=0.0, validate_nll=False, generator_output=None, relax_tau=None, relax_hard=False,
-                 generator_gradient=None, score_baseline=None, entropy_weight=None, score_samples=None):
+                 generator_gradient=None, score_baseline=None, entropy_weight=None, score_samples=None, augment=None):
         # Hyperparameters (train.py:26-32)
         self.CRITIC_ITERS = int(critic_iters)
         self.BATCH_SIZE = int(batch_size)
@@ -246,6 +247,14 @@ class SceneGraphGAN(object):
         if self.relax_hard and generator_output == "logits":
             raise ValueError("relax_hard needs generator_output softmax or gumbel (got logits)")
         self.relax_tau = self._relax_flags[1] or (1.0, 1.0, 0)
+        # augment = "crop=0.5,flip=0.5,brightness=0.2,contrast=0.2,saturation=0.2" (sgg_amd/augment.py): random crop / mirror / colour
+        # jitter of the TRAINING batches, drawn and applied inside the loader's input kernel (csrc/augment.hip); validation and every
+        # evaluation mode read the plain pixels.  None = not given: off for a fresh run, the checkpoint's for a resumed one; a given
+        # spec that contradicts the checkpoint is an error (_loadModel).
+        self._augment_flag = None if augment is None else AugmentSpec.parse(augment)
+        if self._augment_flag is not None and synthetic is not None:
+            raise ValueError("augment works on decoded source pixels: synthetic batches have none (drop --augment or --synthetic)")
+        self.augment = self._augment_flag
         self.shuffle_buffer = bool(shuffle_buffer)      # tf.data shuffle(buffer_size = 10 * batch) on the repeated stream (train.py:176-179)
         self.checkpoints_dir, self.summaries_dir = checkpoints_dir, summaries_dir
         self.rank, self.world, local = dpmod.init_from_env()
@@ -454,7 +463,15 @@ class SceneGraphGAN(object):
         host-to-device copy runs on its own stream while the previous batch trains.  start / stop count (micro-)batches."""
         files, labs = self.dataset["train"]
         return PrefetchLoader(files, labs, self.BATCH_SIZE, lambda it: self._batch_indices(it, "loader"), self.image_means.numpy(),
-                              self.image_stds.numpy(), self.device, stop, start=start, workers=workers, processes=workers > 2)
+                              self.image_stds.numpy(), self.device, stop, start=start, workers=workers, processes=workers > 2,
+                              **self._augment_kw())
+
+    def _augment_kw(self):
+        """The loader's augmentation arguments - nothing for a run without --augment.  The key is --seed alone: every data-parallel
+        layout of a global batch draws the same parameters for the same stream position."""
+        if self.augment is None:
+            return {}
+        return {"augment": self.augment, "seed": self.seed, "rank": self.rank, "world": self.world, "swap": flip_swap_table(self.vocab)}
 
     ############################################################
     ## Saving
@@ -480,6 +497,8 @@ class SceneGraphGAN(object):
                 ck["generator_output"] = dict({"mode": self.relax_mode, "tau": list(self.relax_tau)}, **self._hard_key())
                 if self.score:              # (only a run with the score-function update writes the key)
                     ck["generator_output"]["gradient"] = dict(self.score)
+            if self.augment is not None:    # (only a run that augments writes the key)
+                ck["augment"] = self.augment.as_dict()
             if self.step.D.has_guard or self.step.G.has_guard:      # (only a guarded run writes the key: the clipped / skipped counts)
                 ck["guard"] = {n: net.guard_state() for n, net in (("D", self.step.D), ("G", self.step.G)) if net.has_guard}
             if self.step.G.has_average:     # (only a run that averages writes these keys: without it the checkpoint is what it was)
@@ -517,6 +536,11 @@ class SceneGraphGAN(object):
         if self.relax_hard and not saved_relax.get("hard"):
             raise ValueError("--relax_hard contradicts the checkpoint, which was trained %s"
                              % ("on the raw logits" if saved_mode == "logits" else "with soft %s rows" % saved_mode))
+        saved_augment = AugmentSpec.parse(ck["augment"]) if ck.get("augment") else None
+        if self._augment_flag is not None and self._augment_flag != saved_augment:
+            raise ValueError("--augment %s contradicts the checkpoint, which was trained %s"
+                             % (self._augment_flag, "with %s" % saved_augment if saved_augment is not None else "without augmentation"))
+        self.augment = saved_augment
         self.relax_mode, self.relax_tau, self.relax_hard = saved_mode, saved_tau, bool(saved_relax.get("hard"))
         self.score = dict(saved_score) if saved_score else None
         self.g.load_state_dict(ck["G"])
@@ -653,6 +677,8 @@ class SceneGraphGAN(object):
         vgen = torch.Generator().manual_seed(self.seed + 70007 + self.rank)
         ngen = None                 # noise of the held-out likelihood (validation_nll): seed + 90009 + rank, made at its first use
         log = open(os.path.join(self.summaries_dir, "losses.jsonl"), "a") if self.rank == 0 else None
+        if log is not None and self.augment is not None:        # once per run (a resumed run writes it again, with its start)
+            log.write(json.dumps({"itr": self.itr, "augment": self.augment.as_dict()}) + "\n"); log.flush()
         B, t0, itr0, N = self.BATCH_SIZE, time.time(), self.itr, self.ACCUMULATE
         loader = self._prefetcher(self.itr * N, n_it * N) if self.dataset is not None else None
         stopper, self.stopped_early, self.val_history = ValidationEarlyStop(patience), False, []
@@ -1681,6 +1707,13 @@ def build_parser():
                              "generator maximises (default 0)")
     parser.add_argument("--seed", default=0, type=int,
                         help="the run's seed: the example stream, the noise streams and the Gumbel noise's key derive from it (default 0)")
+    parser.add_argument("--augment", default=None, metavar="SPEC",
+                        help="training-time augmentation of the real-data batches, drawn and applied on the device inside the input "
+                             "kernel: crop=LO (smallest side fraction of a random crop box, (0, 1]), flip=P (mirror with probability P; "
+                             "left / right words of the triple are exchanged), brightness=A, contrast=A, saturation=A (factor in "
+                             "[1 - A, 1 + A], A in [0, 1)), comma-separated, e.g. crop=0.5,flip=0.5,brightness=0.2,contrast=0.2,"
+                             "saturation=0.2.  Validation and evaluation never augment.  Stored in the checkpoint: --resume continues "
+                             "with it, a contradicting flag is an error.  Not with --synthetic (default: off)")
     parser.add_argument("--relax_tau", default=None, metavar="T | T0,T1,N",
                         help="the relaxation's temperature: a constant T, or the schedule tau(it) = T0 (T1 / T0)^(min(it, N) / N) "
                              "(default 1)")
@@ -1744,6 +1777,13 @@ def parse_args(argv=None):
         parser.error("--" + str(e))
     if args.generator_gradient == "score":
         args.generator_output, args.relax_hard = "gumbel", True
+    if args.augment is not None:
+        if args.synthetic:
+            parser.error("--augment works on decoded source pixels: not together with --synthetic")
+        try:
+            AugmentSpec.parse(args.augment)
+        except ValueError as e:
+            parser.error("--" + str(e))
     if args.relax_tau is not None:
         try:
             args.relax_tau = parse_relax_tau(args.relax_tau)
@@ -1772,7 +1812,7 @@ if __name__ == "__main__":
                         validate_nll=params["validate_nll"], generator_output=params["generator_output"],
                         relax_tau=params["relax_tau"], relax_hard=params["relax_hard"], seed=params["seed"],
                         generator_gradient=params["generator_gradient"], score_baseline=params["score_baseline"],
-                        entropy_weight=params["entropy_weight"], score_samples=params["score_samples"])
+                        entropy_weight=params["entropy_weight"], score_samples=params["score_samples"], augment=params["augment"])
     if params["retrieve_out"]:
         if not gan.load_checkpoint():
             print("--retrieve_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
