@@ -14,12 +14,12 @@
 //   * the filter (864 floats, HWIO) is wave-uniform: scalar loads.
 // Fixed summation order (channel quad, kw, kh, channel in program order; no atomics): two calls are bit-equal.
 //
-// LNB: dy is not read - it is COMPUTED while staging, from the operands of the LayerNorm backward of conv1_1's output, with the
-// arithmetic of ln_bwd_apply_kernel (csrc/layernorm.hip) exactly as conv_c3_wgrad_kernel<true> (csrc/conv_wgrad.hip) does:
+// LNB: dy is not read - it is COMPUTED while staging, from the operands of the LayerNorm backward of conv1_1's output, by the
+// function ln_bwd_apply_kernel (csrc/layernorm.hip) and conv_c3_wgrad_kernel<true> (csrc/conv_wgrad.hip) call (ln_math.h: ln_bwd_dy):
 //   dy = rstd * (da * ELU'(n) * gamma - m1 - xhat * m2),  xhat = (y - mean) * rstd,  n = xhat * gamma + beta
 // with m1, m2 from sgg_layernorm_hwc_elu_bwd_sums.  One read of y and da replaces the apply pass (read y, da; write dy) and the
 // plain kernel's read of dy.
-#include "sgg_common.h"
+#include "ln_math.h"
 
 namespace {
 
@@ -87,12 +87,7 @@ __global__ __launch_bounds__(256, 2) void conv_c3_dgrad_kernel(const float* __re
     if constexpr (LNB) {
       const int yy = y0 - 1 + r, xx = x0 - 1 + c;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float xh = (v[k][i] - mean) * rstd;
-        const float n = xh * gm[i] + bt[i];
-        const float dn = v2[k][i] * (n > 0.f ? 1.f : __expf(n));
-        o[i] = rstd * (dn * gm[i] - m1 - xh * m2);
-      }
+      for (int i = 0; i < 4; ++i) o[i] = ln_bwd_dy(v[k][i], v2[k][i], mean, rstd, gm[i], bt[i], m1, m2);
       if (!((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)) o = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     sdy[qs][r][c] = o;

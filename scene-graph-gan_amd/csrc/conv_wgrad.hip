@@ -9,6 +9,7 @@
 // slabs in a fixed order (deterministic, no atomics).
 #include "mma_f32.h"
 #include "conv_halo.h"
+#include "ln_math.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -492,8 +493,8 @@ __device__ __forceinline__ void c3w_lds_barrier() {
 
 // LNB (round 5): dy is not read - it is COMPUTED here, from the operands of the LayerNorm backward of conv1_1's output (the
 // pre-LayerNorm y, the gradient da of the activation, gamma, beta, the per-sample (mean, rstd) and the two per-sample means m1 =
-// mean(dxhat), m2 = mean(dxhat * xhat) of sgg_layernorm_hwc_elu_bwd_sums), with the arithmetic of ln_bwd_apply_kernel
-// (csrc/layernorm.hip):  dy = rstd * (da * ELU'(n) * gamma - m1 - xhat * m2),  xhat = (y - mean) * rstd,  n = xhat * gamma + beta.
+// mean(dxhat), m2 = mean(dxhat * xhat) of sgg_layernorm_hwc_elu_bwd_sums), by the function ln_bwd_apply_kernel (csrc/layernorm.hip)
+// calls (ln_math.h: ln_bwd_dy):  dy = rstd * (da * ELU'(n) * gamma - m1 - xhat * m2),  xhat = (y - mean) * rstd,  n = xhat * gamma + beta.
 // in the training step conv1_1's filter gradient is the ONLY consumer of that dy (the step takes no image gradient - an image
 // gradient computes it the same way in conv_c3_dgrad_kernel<true>, csrc/conv_dgrad_c3.hip - and the bias gradient comes from the
 // LayerNorm reductions), so the LayerNorm backward's apply pass - 411 MB read twice and 411 MB written at batch 64, on the tail of
@@ -599,15 +600,12 @@ __global__ __launch_bounds__(256, LNB ? 2 : 3) void conv_c3_wgrad_kernel(const f
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         if constexpr (LNB) {
-          // dy of this lane's pixel (row 2 wave + m, column 8 q + 4 h + (i & 3)), channels 4 (i >> 2) .. + 3: ln_bwd_apply_kernel's arithmetic
+          // dy of this lane's pixel (row 2 wave + m, column 8 q + 4 h + (i & 3)), channels 4 (i >> 2) .. + 3 (ln_math.h)
           const float mean = cstn[0], rstd = cstn[1], m1 = cstn[2], m2 = cstn[3];
           const bool ok = (okn >> (4 * m + q)) & 1;
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
-            const float xh = (yvn[m][4 * q + c] - mean) * rstd;
-            const float n = xh * gmv[c] + btv[c];
-            const float dn = dvn[m][4 * q + c] * (n > 0.f ? 1.f : __expf(n));
-            const float o = rstd * (dn * gmv[c] - m1 - xh * m2);
+            const float o = ln_bwd_dy(yvn[m][4 * q + c], dvn[m][4 * q + c], mean, rstd, gmv[c], btv[c], m1, m2);
             dv[m][4 * q + c] = ok ? o : 0.f;          // (outside the image: no pixel, no contribution)
           }
         } else {

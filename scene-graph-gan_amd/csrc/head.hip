@@ -19,13 +19,6 @@
 #define HEAD_LN_EPS 1e-12f
 #define NUM_UNITS 512
 
-__device__ __forceinline__ float block_max_256(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
 __device__ __forceinline__ Dual block_sum_256(Dual v, float* red) {
   const float r = block_sum_256(v.r, red);
   const float d = block_sum_256(v.d, red);

@@ -23,6 +23,7 @@
 // A bound that is 2^k too large costs k of the 16 binades between the tensor's maximum and the point where the residual piece turns
 // subnormal (split16.h: an element 2^-d below the maximum keeps min(23, 39 - d) bits): nothing at the sizes that occur (k <= 4).
 #include "split16.h"
+#include "ln_math.h"
 
 #define LN_EPS 1e-12f
 constexpr int SGG_LN_WGS = 1536;      // workgroups per launch of the streaming LayerNorm kernels (six per CU)
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(256) void ln_stats_partial_kernel(const float* __re
     m2_run += m2_c + delta * delta * (n_run * n_c / n_new);
     n_run = n_new;
   }
-  // (dev_run holds a per-wave maximum: combine the four waves)
+  // (dev_run holds a per-wave maximum already: the four waves are combined without block_max_256's wave reduction)
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dev_run;
   __syncthreads();
@@ -148,50 +149,98 @@ __device__ __forceinline__ void ln_merge(const float* __restrict__ part, int G, 
   rstd = rsqrtf(var + LN_EPS);
 }
 
-__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
+// ---- the two output formats of the apply kernels ---------------------------------------------------------------------------
+// Pre-split ("S16") store.  Lane t holds 4 consecutive channels (perfectly coalesced 16-byte loads): they make 8 bytes of leading and
+// 8 bytes of residual pieces; lanes t and t ^ 1 hold the two halves of an 8-channel item, so they swap one half each through a DPP
+// quad permute (no LDS): the even lane then stores the item's 16 bytes of LEADING pieces, the odd lane its 16 bytes of RESIDUAL
+// pieces - one 16-byte store per lane, and the eight lanes of a 32-channel group write its whole 128-byte line with one
+// instruction.  EVERY lane of the wave calls this; `in`: the lane's channels exist (e < N; N % 8 == 0, so a pair is in or out
+// together).
+__device__ __forceinline__ unsigned s16_swap1(unsigned v) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]: lane ^ 1
+}
+__device__ __forceinline__ void s16_store4(float* tensor_b, long long e, const f32x4& o, float scale, bool in) {
+  unsigned hi0, lo0, hi1, lo1;
+  f16_split2(o[0] * scale, o[1] * scale, hi0, lo0);
+  f16_split2(o[2] * scale, o[3] * scale, hi1, lo1);
+  const bool odd = (threadIdx.x & 1) != 0;
+  const unsigned r0 = s16_swap1(odd ? hi0 : lo0), r1 = s16_swap1(odd ? hi1 : lo1);
+  const u32x4 v = odd ? u32x4{r0, r1, lo0, lo1} : u32x4{hi0, hi1, r0, r1};
+  const long long eb = e * 4;
+  unsigned char* g = reinterpret_cast<unsigned char*>(tensor_b) + (eb & ~127LL) + ((eb & 127LL) >> 5) * 16 + (odd ? 64 : 0);
+  if (in) *reinterpret_cast<u32x4*>(g) = v;
+}
 
-template <bool MASK>
-__global__ __launch_bounds__(256) void ln_apply_elu_kernel(const float* __restrict__ y, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, const float* __restrict__ part,
-                                                           float* __restrict__ a, float* __restrict__ stats, long long N,
-                                                           int C, int G, int cpg, float* __restrict__ amax_out, LnMask mk,
-                                                           float nvalid) {
-  __shared__ float red[4];
-  const int b = blockIdx.y, g = blockIdx.x;
-  float mean, rstd;
+// What an apply kernel does with the four values of a lane: f32 as they are, with the running max|x| that the workgroup publishes
+// at its end; or pre-split under a scale fixed by a bound of max|x| that is known before the first store.
+struct LnOutF32 {
+  static constexpr bool presplit = false;
   float amax = 0.f;
-  ln_merge(part + (size_t)b * G * SGG_TS, G, MASK ? nvalid : (float)N, red, mean, rstd);
-  if (g == 0 && threadIdx.x == 0) {
-    stats[b * 2 + 0] = mean;
-    stats[b * 2 + 1] = rstd;
+  __device__ __forceinline__ void store4(float* tensor_b, long long e, const f32x4& o, bool in) {
+    amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
+    if (in) ln_st(tensor_b + e, o);
   }
-  const float* yb = y + (size_t)b * N;
-  float* ab = a + (size_t)b * N;
-  const int ch = (threadIdx.x * 4) % C;   // constant across chunks: LN_CHUNK and 1024 are multiples of C
-  const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + ch);
-  const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + ch);
-  const f32x4 inv = gm * rstd;
-  const f32x4 shift = bt - inv * mean;
+  __device__ __forceinline__ void finish(float* amax_out, float* red) {
+    if (amax_out) block_publish_amax(amax_out, amax, red);      // (the consumer convolution's f16 scaling)
+  }
+};
+struct LnOutS16 {
+  static constexpr bool presplit = true;
+  float scale;
+  __device__ __forceinline__ void set_bound(float bound) { scale = ldexpf(1.f, scale_exp_from_amax(bound)); }
+  __device__ __forceinline__ void store4(float* tensor_b, long long e, const f32x4& o, bool in) { s16_store4(tensor_b, e, o, scale, in); }
+  __device__ __forceinline__ void finish(float*, float*) {}
+};
+
+// The chunk walk of both apply kernels: workgroup g of a sample takes cpg chunks; f(e) loads and computes the four values at element
+// e of the sample, and is called for valid elements only (elements outside the valid region are not loaded).  Every lane reaches
+// the store for every j, with zeros where it has no valid element: the pre-split store exchanges halves between lanes.
+template <bool MASK, class Out, class F>
+__device__ __forceinline__ void ln_walk(float* tensor_b, long long N, int cpg, const LnMask& mk, Out& out, F f) {
   for (int c = 0; c < cpg; ++c) {
-    const long long base = ((long long)g * cpg + c) * LN_CHUNK;
+    const long long base = ((long long)blockIdx.x * cpg + c) * LN_CHUNK;
     if (base >= N) break;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const long long e = base + (threadIdx.x + 256 * j) * 4;
-      if (e < N) {
-        if (MASK && !ln_valid(mk, e)) {
-          ln_st(ab + e, f32x4{0.f, 0.f, 0.f, 0.f});
-          continue;
-        }
-        const f32x4 v = ln_ld(yb + e);
-        f32x4 o = v * inv + shift;
-        o[0] = elu1(o[0]); o[1] = elu1(o[1]); o[2] = elu1(o[2]); o[3] = elu1(o[3]);
-        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
-        ln_st(ab + e, o);
-      }
+      const bool in = e < N;
+      f32x4 o = {0.f, 0.f, 0.f, 0.f};
+      if (in && (!MASK || ln_valid(mk, e))) o = f(e);
+      out.store4(tensor_b, e, o, in);
     }
   }
-  if (amax_out) block_publish_amax(amax_out, amax, red);   // max |a| (the consumer convolution's f16 scaling)
+}
+
+// a = ELU(LN(y)).  LnOutF32: every workgroup merges the G partials in `part` into (mean, rstd), workgroup 0 of a sample writes them
+// to stats [B][2], and max|a| is published into *amax when given.  LnOutS16: stats and the bound of max|a| in *amax are final
+// (ln_finalize_kernel ran before); part, G and nvalid, the last three arguments, are not used.
+template <bool MASK, class Out>
+__global__ __launch_bounds__(256) void ln_apply_elu_kernel(const float* __restrict__ y, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, float* __restrict__ stats,
+                                                           float* __restrict__ a, long long N, int C, int cpg,
+                                                           float* __restrict__ amax, LnMask mk, const float* __restrict__ part, int G,
+                                                           float nvalid) {
+  __shared__ float red[4];
+  const int b = blockIdx.y;
+  Out out;
+  float mean, rstd;
+  if constexpr (Out::presplit) {
+    mean = stats[b * 2 + 0];
+    rstd = stats[b * 2 + 1];
+    out.set_bound(*amax);
+  } else {
+    ln_merge(part + (size_t)b * G * SGG_TS, G, MASK ? nvalid : (float)N, red, mean, rstd);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      stats[b * 2 + 0] = mean;
+      stats[b * 2 + 1] = rstd;
+    }
+  }
+  const float* yb = y + (size_t)b * N;
+  const int ch = (threadIdx.x * 4) % C;   // constant across chunks: LN_CHUNK and 1024 are multiples of C
+  const f32x4 inv = *reinterpret_cast<const f32x4*>(gamma + ch) * rstd;
+  const f32x4 shift = *reinterpret_cast<const f32x4*>(beta + ch) - inv * mean;
+  ln_walk<MASK>(a + (size_t)b * N, N, cpg, mk, out, [&](long long e) { return ln_elu(ln_ld(yb + e), inv, shift); });
+  out.finish(amax, red);
 }
 
 // Statistics only (no apply pass): stats[b] = (mean, rstd) merged from the partials, and an UPPER BOUND of max |ELU(LN(y))|
@@ -212,19 +261,11 @@ __global__ __launch_bounds__(256) void ln_finalize_kernel(const float* __restric
     gb = fmaxf(gb, fabsf(gamma[c]));
     bb = fmaxf(bb, fabsf(beta[c]));
   }
-  dev = wave_max(dev); gb = wave_max(gb); bb = wave_max(bb);
-  __shared__ float mx[3][4];
-  if ((threadIdx.x & 63) == 0) { mx[0][threadIdx.x >> 6] = dev; mx[1][threadIdx.x >> 6] = gb; mx[2][threadIdx.x >> 6] = bb; }
-  __syncthreads();
+  dev = block_max_256(dev, red); gb = block_max_256(gb, red); bb = block_max_256(bb, red);
   if (threadIdx.x == 0) {
     stats[b * 2 + 0] = mean;
     stats[b * 2 + 1] = rstd;
-    if (amax_out) {
-      const float d = fmaxf(fmaxf(mx[0][0], mx[0][1]), fmaxf(mx[0][2], mx[0][3]));
-      const float g = fmaxf(fmaxf(mx[1][0], mx[1][1]), fmaxf(mx[1][2], mx[1][3]));
-      const float bt = fmaxf(fmaxf(mx[2][0], mx[2][1]), fmaxf(mx[2][2], mx[2][3]));
-      atomic_amax(amax_out, g * d * rstd + bt);
-    }
+    if (amax_out) atomic_amax(amax_out, gb * dev * rstd + bb);
   }
 }
 
@@ -258,11 +299,13 @@ __global__ __launch_bounds__(256) void ln_bwd_partial_kernel(const float* __rest
       if (e < N && (!MASK || ln_valid(mk, e))) {
         const f32x4 v = ln_ld(yb + e);
         const f32x4 d = ln_ld(db + e);
-        const f32x4 xh = (v - mean) * rstd;
-        const f32x4 n = xh * gm + bt;
-        f32x4 dn;
+        f32x4 xh, dn;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) dn[q] = d[q] * (n[q] > 0.f ? 1.f : __expf(n[q]));
+        for (int q = 0; q < 4; ++q) {
+          const LnBwdTerms t = ln_bwd_terms(v[q], d[q], mean, rstd, gm[q], bt[q]);
+          xh[q] = t.xhat;
+          dn[q] = t.dn;
+        }
         const f32x4 dxh = dn * gm;
         sA += dn; sB += dn * xh; sX += xh;
         s1 += (dxh[0] + dxh[1]) + (dxh[2] + dxh[3]);
@@ -275,21 +318,17 @@ __global__ __launch_bounds__(256) void ln_bwd_partial_kernel(const float* __rest
   }
   const float S1 = block_sum_256(s1, red);
   const float S2 = block_sum_256(s2, red);
-  mxd = wave_max(mxd);
-  mxx = wave_max(mxx);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { chs[threadIdx.x >> 6] = mxd; chs[4 + (threadIdx.x >> 6)] = mxx; }
-  __syncthreads();
+  mxd = block_max_256(mxd, red);
+  mxx = block_max_256(mxx, red);
   if (threadIdx.x == 0) {
     sspart[((size_t)b * G + g) * 2 + 0] = S1;
     sspart[((size_t)b * G + g) * 2 + 1] = S2;
     if (pq) {      // (pre-split dy: the two maxima its bound is made of)
-      atomic_amax(pq, rstd * fmaxf(fmaxf(chs[0], chs[1]), fmaxf(chs[2], chs[3])));
-      atomic_amax(pq + 1, fmaxf(fmaxf(chs[4], chs[5]), fmaxf(chs[6], chs[7])));
+      atomic_amax(pq, rstd * mxd);
+      atomic_amax(pq + 1, mxx);
     }
   }
   // per-channel reduce across threads with equal (tid*4) % C
-  __syncthreads();
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     chs[threadIdx.x * 12 + q] = sA[q];
@@ -397,163 +436,53 @@ __global__ __launch_bounds__(1024) void ln_bwd_finalize_batch_kernel(LnfArgs a) 
   ln_bwd_finalize_body(sspart, chpart, L.gamma, L.stats, L.dgamma, L.dbeta, L.dbias, L.B, L.C, L.G, L.HW, blockIdx.x - a.first[l], sm);
 }
 
-template <bool MASK>
+// The two per-sample means of the backward, (mean dxhat, mean dxhat * xhat), from the partial sums of ln_bwd_partial_kernel; n:
+// elements of the sample.  Every thread returns the same values.
+__device__ __forceinline__ void ln_bwd_means(const float* __restrict__ sspart, int b, int G, float n, float* red, float& m1, float& m2) {
+  float a1 = 0.f, a2 = 0.f;
+  for (int i = threadIdx.x; i < G; i += 256) {
+    a1 += sspart[((size_t)b * G + i) * 2 + 0];
+    a2 += sspart[((size_t)b * G + i) * 2 + 1];
+  }
+  m1 = block_sum_256(a1, red) / n;
+  m2 = block_sum_256(a2, red) / n;
+}
+
+// dy of the LayerNorm backward.  LnOutF32: max|dy| is published into *amax_out when given.  LnOutS16: pq[0] = max over all
+// workgroups of ln_bwd_partial of rstd * max|dxhat|, pq[1] = their max|xhat| (atomic maxima, the words zeroed by the caller): bound =
+// pq[0] * (2 + pq[1]) >= max|dy| (file header; the two maxima may come from different samples: only looser).  Workgroup (0, 0)
+// publishes the bound in *amax_out for the consumers.
+template <bool MASK, class Out>
 __global__ __launch_bounds__(256) void ln_bwd_apply_kernel(const float* __restrict__ y, const float* __restrict__ da,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const float* __restrict__ stats, const float* __restrict__ sspart,
-                                                           float* __restrict__ dy, long long N, int C, int G, int cpg,
-                                                           float* __restrict__ amax_out, LnMask mk, float nvalid) {
+                                                           const float* __restrict__ pq, float* __restrict__ dy, long long N, int C,
+                                                           int G, int cpg, float* __restrict__ amax_out, LnMask mk, float nvalid) {
   __shared__ float red[4];
-  const int b = blockIdx.y, g = blockIdx.x;
-  const float mean = stats[b * 2 + 0], rstd = stats[b * 2 + 1];
-  float amax = 0.f;
-  float a1 = 0.f, a2 = 0.f;
-  for (int i = threadIdx.x; i < G; i += 256) {
-    a1 += sspart[((size_t)b * G + i) * 2 + 0];
-    a2 += sspart[((size_t)b * G + i) * 2 + 1];
+  const int b = blockIdx.y;
+  Out out;
+  if constexpr (Out::presplit) {
+    const float bound = 1.0001f * pq[0] * (2.f + pq[1]);
+    if (amax_out && b == 0 && blockIdx.x == 0 && threadIdx.x == 0) *amax_out = bound;
+    out.set_bound(bound);
   }
-  const float m1 = block_sum_256(a1, red) / (MASK ? nvalid : (float)N);
-  const float m2 = block_sum_256(a2, red) / (MASK ? nvalid : (float)N);
+  const float mean = stats[b * 2 + 0], rstd = stats[b * 2 + 1];
+  float m1, m2;
+  ln_bwd_means(sspart, b, G, MASK ? nvalid : (float)N, red, m1, m2);
   const float* yb = y + (size_t)b * N;
   const float* db = da + (size_t)b * N;
-  float* ob = dy + (size_t)b * N;
   const int ch = (threadIdx.x * 4) % C;
   const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + ch);
   const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + ch);
-  for (int c = 0; c < cpg; ++c) {
-    const long long base = ((long long)g * cpg + c) * LN_CHUNK;
-    if (base >= N) break;
+  ln_walk<MASK>(dy + (size_t)b * N, N, cpg, mk, out, [&](long long e) {
+    const f32x4 v = ln_ld(yb + e);
+    const f32x4 d = ln_ld(db + e);
+    f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long e = base + (threadIdx.x + 256 * j) * 4;
-      if (e < N) {
-        if (MASK && !ln_valid(mk, e)) {
-          ln_st(ob + e, f32x4{0.f, 0.f, 0.f, 0.f});
-          continue;
-        }
-        const f32x4 v = ln_ld(yb + e);
-        const f32x4 d = ln_ld(db + e);
-        const f32x4 xh = (v - mean) * rstd;
-        const f32x4 n = xh * gm + bt;
-        f32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float dn = d[q] * (n[q] > 0.f ? 1.f : __expf(n[q]));
-          o[q] = rstd * (dn * gm[q] - m1 - xh[q] * m2);
-          amax = fmaxf(amax, fabsf(o[q]));
-        }
-        ln_st(ob + e, o);
-      }
-    }
-  }
-  if (amax_out) block_publish_amax(amax_out, amax, red);
-}
-
-// ---- pre-split ("S16") outputs -------------------------------------------------------------------------------------------
-// Same thread <-> element map as the f32 kernels (lane t holds 4 consecutive channels: perfectly coalesced 16-byte loads).  A lane's
-// four values make 8 bytes of leading and 8 bytes of residual pieces; lanes t and t ^ 1 hold the two halves of an 8-channel item, so
-// they swap one half each through a DPP quad permute (no LDS): the even lane then stores the item's 16 bytes of LEADING pieces, the odd
-// lane its 16 bytes of RESIDUAL pieces - one 16-byte store per lane, and the eight lanes of a 32-channel group write its whole
-// 128-byte line with one instruction.  EVERY lane of the wave calls this; `in`: the lane's channels exist (e < N; N % 8 == 0, so a
-// pair is in or out together).
-__device__ __forceinline__ unsigned s16_swap1(unsigned v) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]: lane ^ 1
-}
-__device__ __forceinline__ void s16_store4(float* tensor_b, long long e, const f32x4& o, float scale, bool in) {
-  unsigned hi0, lo0, hi1, lo1;
-  f16_split2(o[0] * scale, o[1] * scale, hi0, lo0);
-  f16_split2(o[2] * scale, o[3] * scale, hi1, lo1);
-  const bool odd = (threadIdx.x & 1) != 0;
-  const unsigned r0 = s16_swap1(odd ? hi0 : lo0), r1 = s16_swap1(odd ? hi1 : lo1);
-  const u32x4 v = odd ? u32x4{r0, r1, lo0, lo1} : u32x4{hi0, hi1, r0, r1};
-  const long long eb = e * 4;
-  unsigned char* g = reinterpret_cast<unsigned char*>(tensor_b) + (eb & ~127LL) + ((eb & 127LL) >> 5) * 16 + (odd ? 64 : 0);
-  if (in) *reinterpret_cast<u32x4*>(g) = v;
-}
-
-// a = ELU(LN(y)) written pre-split; stats [B][2] and the bound in *amax are final (ln_finalize_kernel ran before)
-template <bool MASK>
-__global__ __launch_bounds__(256) void ln_apply_elu_s16_kernel(const float* __restrict__ y, const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, const float* __restrict__ stats,
-                                                               float* __restrict__ a, long long N, int C, int cpg,
-                                                               const float* __restrict__ amax, LnMask mk) {
-  const int b = blockIdx.y, g = blockIdx.x;
-  const float mean = stats[b * 2 + 0], rstd = stats[b * 2 + 1];
-  const float scale = ldexpf(1.f, scale_exp_from_amax(*amax));
-  const float* yb = y + (size_t)b * N;
-  float* ab = a + (size_t)b * N;
-  const int ch = (threadIdx.x * 4) % C;   // constant across chunks: LN_CHUNK and 1024 are multiples of C
-  const f32x4 inv = *reinterpret_cast<const f32x4*>(gamma + ch) * rstd;
-  const f32x4 shift = *reinterpret_cast<const f32x4*>(beta + ch) - inv * mean;
-  for (int c = 0; c < cpg; ++c) {
-    const long long base = ((long long)g * cpg + c) * LN_CHUNK;
-    if (base >= N) break;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long e = base + (threadIdx.x + 256 * j) * 4;
-      const bool in = e < N;
-      f32x4 o = {0.f, 0.f, 0.f, 0.f};
-      if (in && (!MASK || ln_valid(mk, e))) {
-        const f32x4 v = ln_ld(yb + e);
-        o = v * inv + shift;
-        o[0] = elu1(o[0]); o[1] = elu1(o[1]); o[2] = elu1(o[2]); o[3] = elu1(o[3]);
-      }
-      s16_store4(ab, e, o, scale, in);
-    }
-  }
-}
-
-// dy of the LayerNorm backward written pre-split.  pq[0] = max over all workgroups of ln_bwd_partial of rstd * max|dxhat|, pq[1] =
-// their max|xhat| (atomic maxima, the words zeroed by the caller): bound = pq[0] * (2 + pq[1]) >= max|dy| (file header; the two
-// maxima may come from different samples: only looser).  Workgroup (0, 0) publishes the bound in *amax_out for the consumers.
-template <bool MASK>
-__global__ __launch_bounds__(256) void ln_bwd_apply_s16_kernel(const float* __restrict__ y, const float* __restrict__ da,
-                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                               const float* __restrict__ stats, const float* __restrict__ sspart,
-                                                               const float* __restrict__ pq, float* __restrict__ dy, long long N,
-                                                               int C, int G, int cpg, float* __restrict__ amax_out, LnMask mk,
-                                                               float nvalid) {
-  __shared__ float red[4];
-  const int b = blockIdx.y, g = blockIdx.x;
-  const float bound = 1.0001f * pq[0] * (2.f + pq[1]);
-  if (amax_out && b == 0 && g == 0 && threadIdx.x == 0) *amax_out = bound;
-  const float scale = ldexpf(1.f, scale_exp_from_amax(bound));
-  const float mean = stats[b * 2 + 0], rstd = stats[b * 2 + 1];
-  float a1 = 0.f, a2 = 0.f;
-  for (int i = threadIdx.x; i < G; i += 256) {
-    a1 += sspart[((size_t)b * G + i) * 2 + 0];
-    a2 += sspart[((size_t)b * G + i) * 2 + 1];
-  }
-  const float m1 = block_sum_256(a1, red) / (MASK ? nvalid : (float)N);
-  const float m2 = block_sum_256(a2, red) / (MASK ? nvalid : (float)N);
-  const float* yb = y + (size_t)b * N;
-  const float* db = da + (size_t)b * N;
-  float* ob = dy + (size_t)b * N;
-  const int ch = (threadIdx.x * 4) % C;
-  const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + ch);
-  const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + ch);
-  for (int c = 0; c < cpg; ++c) {
-    const long long base = ((long long)g * cpg + c) * LN_CHUNK;
-    if (base >= N) break;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long e = base + (threadIdx.x + 256 * j) * 4;
-      const bool in = e < N;
-      f32x4 o = {0.f, 0.f, 0.f, 0.f};
-      if (in && (!MASK || ln_valid(mk, e))) {
-        const f32x4 v = ln_ld(yb + e);
-        const f32x4 d = ln_ld(db + e);
-        const f32x4 xh = (v - mean) * rstd;
-        const f32x4 n = xh * gm + bt;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float dn = d[q] * (n[q] > 0.f ? 1.f : __expf(n[q]));
-          o[q] = rstd * (dn * gm[q] - m1 - xh[q] * m2);
-        }
-      }
-      s16_store4(ob, e, o, scale, in);
-    }
-  }
+    for (int q = 0; q < 4; ++q) o[q] = ln_bwd_dy(v[q], d[q], mean, rstd, gm[q], bt[q], m1, m2);
+    return o;
+  });
+  out.finish(amax_out, red);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------
@@ -586,6 +515,12 @@ static int ln_mask(const char* name, int HW, int C, int W, int y0, int x0, int H
   return SGG_OK;
 }
 
+// A launch of a streaming kernel on its (G, B) grid: the instantiation for whole planes (W == 0) or the one for a valid region.
+template <class K, class... Args>
+static void ln_launch(K whole, K masked, int W, const LnGeom& g, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL(W == 0 ? whole : masked, dim3(g.G, g.B), dim3(256), 0, st, args...);
+}
+
 // tile_stats / n_tile_stats (optional): [B][n_tile_stats][4] (count, mean, M2, max |y - mean|) partials of y already produced by the
 // convolution's epilogue (sgg_conv2d_nhwc_fwd); the statistics pass over y is then skipped.  (Not with a valid region: the
 // convolution's partials cover the whole canvas.)
@@ -602,44 +537,23 @@ extern "C" int sgg_layernorm_hwc_elu_fwd(const float* y, const float* gamma, con
   if ((rc = ln_mask("sgg_layernorm_hwc_elu_fwd", HW, C, W, y0, x0, Hv, Wv, mk, nvalid))) return rc;
   const LnGeom g = ln_geom(B, HW, C);
   hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)ws;
-  if (out_format == 1) {
-    // statistics (from the convolution's partials, or a pass of our own) -> stats + the bound of max|a| in *amax_out -> apply
-    const float* parts = tile_stats;
-    int nparts = n_tile_stats;
-    if (!(tile_stats && n_tile_stats > 0)) {
-      if (W == 0) hipLaunchKernelGGL(ln_stats_partial_kernel<false>, dim3(g.G, B), dim3(256), 0, st, y, part, g.N, g.G, g.cpg, mk);
-      else hipLaunchKernelGGL(ln_stats_partial_kernel<true>, dim3(g.G, B), dim3(256), 0, st, y, part, g.N, g.G, g.cpg, mk);
-      parts = part;
-      nparts = g.G;
-    } else {
-      SGG_CHECK_ARG(W == 0, "sgg_layernorm_hwc_elu_fwd: tile_stats cannot be combined with a valid region");
-    }
-    hipLaunchKernelGGL(ln_finalize_kernel, dim3(B), dim3(256), 0, st, parts, nparts, nvalid, gamma, beta, C, stats, amax_out);
-    if (W == 0)
-      hipLaunchKernelGGL(ln_apply_elu_s16_kernel<false>, dim3(g.G, B), dim3(256), 0, st, y, gamma, beta, (const float*)stats, a, g.N, C,
-                         g.cpg, (const float*)amax_out, mk);
-    else
-      hipLaunchKernelGGL(ln_apply_elu_s16_kernel<true>, dim3(g.G, B), dim3(256), 0, st, y, gamma, beta, (const float*)stats, a, g.N, C,
-                         g.cpg, (const float*)amax_out, mk);
-    SGG_LAUNCH_CHECK("sgg_layernorm_hwc_elu_fwd");
-    return SGG_OK;
-  }
+  // statistics partials: the convolution's, or a pass of our own into the workspace
+  const float* parts = tile_stats;
+  int nparts = n_tile_stats;
   if (tile_stats && n_tile_stats > 0) {
     SGG_CHECK_ARG(W == 0, "sgg_layernorm_hwc_elu_fwd: tile_stats cannot be combined with a valid region");
-    hipLaunchKernelGGL(ln_apply_elu_kernel<false>, dim3(g.G, B), dim3(256), 0, st, y, gamma, beta, tile_stats, a, stats, g.N, C,
-                       n_tile_stats, g.cpg, amax_out, mk, nvalid);
-    SGG_LAUNCH_CHECK("sgg_layernorm_hwc_elu_fwd");
-    return SGG_OK;
-  }
-  if (W == 0) {
-    hipLaunchKernelGGL(ln_stats_partial_kernel<false>, dim3(g.G, B), dim3(256), 0, st, y, part, g.N, g.G, g.cpg, mk);
-    hipLaunchKernelGGL(ln_apply_elu_kernel<false>, dim3(g.G, B), dim3(256), 0, st, y, gamma, beta, (const float*)part, a, stats,
-                       g.N, C, g.G, g.cpg, amax_out, mk, nvalid);
   } else {
-    hipLaunchKernelGGL(ln_stats_partial_kernel<true>, dim3(g.G, B), dim3(256), 0, st, y, part, g.N, g.G, g.cpg, mk);
-    hipLaunchKernelGGL(ln_apply_elu_kernel<true>, dim3(g.G, B), dim3(256), 0, st, y, gamma, beta, (const float*)part, a, stats,
-                       g.N, C, g.G, g.cpg, amax_out, mk, nvalid);
+    ln_launch(ln_stats_partial_kernel<false>, ln_stats_partial_kernel<true>, W, g, st, y, (float*)ws, g.N, g.G, g.cpg, mk);
+    parts = (const float*)ws;
+    nparts = g.G;
+  }
+  if (out_format == 1) {      // stats and the bound of max|a| in *amax_out have to be final before the first store
+    hipLaunchKernelGGL(ln_finalize_kernel, dim3(B), dim3(256), 0, st, parts, nparts, nvalid, gamma, beta, C, stats, amax_out);
+    ln_launch(ln_apply_elu_kernel<false, LnOutS16>, ln_apply_elu_kernel<true, LnOutS16>, W, g, st, y, gamma, beta, stats, a, g.N, C,
+              g.cpg, amax_out, mk, parts, nparts, nvalid);
+  } else {
+    ln_launch(ln_apply_elu_kernel<false, LnOutF32>, ln_apply_elu_kernel<true, LnOutF32>, W, g, st, y, gamma, beta, stats, a, g.N, C,
+              g.cpg, amax_out, mk, parts, nparts, nvalid);
   }
   SGG_LAUNCH_CHECK("sgg_layernorm_hwc_elu_fwd");
   return SGG_OK;
@@ -699,47 +613,28 @@ extern "C" int sgg_layernorm_hwc_elu_bwd(const float* y, const float* da, const 
   float* chpart = sspart + (size_t)B * g.G * 2;
   const size_t sm = (size_t)(2 * B + LNF_BL * 32 * 3) * sizeof(float);
   const int hw_valid = W == 0 ? HW : Hv * Wv;
-  if (W == 0)
-    hipLaunchKernelGGL(ln_bwd_partial_kernel<false>, dim3(g.G, B), dim3(256), 0, st, y, da, gamma, beta, stats, sspart, chpart,
-                       pq, g.N, C, g.G, g.cpg, mk);
-  else
-    hipLaunchKernelGGL(ln_bwd_partial_kernel<true>, dim3(g.G, B), dim3(256), 0, st, y, da, gamma, beta, stats, sspart, chpart,
-                       pq, g.N, C, g.G, g.cpg, mk);
+  ln_launch(ln_bwd_partial_kernel<false>, ln_bwd_partial_kernel<true>, W, g, st, y, da, gamma, beta, stats, sspart, chpart, pq, g.N, C,
+            g.G, g.cpg, mk);
   if (dgamma)      // (NULL: the caller reduces the partials later, several layers at once: sgg_layernorm_hwc_bwd_finalize)
     hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3(sgg_cdiv(C, 32)), dim3(1024), sm, st, (const float*)sspart,
                        (const float*)chpart, gamma, stats, dgamma, dbeta, dbias_prev, B, C, g.G, hw_valid);
-  if (out_format == 1) {
-    if (W == 0)
-      hipLaunchKernelGGL(ln_bwd_apply_s16_kernel<false>, dim3(g.G, B), dim3(256), 0, st, y, da, gamma, beta, stats, (const float*)sspart,
-                         (const float*)pq, dy, g.N, C, g.G, g.cpg, amax_out, mk, nvalid);
-    else
-      hipLaunchKernelGGL(ln_bwd_apply_s16_kernel<true>, dim3(g.G, B), dim3(256), 0, st, y, da, gamma, beta, stats, (const float*)sspart,
-                         (const float*)pq, dy, g.N, C, g.G, g.cpg, amax_out, mk, nvalid);
-    SGG_LAUNCH_CHECK("sgg_layernorm_hwc_elu_bwd");
-    return SGG_OK;
-  }
-  if (W == 0)
-    hipLaunchKernelGGL(ln_bwd_apply_kernel<false>, dim3(g.G, B), dim3(256), 0, st, y, da, gamma, beta, stats,
-                       (const float*)sspart, dy, g.N, C, g.G, g.cpg, amax_out, mk, nvalid);
+  if (out_format == 1)
+    ln_launch(ln_bwd_apply_kernel<false, LnOutS16>, ln_bwd_apply_kernel<true, LnOutS16>, W, g, st, y, da, gamma, beta, stats, sspart, pq,
+              dy, g.N, C, g.G, g.cpg, amax_out, mk, nvalid);
   else
-    hipLaunchKernelGGL(ln_bwd_apply_kernel<true>, dim3(g.G, B), dim3(256), 0, st, y, da, gamma, beta, stats,
-                       (const float*)sspart, dy, g.N, C, g.G, g.cpg, amax_out, mk, nvalid);
+    ln_launch(ln_bwd_apply_kernel<false, LnOutF32>, ln_bwd_apply_kernel<true, LnOutF32>, W, g, st, y, da, gamma, beta, stats, sspart, pq,
+              dy, g.N, C, g.G, g.cpg, amax_out, mk, nvalid);
   SGG_LAUNCH_CHECK("sgg_layernorm_hwc_elu_bwd");
   return SGG_OK;
 }
 
-// The two per-sample means of the backward, as every workgroup of ln_bwd_apply_kernel derives them from the partial sums (the same
-// strided per-thread sums, the same block reduction, the same division: bit-identical values): means[b] = (mean dxhat, mean dxhat * xhat).
+// means[b] = (mean dxhat, mean dxhat * xhat) of every sample, for a consumer that computes dy itself: the values every workgroup of
+// ln_bwd_apply_kernel gets from the same call.
 __global__ __launch_bounds__(256) void ln_bwd_means_kernel(const float* __restrict__ sspart, float* __restrict__ means, int G, float n) {
   __shared__ float red[4];
   const int b = blockIdx.x;
-  float a1 = 0.f, a2 = 0.f;
-  for (int i = threadIdx.x; i < G; i += 256) {
-    a1 += sspart[((size_t)b * G + i) * 2 + 0];
-    a2 += sspart[((size_t)b * G + i) * 2 + 1];
-  }
-  const float m1 = block_sum_256(a1, red) / n;
-  const float m2 = block_sum_256(a2, red) / n;
+  float m1, m2;
+  ln_bwd_means(sspart, b, G, n, red, m1, m2);
   if (threadIdx.x == 0) {
     means[2 * b + 0] = m1;
     means[2 * b + 1] = m2;

@@ -141,6 +141,15 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// block-wide maximum, same contract as block_sum_256
+__device__ __forceinline__ float block_max_256(float v, float* red) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
 // ---- per-tensor power-of-two scaling for the f16x3 convolution mode --------------------------------------
 // amax words hold max|x| of a tensor as float bits (non-negative floats order like unsigned ints -> atomicMax).
 __device__ __forceinline__ void atomic_amax(float* p, float v) {
@@ -152,11 +161,8 @@ __device__ __forceinline__ void atomic_amax(float* p, float v) {
 }
 // block-wide (256 threads) max published once per workgroup; `red` is >= 4 floats of LDS
 __device__ __forceinline__ void block_publish_amax(float* p, float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) atomic_amax(p, fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+  v = block_max_256(v, red);
+  if (threadIdx.x == 0) atomic_amax(p, v);
 }
 // exponent e with |x| * 2^e <= 2^14 for every |x| <= amax (fp16 max is 65504); 0 for an all-zero tensor
 __device__ __forceinline__ int scale_exp_from_amax(float amax) {

@@ -68,6 +68,35 @@ def test_layernorm_outputs_presplit_are_todays_split_bit_for_bit(mode2, shape, r
     assert torch.equal(got_hi, exp_hi) and torch.equal(got_lo, exp_lo), "backward planes differ from f16_split2 of the f32 output"
 
 
+def test_layernorm_forward_presplit_from_the_convolutions_tile_partials(mode2):
+    """What the default configuration runs: the statistics come from the convolution's tile partials (tile_stats) AND the output is
+    pre-split.  N = 1536 (one ragged chunk), two samples; the partials of three unequal slices of each plane are made here in
+    float64.  The planes are bit for bit f16_split2 of the f32 output of the same partials under the published bound."""
+    hip = mode2
+    shape = (2, 6, 8, 32)
+    B, C = shape[0], shape[3]
+    y = rnd(shape, 1) * 1.7 + 0.3
+    gamma, beta = (1.0 + rnd((C,), 3, 0.2)).cuda(), rnd((C,), 4, 0.2).cuda()
+    rows = []
+    for plane in y.reshape(B, -1).double():
+        parts = plane.split([512, 640, 384])
+        rows.append([[p.numel(), float(p.mean()), float(((p - p.mean()) ** 2).sum()), float((p - p.mean()).abs().max())] for p in parts])
+    ts = torch.tensor(rows, dtype=torch.float64).float().cuda()
+    assert tuple(ts.shape) == (2, 3, 4)
+    yd = y.cuda()
+    a32, a16 = torch.empty_like(yd), torch.full_like(yd, float("nan"))
+    st32, st16 = torch.empty((B, 2), device="cuda"), torch.empty((B, 2), device="cuda")
+    w32, w16 = torch.zeros(1, device="cuda"), torch.zeros(1, device="cuda")
+    hip.ln_elu_fwd(yd, gamma, beta, a32, st32, w32, tile_stats=ts)
+    hip.ln_elu_fwd(yd, gamma, beta, a16, st16, w16, tile_stats=ts, out_s16=True)
+    assert torch.allclose(st16, st32, rtol=1e-6, atol=0)
+    amax, bound = float(w32), float(w16)
+    assert amax <= bound <= 16.0 * amax, (amax, bound)
+    exp_hi, exp_lo = s16_pieces(to_s16(a32.cpu(), bound))
+    got_hi, got_lo = s16_pieces(a16.cpu())
+    assert torch.equal(got_hi, exp_hi) and torch.equal(got_lo, exp_lo), "forward planes differ from f16_split2 of the f32 output"
+
+
 def _weights(hip, Ci, Co, k, lay_f, lay_b, seed):
     w = (rnd((k, k, Ci, Co), seed, 1.0 / math.sqrt(k * k * Ci))).cuda()
     wf = torch.empty((k, k, Co, Ci), device="cuda")
