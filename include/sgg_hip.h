@@ -560,6 +560,37 @@ int sgg_retrieve_topk(const float* scores, long long lds, int Q, int n_images, i
 int sgg_retrieve_ranks(const float* scores, long long lds, int Q, int n_images, const int* rel_ptr, const int* rel_idx, int* ranks,
                        int* first_rank, double* ap, int* status, void* stream);
 
+/* ---- predicate classification: predicates ranked per entity pair, candidates ranked per image (csrc/predcls.hip) -------------
+ * Given the (subject, object) pairs of an image, the likelihood above for EVERY predicate token of every pair, and the two rankings
+ * the PredCls protocol needs.  No entry point uses a workspace, a float atomic or a host read-back, and two calls give the same bits.
+ * sgg_pair_predicate_logp: grid (tile of 256 predicate columns, tile of 16 pairs, image), one thread per column.
+ *   logits, ld, lse, N, nb, V: as sgg_triple_logp takes them (finite logits are a precondition).  pairs int32 [nb][P][2] = (s, o);
+ *   pair_count int32 [nb], clamped to [0, P] on the device.  For a valid pair and a token v: lp_k(v) = (a_0(s) + a_1(v)) + a_2(o),
+ *   m = max_k lp_k, joint(v) = m + (log(sum_k exp(lp_k - m)) - log N), summed in sample order in fp32 - bit for bit sgg_triple_logp's
+ *   mix of (s, v, o).  marg = the same with a_1 = 0.f: the pair's log-probability with the predicate marginalised; joint(v) - marg is
+ *   log p(v | s, o, image).  joint fp32: row j * P + p holds V floats, rows ldj >= V apart (columns >= V are never written);
+ *   marg fp32 [nb][P]; status int32 [nb][P]: 0 valid, -3 padding (p >= pair_count[j]), -4 a token outside [0, V) - the float
+ *   outputs of such a pair hold NaN, nothing is read out of bounds.  The draws are walked twice (maxima, then sums), 64 at a time:
+ *   each predicate row is read once per walk and pair tile.  1 <= N <= 4096, 1 <= P <= 4096, 1 <= nb <= 65535, 1 <= V <= 2^21.
+ * sgg_predcls_pair_topk: one workgroup per (pair, image).  top_tok int32 [nb][P][Kc], top_score fp32 [nb][P][Kc]: the first Kc
+ *   tokens of the pair's joint row under (joint descending, token ascending; +0 and -0 equal) and their scores' own bits; slots
+ *   behind min(Kc, V), and every slot of a pair with status != 0, hold -1 and NaN.  gt_pair int32 [nb][M] (the pair index of true
+ *   triple m, or -1), gt_pred int32 [nb][M] -> gt_rank int32 [nb][M] = 1 + the number of tokens that precede gt_pred in its pair's
+ *   order; 0 where gt_pair is outside [0, P), the pair is not valid or the token lies outside [0, V).  1 <= Kc <= 128,
+ *   1 <= M <= 4096.
+ * sgg_predcls_merge: one workgroup per image.  The candidates are (pair i, slot r < per_pair <= Kc) with top_tok >= 0, scored
+ *   top_score - marg[i] (conditional = 1) or top_score (conditional = 0), ordered by (score descending, i ascending, r ascending);
+ *   the first K: triples int64 [nb][K][3] = (pairs[i][0], token, pairs[i][1]), scores fp32 [nb][K], src int32 [nb][K] =
+ *   i * per_pair + r, n_distinct int32 [nb] = the number of candidates (it may exceed K); slots behind it hold -1 / NaN / -1: the
+ *   layout of sgg_rank_triples, which sgg_match_triples takes.  per_pair = 1 lists one predicate per pair (the graph constraint).
+ *   The pairs of an image must be distinct.  P * per_pair <= 2^21, 1 <= K <= 1024. */
+int sgg_pair_predicate_logp(const float* logits, long long ld, const float* lse, int N, int nb, int V, const int* pairs,
+                            const int* pair_count, int P, float* joint, long long ldj, float* marg, int* status, void* stream);
+int sgg_predcls_pair_topk(const float* joint, long long ldj, const int* status, int nb, int P, int V, int Kc, const int* gt_pair,
+                          const int* gt_pred, int M, int* top_tok, float* top_score, int* gt_rank, void* stream);
+int sgg_predcls_merge(const int* pairs, const int* top_tok, const float* top_score, const float* marg, int nb, int P, int Kc,
+                      int per_pair, int conditional, int K, long long* triples, float* scores, int* src, int* n_distinct, void* stream);
+
 /* ---- relaxed generator output: softmax / Gumbel-softmax rows for the critic, and their gradient (csrc/relax.hip) ---------------
  * The critic's fake rows as points of the probability simplex instead of raw decoder logits.  Neither entry point uses a workspace
  * or a float atomic, and two calls give the same bits.  Rows are any 4-byte alignment; element offsets are 64-bit.  R >= 1,

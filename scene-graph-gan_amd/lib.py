@@ -103,6 +103,9 @@ SIGNATURES = {
     "sgg_query_logp": (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _ll, _ll, _vp]),
     "sgg_retrieve_topk": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _vp]),
     "sgg_retrieve_ranks": (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgg_pair_predicate_logp": (_i, [_vp, _ll, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _ll, _vp, _vp, _vp]),
+    "sgg_predcls_pair_topk": (_i, [_vp, _ll, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "sgg_predcls_merge": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sgg_relax_rows": (_i, [_vp, _ll, _i, _i, _f, _i, _ull, _ull, _vp, _ll, _vp, _ll, _vp]),
     "sgg_relax_rows_bwd": (_i, [_vp, _ll, _vp, _ll, _i, _i, _f, _f, _vp, _ll, _vp]),
     "sgg_relax_rows_hard": (_i, [_vp, _ll, _i, _i, _i, _ull, _ull, _vp, _ll, _vp, _vp]),
@@ -1369,6 +1372,75 @@ class HipKernels:
                                  "ap": ((Q,), torch.float64), "status": ((Q,), torch.int32)}, out, scores.device)
         self._check(self.lib.sgg_retrieve_ranks(_p(sc), lds, Q, n, _p(rel_ptr), _p(rel_idx), _p(res["ranks"]), _p(res["first_rank"]),
                                                 _p(res["ap"]), _p(res["status"]), self._stream()), "sgg_retrieve_ranks")
+        return res
+
+    # -- predicate classification (csrc/predcls.hip; host side and the definitions: sgg_amd/predcls.py) -----------------------
+    def pair_predicate_logp(self, logits, lse, pairs, pair_count, joint=None, out=None):
+        """The mixture log-probability of EVERY predicate token for given (subject, object) pairs (csrc/predcls.hip): logits fp32
+        [N, nb, 3, V], lse fp32 [N, nb, 3], pairs int32 [nb, P, 2], pair_count int32 [nb] -> dict of device tensors: joint fp32
+        [nb, P, V] (bit for bit triple_logp's mix of (s, v, o); `joint`: the caller's [nb, P, >= V] buffer or a column slice of it,
+        rows one stride apart, only its V columns are written), marg fp32 [nb, P] (the pair with the predicate marginalised), status
+        int32 [nb, P] (0 valid, -3 padding, -4 a token outside [0, V); NaN in the floats of a pair that is not valid).
+        1 <= N, P <= 4096.  out: optional dict of preallocated contiguous marg / status."""
+        self._dev(logits, lse, pairs, pair_count, joint)
+        assert logits.dim() == 4 and logits.shape[2] == 3, "logits must be [N, nb, 3, V]"
+        N, nb = int(logits.shape[0]), int(logits.shape[1])
+        x, ld = self._logit_rows(logits)
+        V = int(x.shape[2])
+        assert lse.dtype == torch.float32 and lse.numel() == N * nb * 3 and lse.is_contiguous(), "lse must be contiguous [N, nb, 3]"
+        assert pairs.dtype == torch.int32 and pairs.dim() == 3 and pairs.shape[0] == nb and pairs.shape[2] == 2 and pairs.is_contiguous(), \
+            "pairs must be contiguous int32 [nb, P, 2]"
+        P = int(pairs.shape[1])
+        assert pair_count.dtype == torch.int32 and tuple(pair_count.shape) == (nb,) and pair_count.is_contiguous()
+        if joint is None:
+            joint = torch.empty((nb, P, V), dtype=torch.float32, device=logits.device)
+        assert joint.dim() == 3 and tuple(joint.shape) == (nb, P, V), "joint must be [nb, P, V]"
+        jv, ldj = self._rows(joint, "joint")
+        res = self._out_tensors({"marg": ((nb, P), torch.float32), "status": ((nb, P), torch.int32)}, out, logits.device)
+        self._check(self.lib.sgg_pair_predicate_logp(_p(x), ld, _p(lse), N, nb, V, _p(pairs), _p(pair_count), P, _p(jv), ldj,
+                                                     _p(res["marg"]), _p(res["status"]), self._stream()), "sgg_pair_predicate_logp")
+        res["joint"] = joint
+        return res
+
+    def predcls_pair_topk(self, joint, status, Kc, gt_pair, gt_pred, out=None):
+        """Per pair the first Kc predicate tokens of its joint row under (joint descending, token ascending): joint fp32 [nb, P, V]
+        (rows one stride apart) and status int32 [nb, P] of pair_predicate_logp, gt_pair int32 [nb, M] (the pair of true triple m, or
+        -1), gt_pred int32 [nb, M] -> {"top_tok": int32 [nb, P, Kc], "top_score": fp32 [nb, P, Kc] (the rows' own bits; -1 / NaN
+        behind min(Kc, V) and for a pair that is not valid), "gt_rank": int32 [nb, M] (1 + the tokens ahead of the true predicate in
+        its pair's order; 0 without a valid pair or token)}.  1 <= Kc <= 128, 1 <= M <= 4096.  out: optional preallocated tensors."""
+        self._dev(joint, status, gt_pair, gt_pred)
+        assert joint.dim() == 3, "joint must be [nb, P, V]"
+        nb, P, V = (int(n) for n in joint.shape)
+        jv, ldj = self._rows(joint, "joint")
+        assert status.dtype == torch.int32 and tuple(status.shape) == (nb, P) and status.is_contiguous()
+        M, Kc = int(gt_pair.shape[1]), max(int(Kc), 0)
+        for t in (gt_pair, gt_pred):
+            assert t.dtype == torch.int32 and tuple(t.shape) == (nb, M) and t.is_contiguous(), "gt_pair / gt_pred must be int32 [nb, M]"
+        res = self._out_tensors({"top_tok": ((nb, P, Kc), torch.int32), "top_score": ((nb, P, Kc), torch.float32),
+                                 "gt_rank": ((nb, M), torch.int32)}, out, joint.device)
+        self._check(self.lib.sgg_predcls_pair_topk(_p(jv), ldj, _p(status), nb, P, V, Kc, _p(gt_pair), _p(gt_pred), M, _p(res["top_tok"]),
+                                                   _p(res["top_score"]), _p(res["gt_rank"]), self._stream()), "sgg_predcls_pair_topk")
+        return res
+
+    def predcls_merge(self, pairs, top_tok, top_score, marg, K, per_pair=1, conditional=False, out=None):
+        """The first K (pair, predicate) candidates of every image: pairs int32 [nb, P, 2], top_tok / top_score [nb, P, Kc] of
+        predcls_pair_topk, marg fp32 [nb, P]; the candidates are the slots r < per_pair of every pair with a token >= 0, scored
+        top_score - marg (conditional) or top_score, ordered by (score descending, pair index ascending, r ascending) ->
+        {"triples": int64 [nb, K, 3] = (s, token, o), "scores": fp32 [nb, K], "src": int32 [nb, K] = pair * per_pair + r,
+        "n_distinct": int32 [nb] (the candidates; it may exceed K)}; -1 / NaN / -1 behind them: rank_triples' layout, what
+        match_triples takes.  per_pair = 1: one predicate per pair (the graph constraint).  P * per_pair <= 2^21, 1 <= K <= 1024."""
+        self._dev(pairs, top_tok, top_score, marg)
+        assert pairs.dtype == torch.int32 and pairs.dim() == 3 and pairs.shape[2] == 2 and pairs.is_contiguous(), "pairs must be int32 [nb, P, 2]"
+        nb, P = int(pairs.shape[0]), int(pairs.shape[1])
+        assert top_tok.dtype == torch.int32 and top_tok.dim() == 3 and tuple(top_tok.shape[:2]) == (nb, P) and top_tok.is_contiguous()
+        Kc, K = int(top_tok.shape[2]), max(int(K), 0)
+        assert top_score.dtype == torch.float32 and tuple(top_score.shape) == (nb, P, Kc) and top_score.is_contiguous()
+        assert marg.dtype == torch.float32 and tuple(marg.shape) == (nb, P) and marg.is_contiguous()
+        res = self._out_tensors({"triples": ((nb, K, 3), torch.int64), "scores": ((nb, K), torch.float32), "src": ((nb, K), torch.int32),
+                                 "n_distinct": ((nb,), torch.int32)}, out, pairs.device)
+        self._check(self.lib.sgg_predcls_merge(_p(pairs), _p(top_tok), _p(top_score), _p(marg), nb, P, Kc, int(per_pair),
+                                               int(bool(conditional)), K, _p(res["triples"]), _p(res["scores"]), _p(res["src"]),
+                                               _p(res["n_distinct"]), self._stream()), "sgg_predcls_merge")
         return res
 
     # -- relaxed generator output (csrc/relax.hip) ---------------------------------------------------------------

@@ -45,6 +45,7 @@ from sgg_amd import dp as dpmod
 from sgg_amd import ground as groundmod
 from sgg_amd import guard as guardmod
 from sgg_amd import kbest as kbestmod
+from sgg_amd import predcls as pclsmod
 from sgg_amd import retrieve as retrmod
 from sgg_amd.api import kernels_for
 from sgg_amd.augment import AugmentSpec, flip_swap_table
@@ -1561,6 +1562,159 @@ class SceneGraphGAN(object):
                     json.dump(res, f, indent=1)
             return res
 
+    ############################################################
+    ## Predicate classification: predicates ranked per entity pair (csrc/predcls.hip, sgg_amd/predcls.py)
+    ############################################################
+    def predcls(self, items=None, max_images=None, ks=(20, 50, 100), n_samples=None, pairs="all", score="joint", train_triples=None,
+                return_details=False, out_path=None, logits_budget_bytes=DEFAULT_LOGITS_BUDGET_BYTES):
+        """The PredCls protocol of the scene-graph literature: the ENTITIES of an image are given (the distinct subject / object words
+        of its true triples), the model says which ordered pairs are related and by which predicate.  Every candidate (s, v, o) is
+        scored exactly by the likelihood of likelihood() / retrieve() - the mixture over the image's n_samples noise draws (default
+        TEST_BATCH_MULTIPLIER x TEST_BATCH_SIZE) - for ALL V predicates of every candidate pair; sgg_amd/predcls.py has the
+        definitions.  The critic is not run.
+
+        items, train_triples: as evaluate().  pairs: "all" (every ordered pair of two different entities plus the true self pairs) or
+        "gt" (the true pairs only: predicate detection).  score: "joint" (log p(s, v, o | image): the exact ranking of the mixture
+        over the candidates) or "conditional" (log p(v | s, o, image), the literature's score).  ks: at most 1024.
+
+        Schedule: the passes and the noise stream of likelihood().  Per batch one copy to the device (pairs, counts, the padded
+        ground truth, each true triple's pair index and predicate); K.softmax_xent (lse only); per chunk of pairs - the joint
+        buffer [nb, Pc, V] stays within a quarter of the logits budget - K.pair_predicate_logp and K.predcls_pair_topk; then
+        K.predcls_merge and K.match_triples once per constraint mode (one predicate per pair / up to predicates_per_pair =
+        min(128, V, max(ks)) of them: exact while max(ks) <= 128), and one copy back.
+
+        Returns (rank 0 writes it as JSON to out_path): graph_constraint and no_graph_constraint (each a RecallAccumulator.result():
+        R@K, mR@K, zsR@K), predicate_given_pair (top1, top5, mean_rank and mean_predicate_top1 of the true predicate among all V
+        predicates of its own pair, over the distinct valid true triples), ks, pairs, score, samples_per_image, predicates_per_pair,
+        mean_pairs_per_image, n_images_truncated (images with more than 4096 candidate pairs: the true pairs are kept),
+        generator_weights, definition and, with return_details, details: per image {"image", "n_pairs", "gt_rank", and per mode
+        "triples", "scores", "pos", "n_gt", "n_candidates"}.  A ground-truth list of more than 4096 triples or a token outside the
+        vocabulary raises ValueError before anything is launched.  Touches no weights and no optimiser state."""
+        pclsmod.check_args(pairs, score)
+        with self._eval_weights() as weights:
+            ks = tuple(sorted(set(int(k) for k in ks)))
+            if not ks or ks[0] < 1 or ks[-1] > pclsmod.MAX_K:
+                raise ValueError("predcls: ks must be integers in 1..%d (got %r)" % (pclsmod.MAX_K, ks))
+            items = self._evaluate_items(items, max_images)
+            V = len(self.vocab)
+            for key, _, real in items:
+                if len(real) > MAX_GT:
+                    raise ValueError("predcls: image %s has %d ground-truth triples (at most %d per image)" % (key, len(real), MAX_GT))
+                for t in real:
+                    if len(t) != 3 or not all(0 <= x < V for x in t):
+                        raise ValueError("predcls: image %s: ground-truth triple %r is not three tokens in [0, %d)" % (key, list(t), V))
+            if train_triples is None and self.dataset is not None:
+                train_triples = set(map(tuple, np.concatenate([self.dataset["train"][1], self.dataset["val"][1]]).tolist()))
+            K, V, TB, N, _ = self._sampling_setup("predcls", n_samples, None)
+            modes = ("graph_constraint", "no_graph_constraint")
+            acc = {mode: RecallAccumulator(ks, V) for mode in modes}
+            pacc = pclsmod.PredicateAccumulator(V)
+            top_k, Kc = max(ks), min(pclsmod.MAX_KC, V, max(ks))
+            cand = [pclsmod.candidate_pairs(real, pairs) for _, _, real in items]
+            details = []
+            if items:
+                need_kernels(K, "predcls", "pair_predicate_logp", "predcls_pair_topk", "predcls_merge", "match_triples")
+                dev = self.device
+                nb = images_per_pass(N, V, TB, len(items), logits_budget_bytes)
+                M = max(1, max(len(real) for _, _, real in items))
+                P = max(1, max(len(c) for c, _ in cand))
+                Pc, n_chunks = pclsmod.pair_chunk(P, nb, V, logits_budget_bytes)
+                Pp = Pc * n_chunks                              # (the pairs behind an image's count are padding: status -3)
+                per_pair = {"graph_constraint": 1, "no_graph_constraint": Kc}
+                in_parts = [("gt", np.int64, (nb, M, 3)), ("pairs", np.int32, (nb, Pp, 2)), ("pairs_c", np.int32, (n_chunks, nb, Pc, 2)),
+                            ("count_c", np.int32, (n_chunks, nb)), ("gt_count", np.int32, (nb,)),
+                            ("gt_pair_c", np.int32, (n_chunks, nb, M)), ("gt_pred", np.int32, (nb, M))]
+                in_host, _, in_views = self._device_pack(in_parts, "cpu")
+                h_in = in_views(in_host.numpy())                # (numpy views of the host buffer: filled in place)
+                in_packed, d_in, _ = self._device_pack(in_parts, dev)
+                back_parts = [("gt_rank", np.int32, (nb, M))]
+                for mode in modes:
+                    back_parts += [(mode + "/triples", np.int64, (nb, top_k, 3)), (mode + "/scores", np.float32, (nb, top_k)),
+                                   (mode + "/src", np.int32, (nb, top_k)), (mode + "/n_distinct", np.int32, (nb,)),
+                                   (mode + "/pos", np.int32, (nb, M)), (mode + "/n_gt", np.int32, (nb,))]
+                packed, back, views = self._device_pack(back_parts, dev)
+                joint = torch.empty((nb, Pc, V), dtype=torch.float32, device=dev)
+                full = {"marg": torch.empty((nb, Pp), dtype=torch.float32, device=dev),
+                        "top_tok": torch.empty((nb, Pp, Kc), dtype=torch.int32, device=dev),
+                        "top_score": torch.empty((nb, Pp, Kc), dtype=torch.float32, device=dev)}
+                status = torch.empty((nb, Pc), dtype=torch.int32, device=dev)
+                part = full if n_chunks == 1 else {"marg": torch.empty((nb, Pc), dtype=torch.float32, device=dev),
+                                                   "top_tok": torch.empty((nb, Pc, Kc), dtype=torch.int32, device=dev),
+                                                   "top_score": torch.empty((nb, Pc, Kc), dtype=torch.float32, device=dev),
+                                                   "gt_rank": torch.empty((nb, M), dtype=torch.int32, device=dev)}
+                lse = torch.empty((N, nb, 3), dtype=torch.float32, device=dev)
+                with contextlib.closing(self._sample_batches([(key, x) for key, x, _ in items], N, nb)) as batches:
+                    for i0, n, images, logits in batches:
+                        for a in h_in.values():
+                            a[...] = 0
+                        h_in["gt_pair_c"][...] = -1             # (the padded images of the last batch: no pairs, no ground truth)
+                        for j in range(n):
+                            real, (pr, _) = items[i0 + j][2], cand[i0 + j]
+                            if not len(real):
+                                continue
+                            g = np.asarray(real, dtype=np.int64).reshape(-1, 3)
+                            h_in["gt"][j, :len(g)] = g
+                            h_in["gt_count"][j] = len(g)
+                            h_in["gt_pred"][j, :len(g)] = g[:, 1]
+                            h_in["pairs"][j, :len(pr)] = pr
+                            where = pclsmod.gt_pair_index(pr, real)
+                            for c in range(n_chunks):
+                                own = pr[c * Pc:(c + 1) * Pc]
+                                h_in["pairs_c"][c, j, :len(own)] = own
+                                h_in["count_c"][c, j] = len(own)
+                                h_in["gt_pair_c"][c, j, :len(g)] = np.where((where >= c * Pc) & (where < (c + 1) * Pc), where - c * Pc, -1)
+                        in_packed.copy_(in_host)
+                        K.softmax_xent(logits, None, lse=lse.view(-1))
+                        for c in range(n_chunks):
+                            K.pair_predicate_logp(logits, lse, d_in["pairs_c"][c], d_in["count_c"][c], joint=joint,
+                                                  out={"marg": part["marg"], "status": status})
+                            K.predcls_pair_topk(joint, status, Kc, d_in["gt_pair_c"][c], d_in["gt_pred"],
+                                                out={"top_tok": part["top_tok"], "top_score": part["top_score"],
+                                                     "gt_rank": back["gt_rank"] if n_chunks == 1 else part["gt_rank"]})
+                            if n_chunks > 1:                    # (a true triple's pair lies in one chunk: the others report rank 0)
+                                for name in full:
+                                    full[name][:, c * Pc:(c + 1) * Pc].copy_(part[name])
+                                if c == 0:
+                                    back["gt_rank"].copy_(part["gt_rank"])
+                                else:
+                                    back["gt_rank"].add_(part["gt_rank"])
+                        for mode in modes:
+                            out = {name: back[mode + "/" + name] for name in ("triples", "scores", "src", "n_distinct")}
+                            K.predcls_merge(d_in["pairs"], full["top_tok"], full["top_score"], full["marg"], top_k,
+                                            per_pair=per_pair[mode], conditional=score == "conditional", out=out)
+                            K.match_triples(out["triples"], out["n_distinct"], d_in["gt"], d_in["gt_count"], vocab=V,
+                                            out={"pos": back[mode + "/pos"], "n_gt": back[mode + "/n_gt"]})
+                        h = views(packed.cpu().numpy())
+                        for j in range(n):
+                            key, _, real = items[i0 + j]
+                            zs = None if train_triples is None else zero_shot_mask(real, train_triples)
+                            rank = h["gt_rank"][j, :len(real)].copy()
+                            for mode in modes:
+                                acc[mode].add(h[mode + "/pos"][j, :len(real)], real, zs)
+                            keep = h[modes[0] + "/pos"][j, :len(real)] >= -1       # (the distinct valid true triples, as R@K counts them)
+                            pacc.add(rank[keep], np.asarray(real, dtype=np.int64).reshape(-1, 3)[keep])
+                            if return_details:
+                                d = {"image": key, "n_pairs": int(len(cand[i0 + j][0])), "gt_rank": rank.tolist()}
+                                for mode in modes:
+                                    u = min(int(h[mode + "/n_distinct"][j]), top_k)
+                                    d[mode] = {"triples": h[mode + "/triples"][j, :u].tolist(),
+                                               "scores": [float(s) for s in h[mode + "/scores"][j, :u]],
+                                               "pos": h[mode + "/pos"][j, :len(real)].tolist(), "n_gt": int(h[mode + "/n_gt"][j]),
+                                               "n_candidates": int(h[mode + "/n_distinct"][j])}
+                                details.append(d)
+            res = {mode: acc[mode].result(self.reverse_vocab) for mode in modes}
+            res.update({"predicate_given_pair": pacc.result(), "ks": list(ks), "pairs": pairs, "score": score, "samples_per_image": N,
+                        "predicates_per_pair": Kc,
+                        "mean_pairs_per_image": float(np.mean([len(c) for c, _ in cand])) if cand else None,
+                        "n_images_truncated": int(sum(t for _, t in cand)), "generator_weights": weights,
+                        "definition": pclsmod.DEFINITION})
+            if return_details:
+                res["details"] = details
+            if self.rank == 0 and out_path:
+                with open(out_path, "w") as f:
+                    json.dump(res, f, indent=1)
+            return res
+
 
 def _str2bool(v):
     """--resume of the reference is `type=bool` (train.py:410), which makes every non-empty string - "False" included - true."""
@@ -1636,6 +1790,16 @@ def build_parser():
                         help="load the checkpoint in --checkpoints_dir, write R@K, mR@K and zsR@K of the test images (distinct "
                              "predictions, denominators |GT|) as JSON to this file and exit; no training")
     parser.add_argument("--metrics_k", default="20,50,100", help="the K values of --metrics_out, comma-separated")
+    parser.add_argument("--predcls_out", default=None,
+                        help="load the checkpoint in --checkpoints_dir, write predicate classification (PredCls: the entities of an "
+                             "image given, predicates ranked per entity pair by the generator's likelihood; R@K, mR@K, zsR@K with and "
+                             "without the graph constraint, predicate accuracy given the true pair) of the test images as JSON to this "
+                             "file and exit; no training (--max_test_images, --predict_samples and --eval_live apply)")
+    parser.add_argument("--predcls_k", default=None, help="with --predcls_out: the K values, comma-separated in 1..1024 (default 20,50,100)")
+    parser.add_argument("--predcls_pairs", default=None, choices=pclsmod.PAIR_MODES,
+                        help="with --predcls_out: all = every ordered pair of two different entities (default); gt = the true pairs only")
+    parser.add_argument("--predcls_score", default=None, choices=pclsmod.SCORES,
+                        help="with --predcls_out: joint = log p(s, v, o | image) (default); conditional = log p(v | s, o, image)")
     parser.add_argument("--diagnostics_every", default=0, type=int,
                         help="every N iterations, report per-tensor gradient / parameter / update norms and non-finite counts of both "
                              "networks and the critic's gradient-penalty slopes: summary under \"diag\" in losses.jsonl, per-tensor table in "
@@ -1760,6 +1924,19 @@ def parse_args(argv=None):
         for flag in ("likelihood_out", "saliency_dir", "predict_dir", "metrics_out", "test_only"):
             if getattr(args, flag):
                 parser.error("--retrieve_out is a run of its own: not together with --%s" % flag)
+    for flag in ("predcls_k", "predcls_pairs", "predcls_score"):
+        if getattr(args, flag) is not None and not args.predcls_out:
+            parser.error("--%s needs --predcls_out" % flag)
+    if args.predcls_out:
+        for flag in ("retrieve_out", "likelihood_out", "saliency_dir", "predict_dir", "metrics_out", "test_only"):
+            if getattr(args, flag):
+                parser.error("--predcls_out is a run of its own: not together with --%s" % flag)
+        try:
+            args.predcls_k = tuple(int(k) for k in (args.predcls_k or "20,50,100").split(",") if k.strip())
+        except ValueError:
+            parser.error("--predcls_k must be comma-separated integers (got %r)" % args.predcls_k)
+        if not args.predcls_k or min(args.predcls_k) < 1 or max(args.predcls_k) > pclsmod.MAX_K:
+            parser.error("--predcls_k must be integers in 1..%d" % pclsmod.MAX_K)
     if args.retrieve_top is not None and not 1 <= args.retrieve_top <= retrmod.MAX_TOP:
         parser.error("--retrieve_top must be in 1..%d" % retrmod.MAX_TOP)
     if args.retrieve_max_queries is not None and args.retrieve_max_queries < 1:
@@ -1827,6 +2004,17 @@ if __name__ == "__main__":
                            return_details=True, out_path=params["retrieve_out"])
         if gan.rank == 0:
             print({k: v for k, v in res.items() if k != "details"})
+    elif params["predcls_out"]:
+        if not gan.load_checkpoint():
+            print("--predcls_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
+                  file=sys.stderr)
+            sys.exit(2)
+        res = gan.predcls(max_images=params["max_test_images"], ks=params["predcls_k"], n_samples=params["predict_samples"],
+                          pairs=params["predcls_pairs"] or "all", score=params["predcls_score"] or "joint", return_details=True,
+                          out_path=params["predcls_out"])
+        if gan.rank == 0:
+            print({k: ({a: b for a, b in v.items() if a != "predicates"} if isinstance(v, dict) else v)
+                   for k, v in res.items() if k not in ("details", "definition")})
     elif params["likelihood_out"]:
         if not gan.load_checkpoint():
             print("--likelihood_out: no checkpoint at %s (train first, or pass the run's --checkpoints_dir)" % gan._ckpt_path(),
