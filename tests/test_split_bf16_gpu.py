@@ -49,7 +49,8 @@ def test_modes_agree_at_full_layer_shapes(hip):
 def test_training_trajectory_default_mode_tracks_native_f32(hip):
     """Ten G+D iterations (critic_iters = 2, fresh noise / alpha per update) from the same weights in the default f16x3 mode and in
     native f32 MFMA arithmetic: the loss trajectories stay together (Adam amplifies rounding differences step by step: the bound
-    grows with the iteration).  configs[0] shapes; the penalty is active (embedding scaled)."""
+    grows with the iteration).  configs[0] shapes; the penalty is active (embedding scaled).  Both sides are the library: past the first
+    update against the fp64 oracle: tests/test_trajectory_gpu.py."""
     B, S, V, iters, ci = 8, 64, 50, 10, 2
     images, labels, _ = O.synth_batch(B, S, V)
     gsd, dsd = init_state_dict("G", V, S), init_state_dict("D", V, S)

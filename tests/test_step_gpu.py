@@ -6,6 +6,8 @@ Tolerances (fp32 on both sides, different summation orders):
   logits                          : |d| <= 1e-5 + 1e-5*max|ref|
   gradients                       : max|d| <= 2e-4 * max|ref| per tensor (+ floor 1e-7)
   arg-maxed triple tokens         : exact; the seeds' minimum top-2 logit margin exceeds 4x the logit tolerance
+
+Every comparison here is a first update from fresh state (t = 1, m = v = 0); past the first update: tests/test_trajectory_gpu.py.
 """
 import pytest
 import torch
